@@ -4,11 +4,19 @@
 A "step" = one pass of the hot path over one batch: solve B = 4096 independent N = 20 NMPC problems
 (BASELINE.json configs[2]: constant f_ext, 6-face tightened corridor per stage, cold start) with the
 HIP solver, inputs already resident in HBM, outputs left in HBM, strictly serial launches on one stream; the K-step
-region is timed 5 times and the median reported (config.pipelined_solves_per_s: the same steps round-robin on 2 streams,
-informational).  N GPUs -> each rank solves its own 4096-problem shard (different seed), no data-path collective ("weak").
---scaling strong / --config 3 / --config 4: the other BASELINE configs and the scatter -> solve -> gather form of SURVEY 8e.
+region is timed once (exactly K timed steps).  N GPUs -> each rank solves its own 4096-problem shard (different seed), no
+data-path collective ("weak").  --scaling strong / --config 3 / --config 4: the other BASELINE configs and the
+scatter -> solve -> gather form of SURVEY 8e.
 
-  python bench.py --gpus 1 --steps 20 --warmup 3
+--full adds everything beyond the headline figure: the K-step region timed 5 times and the median reported, the solver
+kernel's own duration and the roofline, the same steps round-robin on 2 streams (config.pipelined_solves_per_s), the
+per-phase times of a strong-scaling step and -- unless --no-cpu -- the CPU baseline, the end-to-end host-buffer legs, the
+drop-in latency and the full planner tick.
+
+--dump-outputs DIR writes what the timed path returned in its last step (rank 0) as DIR/<name>.npy, float64; outputs
+above 64 MB in all are cut to a fixed, seeded sample of problems (DIR/sample_index.npy).
+
+  python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 
@@ -226,6 +234,24 @@ def launch_plan(args):
     return plan
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, seed=20240607):
+    """arrays: name -> float64 array with the problems on axis 0.  Written as d/<name>.npy; when they hold more than
+    DUMP_LIMIT_BYTES together, the same fixed, seeded sample of problems is taken from each (d/sample_index.npy)."""
+    os.makedirs(d, exist_ok=True)
+    n = min(a.shape[0] for a in arrays.values())
+    per_problem = sum(a[:1].nbytes for a in arrays.values())
+    if n * per_problem > DUMP_LIMIT_BYTES:
+        k = int(DUMP_LIMIT_BYTES // (per_problem + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -239,13 +265,16 @@ def main():
                     help="weak: every rank solves its own batch (no data-path communication).  strong: rank 0 owns the whole batch in "
                          "HBM; every step scatters the shards (grouped RCCL send/recv), solves, gathers the plans back (SURVEY 8e); "
                          "configs[4]: one nominal problem is broadcast, the samples are drawn on every rank's device")
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step region is timed this many times; the MEDIAN is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="the K-step region is timed this many times; the MEDIAN is reported (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: repeats of the timed region, kernel time and roofline, the 2-stream rate, "
+                    "strong-scaling phases and (unless --no-cpu) the CPU baseline / end-to-end / drop-in latency / full-tick legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--no-order-hint", action="store_true", help="configs[4]: queue the problems by the cost of the initial guess instead of by the previous tick's iteration counts")
     ap.add_argument("--mu0", type=float, default=None, help="frp_nmpc_options.mu0, the barrier parameter the interior-point iteration starts from (default: the library's 1.0); "
                     "a caller of warm-started problems (configs[4], the device tick) lowers it; set for the GPU and for the CPU baseline alike, named in config")
     ap.add_argument("--twist", type=int, default=0, help="frp_nmpc_options.twist: stages the model wave eliminates forward while the Riccati wave runs the rest backward "
                     "(0 = the plain solve, -1 = 9 N / 20 up to 1024 problems and 3 N / 10 beyond; N <= 20 only; DESIGN 9.1)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / end-to-end / drop-in latency legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline / end-to-end / drop-in latency legs")
     ap.add_argument("--chunks", type=int, default=0, help="--scaling strong: pieces every shard is cut into so that transfers overlap the solve (1 = serial scatter -> "
                     "solve -> gather; 0 = auto: 2 when there is more than one rank and a shard holds at least two rounds of resident workgroups, else 1 -- measured on "
                     "one GPU, where nothing is transferred: a piece smaller than a round of resident workgroups costs more than it hides, profiles/r04_strong_chunks.txt)")
@@ -255,6 +284,8 @@ def main():
                     help="informational: `value` is always the strictly serial single-stream rate; the rate with the steps issued "
                          "round-robin on 2 streams (the tail of one launch overlapping the next) is reported in config.pipelined_*")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.dry_run:
         print(json.dumps(launch_plan(args)))
         return
@@ -372,7 +403,7 @@ def main():
         ticks = args.warmup + args.steps * (args.repeats + 2) + 4
         w1 = workloads.config4_nominal(1, ticks=ticks)
         N, M, model = w1["N"], w1["M"], w1["model"]
-        wcpu = workloads.config4_nominal(min(B_total, 4096), ticks=1)
+        wcpu = workloads.config4_nominal(min(B_total, 4096), ticks=1) if args.full else None  # (the CPU baseline's problems)
         # one nominal problem from rank 0 to everybody (a few KB), the samples drawn where they are used
         nominal = [torch.from_numpy(np.ascontiguousarray(w1[k])).to(dev) for k in ("mpc_output", "E")]
         fbar = torch.from_numpy(np.ascontiguousarray(w1["f_ext"].mean(0))).to(dev)
@@ -428,14 +459,29 @@ def main():
     # the dominant kernel's duration comes from THE SAME launches as ms_per_step: a hipEvent pair around the solver kernel of
     # every 4th launch of the timed regions, on the launch stream (frp_nmpc_kernel_timing_*), read after the last region
     # (a pair costs its launch ~8 us of queue bubbles: observing every launch would slow the region it measures by 0.8 %)
+    # (--full only: a plain run times its steps without the event pairs)
     nrep = max(1, args.repeats)
     ev_stride = 4 if nrep * args.steps >= 16 and not strong else 1   # (strong scaling: a step is several piece launches, all of them timed)
-    solver.kernel_timing_begin((nrep * args.steps + 8) * (max(1, args.chunks) if strong else 1), ev_stride)
+    if args.full:
+        solver.kernel_timing_begin((nrep * args.steps + 8) * (max(1, args.chunks) if strong else 1), ev_stride)
     if cfg == 4:
         it_acc.zero_()
     reps = [timed(step, args.steps) for _ in range(nrep)]
     timed_ticks_it = [int(x) for x in it_acc.cpu()] if cfg == 4 else None  # [sum of iterations over the timed ticks, ticks]
-    kernel_ms, kernel_launches = solver.kernel_timing_end()
+    # what a caller of the timed path receives from its last step, taken before anything below runs the solver again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if cfg == 4:
+            res = {"mpc_output": fleet.mpc_output, "z": ds.z, "exitflag": ds.exitflag, "iters": ds.iters, "info": ds.info}
+            nres = B
+        elif strong:
+            res = {"z": full_out[0], "exitflag": full_out[1], "iters": full_out[2]}
+            nres = B_total
+        else:
+            res = {"z": ds.z, "exitflag": ds.exitflag, "iters": ds.iters, "info": ds.info}
+            nres = B
+        dumped = {k: v[:nres].double().cpu().numpy() for k, v in res.items()}
+    kernel_ms, kernel_launches = solver.kernel_timing_end() if args.full else (0.0, 0)
     if strong and kernel_launches:  # per step: the sum over the pieces of this rank's shard
         kernel_ms = kernel_ms * kernel_launches / (nrep * args.steps)
     per_rank_s = [float(np.median(reps))]  # this rank's own median region time (before the max over ranks)
@@ -452,7 +498,7 @@ def main():
 
     # informational: the same steps issued round-robin on two streams (own solver state / outputs each)
     pipelined = None
-    if cfg in (2, 3) and not strong:
+    if args.full and cfg in (2, 3) and not strong:
         d2 = solver.DeviceSolver(B, N, M, ds.MF, model, f"cuda:{local_rank}")
         d2.xinit, d2.x0, d2.params, d2.nfaces = ds.xinit, ds.x0, ds.params, ds.nfaces
         d2.opt = ds.opt
@@ -471,7 +517,7 @@ def main():
 
     # per-phase times of a strong-scaling step (not inside the timed region: each phase is bracketed by a barrier here)
     phase_ms = None
-    if phases is not None:
+    if args.full and phases is not None:
         acc = [0.0, 0.0, 0.0]
         for _ in range(5):
             for i, ph in enumerate(phases):
@@ -516,7 +562,7 @@ def main():
         alg_bytes = 8.0 * (9 + 17 * N + N * (10 + 4 * M) + 1) + 8.0 * 17 * N + 136.0  # dense ABI image of one solve: params + output + info (26 456 B at N = 20, M = 30)
         achieved_gbs = B * alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
         kname = "nmpc_ipm_lds_kernel"
-        traffic, traffic_src = pmc_traffic(B, kname) if cfg == 2 else (None, None)
+        traffic, traffic_src = pmc_traffic(B, kname) if cfg == 2 and args.full else (None, None)
         names = {2: "BASELINE.json configs[2]: N=20, constant f_ext~U[-3,3]^3, 6-face tightened corridor per stage, cold start, reference 30-row parameter layout",
                  3: "BASELINE.json configs[3]: N=30, time-varying f_ext, per-stage polytopes with <=15 faces, cold start",
                  4: "BASELINE.json configs[4]: Monte-Carlo f_ext~N(fbar,0.5^2 I) around one nominal problem, N=20, warm-started receding horizon, one step = one tick (pack + solve + update on the device)"}
@@ -531,7 +577,7 @@ def main():
                        "per_rank_solves_per_s": ([B_total / max(1, ranks_seen) * args.steps / x for x in per_rank_s] if not strong else None), "collectives": ("RCCL (torch.distributed nccl backend)" if dist is not None else "none (single process)"),
                        "batch_per_gpu": B, "batch_total": B_total, "horizon": int(N), "converged_frac": conv_frac,
                        "mean_ipm_iterations": mean_it, **({"mean_ipm_iterations_note": "mean over the timed ticks (what the rate and the kernel time average over); p95 / max / redos: the last tick"} if cfg == 4 else {}), "mean_gauss_newton_redos": float(stats[4] / stats[2]), "max_ipm_iterations": int(stats[3]), "p95_ipm_iterations": float(np.percentile(it, 95)) if len(it) else 0.0,
-                       "timing": f"median of {len(reps)} repeats of the {args.steps}-step region, strictly serial launches on one stream; max over ranks per repeat",
+                       "timing": (f"median of {len(reps)} repeats" if len(reps) > 1 else "one timing") + f" of the {args.steps}-step region, strictly serial launches on one stream; max over ranks per repeat",
                        "repeat_ms_per_step": [r / args.steps * 1e3 for r in reps],
                        "pipelined_solves_per_s": pipelined,
                        "pipelined_note": "the same steps issued round-robin on 2 HIP streams (the few long solves at the end of a launch overlap the head of the next); informational, never `value`",
@@ -551,7 +597,9 @@ def main():
         }
         if phase_ms is not None:
             out["config"]["strong_scaling_phases"] = phase_ms
-        if not args.no_cpu and world == 1 and not strong and cfg == 2:
+        if not args.full:  # a plain run: the headline figure and the statistics of its own steps
+            del out["roofline"], out["config"]["pipelined_solves_per_s"], out["config"]["pipelined_note"]
+        if args.full and not args.no_cpu and world == 1 and not strong and cfg == 2:
             # secondary timings of SURVEY 8d (never `value`): host buffers in and out, and the single-problem drop-in call
             outs = solver.solve_batch_host(wcpu)
             e2e = []
@@ -673,11 +721,13 @@ def main():
                                                             "plans_vs_default_mu0": fw["plans_vs_default_mu0"]}
             except Exception as e:  # secondary evidence, never a reason to lose the bench line
                 out["full_tick"] = {"error": repr(e)}
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(wcpu, diverge_mu=float(ds.opt.diverge_mu), mu0=float(ds.opt.mu0))
-        elif not args.no_cpu:
+        elif args.full and not args.no_cpu:
             out["cpu_baseline"] = None
         line = json.dumps(out)
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

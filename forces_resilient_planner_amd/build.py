@@ -186,14 +186,14 @@ def build_dropin_archives(verbose=False):
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
         out.append(dst)
-    # when the reference tree is here (build container): a stand-in for plan_manage's link line -- a program compiled against the
-    # REFERENCE's generated headers, linked by plain g++ against the two archives + the HIP runtime; -m gpu tests run it on the box
-    ref_inc = ["/root/reference/src/resilient_planner/plan_manage/solver/%s/FORCESNLPsolver_%s/include" % (m, m) for m in ("normal", "final")]
-    stub_src = os.path.join(ROOT, "tests", "cpp", "static_dropin_stub.cpp")
+    # when the oracle recipe compiled tests/cpp/static_dropin_stub.cpp against the REFERENCE's generated headers (oracle/_ref, see
+    # oracle/Makefile): a stand-in for plan_manage's link line -- that object linked by plain g++ against the two archives + the HIP
+    # runtime; -m gpu tests run it on the box
+    stub_obj = os.path.join(ROOT, "oracle", "_ref", "static_dropin_stub.o")
     stub = os.path.join(os.path.dirname(DROPIN_DIR), "planner_stub")
-    if all(os.path.isdir(d) for d in ref_inc) and os.path.exists(stub_src) and _stale(stub, out + [stub_src]):
+    if os.path.exists(stub_obj) and _stale(stub, out + [stub_obj]):
         rocm = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "lib")
-        subprocess.check_call(["g++", "-O1", "-I" + ref_inc[0], "-I" + ref_inc[1], stub_src, "-L" + DROPIN_DIR, "-l:libFORCESNLPsolver_normal.a",
+        subprocess.check_call(["g++", stub_obj, "-L" + DROPIN_DIR, "-l:libFORCESNLPsolver_normal.a",
                                "-l:libFORCESNLPsolver_final.a", "-L" + rocm, "-lamdhip64", "-lpthread", "-Wl,-rpath," + rocm, "-o", stub])
     return out
 
@@ -244,7 +244,7 @@ def build_ubench(verbose=True):
 
 
 def build_oracle(verbose=True):
-    """Test infrastructure: oracle/liboracle.so and, when /root/reference is present, oracle/_ref."""
+    """Test infrastructure: oracle/liboracle.so and, when the reference tree is present, oracle/_ref."""
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "all"],
                           stdout=None if verbose else subprocess.DEVNULL)
 

@@ -1,10 +1,19 @@
 // A stand-in for plan_manage's link line (plan_manage/CMakeLists.txt:64-65, 82-83): compiled against the REFERENCE's generated
 // headers, linked by plain g++ against libFORCESNLPsolver_normal.a / libFORCESNLPsolver_final.a (this repo's archives under the
 // reference's file names) + the HIP runtime.  argv[1] = a file holding a FORCESNLPsolver_normal_params image (optional).
+// Built by the oracle recipe (oracle/Makefile, target ref) where the reference tree is; with -DFRP_STUB_OWN_HEADER against
+// include/frp_nmpc.h instead, whose structs are layout-identical (tests/golden/reference_abi.json, tests/test_capi_cpu.py).
 #include <cstdio>
 #include <cstring>
+#ifdef FRP_STUB_OWN_HEADER
+#include "frp_nmpc.h"
+#define FRP_STUB_TYPES(R) typedef frp_forces_params R##_params; typedef frp_forces_output R##_output; typedef frp_forces_info R##_info;
+FRP_STUB_TYPES(FORCESNLPsolver_normal)
+FRP_STUB_TYPES(FORCESNLPsolver_final)
+#else
 #include "FORCESNLPsolver_normal.h"
 #include "FORCESNLPsolver_final.h"
+#endif
 int main(int argc, char **argv)
 {
     static FORCESNLPsolver_normal_params p; static FORCESNLPsolver_normal_output o; static FORCESNLPsolver_normal_info i;

@@ -11,16 +11,36 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*flags, dist=False):
-    env = dict(os.environ)
-    if dist:
-        env.update(FRP_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--repeats", "2", "--no-cpu", *flags],
-                       capture_output=True, text=True, env=env, timeout=600)
+def _run(args, env=None):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def _bench(*flags, dist=False):
+    """--full: the tests below check the legs beyond the headline figure."""
+    env = dict(os.environ)
+    if dist:
+        env.update(FRP_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
+    return _run(["--steps", "2", "--warmup", "1", "--repeats", "2", "--full", "--no-cpu", *flags], env)
+
+
+def test_plain_line_times_exactly_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run: one timed region of --steps steps, the headline fields, no secondary legs; --dump-outputs writes the plans,
+    exit flags, iteration counts and info rows of the last timed step as float64 .npy files."""
+    import numpy as np
+    d = _run(["--steps", "3", "--warmup", "1", "--batch", "512", "--dump-outputs", str(tmp_path)])
+    assert d["unit"] == "solves/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 3
+    assert len(d["config"]["repeat_ms_per_step"]) == 1 and d["ms_per_step"] == d["config"]["repeat_ms_per_step"][0]
+    assert abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert "roofline" not in d and "cpu_baseline" not in d and "end_to_end" not in d and "pipelined_solves_per_s" not in d["config"]
+    out = {n: np.load(tmp_path / (n + ".npy")) for n in ("z", "exitflag", "iters", "info")}
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert out["z"].shape == (512, 20, 17) and out["exitflag"].shape == (512,) and out["info"].shape[0] == 512
+    assert np.isfinite(out["z"]).all() and (out["exitflag"] == 1).mean() == d["config"]["converged_frac"]
+    assert out["iters"].max() == d["config"]["max_ipm_iterations"]
 
 
 def test_default_line_is_the_serial_single_stream_rate():

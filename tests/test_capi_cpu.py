@@ -45,68 +45,57 @@ def test_dropin_struct_layouts_match_reference_sizes():
     assert solver.ForcesInfo.res_eq.offset == 8 and solver.ForcesInfo.solvetime.offset == 120
 
 
-REF_INC = "/root/reference/src/resilient_planner/plan_manage/solver/{m}/FORCESNLPsolver_{m}/include"
+REFERENCE_ABI = os.path.join(ROOT, "tests", "golden", "reference_abi.json")
+OWN = {"params": "frp_forces_params", "output": "frp_forces_output", "info": "frp_forces_info"}
+OWN_EXIT = {"OPTIMAL": "FRP_EXIT_OPTIMAL", "MAXITREACHED": "FRP_EXIT_MAXIT", "FACTORIZATION_ERROR": "FRP_EXIT_FACTORIZATION",
+            "BADFUNCEVAL": "FRP_EXIT_BADFUNCEVAL", "NOPROGRESS": "FRP_EXIT_NOPROGRESS", "PARAM_VALUE_ERROR": "FRP_EXIT_PARAM_VALUE"}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INC.format(m="normal")), reason="reference tree absent (GPU box)")
 @pytest.mark.parametrize("m", ["normal", "final"])
 def test_dropin_matches_the_references_own_header(m, tmp_path):
-    """Build-container check against the header plan_manage compiles with (FORCESNLPsolver_normal.h:153-323, included by
-    forces_normal.cpp:2-3): one translation unit sees BOTH headers, compares every struct field, the callback type and
-    the solve prototype, and then links the reference's prototype against libfrp_nmpc_amd.so."""
-    src = tmp_path / "hdr.cpp"
+    """Against the header plan_manage compiles with (FORCESNLPsolver_normal.h:153-323, included by forces_normal.cpp:2-3), as
+    recorded in tests/golden/reference_abi.json (tests/tools/gen_reference_abi.py: what a compiler sees in it): one translation
+    unit compares every struct field, the callback type, the solve prototype and the exit codes of include/frp_nmpc.h with the
+    recorded ones, and then links the reference's symbol against libfrp_nmpc_amd.so."""
+    import json
+    ref = json.load(open(REFERENCE_ABI))["models"][m]
     R = f"FORCESNLPsolver_{m}"
-    src.write_text(f"""
-#include "{R}.h"
-// this repo's header declares the same two C symbols with its own (layout-compatible) struct names
-#define FORCESNLPsolver_normal_solve frp_shadow_normal_solve
-#define FORCESNLPsolver_final_solve frp_shadow_final_solve
+    asserts = []
+    for s, own in OWN.items():
+        asserts.append(f'static_assert(sizeof({own}) == {ref[s]["size"]}, "{s}");')
+        for f, (off, size) in ref[s]["fields"].items():
+            if s == "output":  # x01 .. x20: the rows of this header's one array
+                k = int(f[1:]) - 1
+                asserts.append(f"static_assert(offsetof({own}, x) + {k} * sizeof(((({own} *)0)->x[0])) == {off} && sizeof((({own} *)0)->x[{k}]) == {size}, \"{f}\");")
+            else:
+                asserts.append(f"static_assert(offsetof({own}, {f}) == {off} && sizeof((({own} *)0)->{f}) == {size}, \"{f}\");")
+    # exit codes the caller distinguishes (nmpc_solver.cpp:398-421); "no usable device" is reported with the reference's own
+    # "solver not valid on this machine" value; the runtime-fault code is outside the reference's set
+    codes = ref["exit_codes"]
+    asserts += [f'static_assert({own} == {codes[c]}, "{c}");' for c, own in OWN_EXIT.items()]
+    asserts.append(f'static_assert(FRP_EXIT_NO_DEVICE == {codes["LICENSE_ERROR"]} && FRP_EXIT_DEVICE_FAULT < {codes["LICENSE_ERROR"]}, "machine-level codes");')
+    asserts.append(f'static_assert(std::is_same<frp_forces_extfunc, {ref["extfunc"]}>::value, "callback type");')
+    asserts.append(f'static_assert(std::is_same<decltype(&{R}_solve), {ref["solve"].replace("{solver}_", "frp_forces_")}>::value, "reference prototype");')
+    src = tmp_path / "hdr.cpp"
+    src.write_text("""
 #include "frp_nmpc.h"
-#undef FORCESNLPsolver_normal_solve
-#undef FORCESNLPsolver_final_solve
 #include <cstddef>
 #include <cstdio>
 #include <type_traits>
-#define SAME_FIELD(RT, FT, rf, ff) static_assert(offsetof(RT, rf) == offsetof(FT, ff) && sizeof(((RT *)0)->rf) == sizeof(((FT *)0)->ff), #rf)
-static_assert(sizeof({R}_params) == sizeof(frp_forces_params), "params");
-SAME_FIELD({R}_params, frp_forces_params, xinit, xinit);
-SAME_FIELD({R}_params, frp_forces_params, x0, x0);
-SAME_FIELD({R}_params, frp_forces_params, all_parameters, all_parameters);
-SAME_FIELD({R}_params, frp_forces_params, num_of_threads, num_of_threads);
-static_assert(sizeof({R}_output) == sizeof(frp_forces_output), "output");
-static_assert(offsetof({R}_output, x01) == 0 && offsetof({R}_output, x02) == 17 * sizeof(double) && offsetof({R}_output, x20) == 19 * 17 * sizeof(double), "x01..x20 contiguous");
-static_assert(sizeof({R}_info) == sizeof(frp_forces_info), "info");
-SAME_FIELD({R}_info, frp_forces_info, it, it); SAME_FIELD({R}_info, frp_forces_info, it2opt, it2opt);
-SAME_FIELD({R}_info, frp_forces_info, res_eq, res_eq); SAME_FIELD({R}_info, frp_forces_info, res_ineq, res_ineq);
-SAME_FIELD({R}_info, frp_forces_info, rsnorm, rsnorm); SAME_FIELD({R}_info, frp_forces_info, rcompnorm, rcompnorm);
-SAME_FIELD({R}_info, frp_forces_info, pobj, pobj); SAME_FIELD({R}_info, frp_forces_info, dobj, dobj);
-SAME_FIELD({R}_info, frp_forces_info, dgap, dgap); SAME_FIELD({R}_info, frp_forces_info, rdgap, rdgap);
-SAME_FIELD({R}_info, frp_forces_info, mu, mu); SAME_FIELD({R}_info, frp_forces_info, mu_aff, mu_aff);
-SAME_FIELD({R}_info, frp_forces_info, sigma, sigma); SAME_FIELD({R}_info, frp_forces_info, lsit_aff, lsit_aff);
-SAME_FIELD({R}_info, frp_forces_info, lsit_cc, lsit_cc); SAME_FIELD({R}_info, frp_forces_info, step_aff, step_aff);
-SAME_FIELD({R}_info, frp_forces_info, step_cc, step_cc); SAME_FIELD({R}_info, frp_forces_info, solvetime, solvetime);
-SAME_FIELD({R}_info, frp_forces_info, fevalstime, fevalstime);
-static_assert(std::is_same<{R}_extfunc, frp_forces_extfunc>::value, "callback type");
-static_assert(std::is_same<decltype(&{R}_solve), int (*)({R}_params *, {R}_output *, {R}_info *, FILE *, {R}_extfunc)>::value, "reference prototype");
-static_assert(std::is_same<decltype(&frp_shadow_{m}_solve), int (*)(frp_forces_params *, frp_forces_output *, frp_forces_info *, FILE *, frp_forces_extfunc)>::value, "this repo's prototype");
-// return codes the caller distinguishes (nmpc_solver.cpp:398-421)
-static_assert(OPTIMAL_{R} == FRP_EXIT_OPTIMAL && MAXITREACHED_{R} == FRP_EXIT_MAXIT && FACTORIZATION_ERROR_{R} == FRP_EXIT_FACTORIZATION &&
-              BADFUNCEVAL_{R} == FRP_EXIT_BADFUNCEVAL && NOPROGRESS_{R} == FRP_EXIT_NOPROGRESS && PARAM_VALUE_ERROR_{R} == FRP_EXIT_PARAM_VALUE, "exit codes");
-// "no usable device" is reported with the reference's own "solver not valid on this machine" value; the runtime-fault code is
-// outside the reference's set
-static_assert(LICENSE_ERROR_{R} == FRP_EXIT_NO_DEVICE && FRP_EXIT_DEVICE_FAULT < LICENSE_ERROR_{R}, "machine-level codes");
+""" + "\n".join(asserts) + f"""
 int main() {{
-    // the reference's prototype resolved by this repo's library, exactly what plan_manage's link step does
-    int (*solve)({R}_params *, {R}_output *, {R}_info *, FILE *, {R}_extfunc) = &{R}_solve;
+    // the reference's symbol resolved by this repo's library, exactly what plan_manage's link step does
+    auto solve = &{R}_solve;
     return solve ? 0 : 1;
 }}
 """)
     exe = tmp_path / "hdr"
-    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-I" + REF_INC.format(m=m), "-I" + os.path.join(ROOT, "include"), str(src),
+    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
            "-L" + os.path.dirname(solver.LIB_PATH), "-l:" + os.path.basename(solver.LIB_PATH), "-Wl,-rpath," + os.path.dirname(solver.LIB_PATH),
            "-Wl,--unresolved-symbols=ignore-in-shared-libs", "-o", str(exe)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+    assert len(asserts) == 3 + 4 + 3 + 19 + 6 + 1 + 2
 
 
 def test_abi_check_rejects_a_caller_built_against_another_header():
@@ -423,29 +412,34 @@ def test_product_objects_hold_no_truncated_scalar_immediates(monkeypatch):
     assert build.codegen_flags_trusted()
 
 
-def _build_static_dropin_program(tmp_path):
-    """A C++ program compiled against the REFERENCE's generated headers and linked, by plain g++, against static archives with
-    the reference's file names (plan_manage/CMakeLists.txt:64-65, 82-83) + the HIP runtime."""
+def _build_static_dropin_programs(tmp_path):
+    """C++ programs linked, by plain g++, against static archives with the reference's file names (plan_manage/CMakeLists.txt:64-65,
+    82-83) + the HIP runtime: tests/cpp/static_dropin_stub.cpp compiled against include/frp_nmpc.h (layout-identical to the
+    reference's generated headers: test_dropin_matches_the_references_own_header) and, where the oracle recipe built it, the same
+    program compiled against the REFERENCE's generated headers (oracle/_ref/static_dropin_stub.o)."""
     import subprocess
     from forces_resilient_planner_amd import build
     build.build_native(force=False, verbose=False)
     build.build_dropin_archives()
-    inc = [REF_INC.format(m=m) for m in ("normal", "final")]
-    if not all(os.path.isdir(d) for d in inc):
-        pytest.skip("reference headers absent (GPU box)")
     src = os.path.join(ROOT, "tests", "cpp", "static_dropin_stub.cpp")
-    exe = tmp_path / "planner_stub"
     rocm = "/opt/rocm/lib"
-    r = subprocess.run(["g++", "-O1", "-I" + inc[0], "-I" + inc[1], str(src), "-L" + build.DROPIN_DIR, "-l:libFORCESNLPsolver_normal.a",
-                        "-l:libFORCESNLPsolver_final.a", "-L" + rocm, "-lamdhip64", "-lpthread", "-Wl,-rpath," + rocm, "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    link = ["-L" + build.DROPIN_DIR, "-l:libFORCESNLPsolver_normal.a", "-l:libFORCESNLPsolver_final.a", "-L" + rocm, "-lamdhip64", "-lpthread", "-Wl,-rpath," + rocm]
+    objs = {"own_header": ["-O1", "-DFRP_STUB_OWN_HEADER", "-I" + os.path.join(ROOT, "include"), src]}
+    ref_obj = os.path.join(ROOT, "oracle", "_ref", "static_dropin_stub.o")
+    if os.path.exists(ref_obj):
+        objs["reference_headers"] = [ref_obj]
+    exes = []
+    for name, inputs in objs.items():
+        exe = tmp_path / ("planner_stub_" + name)
+        r = subprocess.run(["g++", *inputs, *link, "-o", str(exe)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        exes.append(exe)
+    return exes
 
 
 @pytest.mark.skipif(_has_gpu(), reason="checks the no-device behaviour of the statically linked stub")
 def test_static_archives_with_the_references_file_names_link_and_fail_loudly_without_a_device(tmp_path):
     import subprocess
-    exe = _build_static_dropin_program(tmp_path)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.split()[:2] == ["-100", "-100"], r.stdout + r.stderr
+    for exe in _build_static_dropin_programs(tmp_path):
+        r = subprocess.run([str(exe)], capture_output=True, text=True)
+        assert r.returncode == 0 and r.stdout.split()[:2] == ["-100", "-100"], r.stdout + r.stderr

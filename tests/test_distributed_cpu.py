@@ -233,3 +233,23 @@ def test_bench_dry_run_plans_eight_ranks_without_a_device():
     # configs[2] strong at 8 ranks: shards of 512 are below two rounds of resident workgroups -> one piece; configs[3]: 2048 >= 2 * 512 -> two
     assert plan("--gpus", "8", "--scaling", "strong", "--config", "2")["ranks"][0]["pieces"] == 1
     assert plan("--gpus", "8", "--scaling", "strong", "--config", "3")["ranks"][0]["pieces"] == 2
+
+
+def test_bench_dump_outputs_samples_large_outputs_the_same_way_every_time(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files; above 64 MB in all, one fixed, seeded sample of problems taken from every array."""
+    import numpy as np
+    import bench
+    small = {"z": np.arange(4 * 2 * 3, dtype=np.float64).reshape(4, 2, 3), "exitflag": np.array([1, 1, 0, 1], dtype=np.float64)}
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert sorted(os.listdir(tmp_path / "s")) == ["exitflag.npy", "z.npy"]
+    assert np.array_equal(np.load(tmp_path / "s" / "z.npy"), small["z"])
+    B = 70000
+    big = {"mpc_output": np.random.default_rng(1).standard_normal((B, 21, 17)), "exitflag": np.arange(B, dtype=np.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("mpc_output", "exitflag", "sample_index")}
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES and all(a.dtype == np.float64 for a in got.values())
+    idx = got["sample_index"].astype(np.int64)
+    assert len(idx) > B // 4 and np.all(np.diff(idx) > 0) and np.array_equal(got["exitflag"], idx.astype(np.float64))
+    assert np.array_equal(got["mpc_output"], big["mpc_output"][idx])
+    assert all(np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), a) for n, a in got.items())

@@ -1550,13 +1550,13 @@ def test_default_code_generation_build_passes_the_variant_and_horizon_tests():
 
 def test_statically_linked_planner_stub_solves_config0(tmp_path):
     """The reference links libFORCESNLPsolver_normal.a / libFORCESNLPsolver_final.a by file name (plan_manage/CMakeLists.txt:64-65,
-    82-83).  build() makes archives with those names and, in the build container, a stub compiled against the reference's own
-    headers and linked against them by plain g++; here it solves BASELINE configs[0] with both solvers."""
+    82-83).  build() makes archives with those names and, where oracle/_ref holds the stub compiled against the reference's own
+    headers, links it against them by plain g++; here it solves BASELINE configs[0] with both solvers."""
     import subprocess
     from forces_resilient_planner_amd import build
     stub = os.path.join(os.path.dirname(build.DROPIN_DIR), "planner_stub")
     if not os.path.exists(stub):
-        pytest.skip("planner_stub is built where the reference headers are (build container)")
+        pytest.skip("planner_stub is linked where oracle/_ref holds the stub compiled against the reference headers")
     w0 = workloads.config0()
     p = solver.ForcesParams()
     p.xinit[:] = w0["xinit"][0]; p.x0[:] = w0["x0"][0].ravel(); p.all_parameters[:] = w0["params"][0].ravel(); p.num_of_threads = 1

@@ -5,8 +5,8 @@ R=$PWD/gpurun_out/ab; rm -rf $R; mkdir -p $R
 timeout 600 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "horizon or batch or fixture or oracle" > $R/pytest.txt 2>&1; tail -3 $R/pytest.txt
 tools/ubench/sweep_timing > $R/sweep_timing.txt 2>&1; tail -8 $R/sweep_timing.txt
 for i in 1 2; do
-  python bench.py --steps 20 --warmup 3 --no-cpu 2>/dev/null | tail -1 > $R/new_$i.json
-  FRP_LIB=$PWD/forces_resilient_planner_amd/lib_prev.so python bench.py --steps 20 --warmup 3 --no-cpu 2>/dev/null | tail -1 > $R/prev_$i.json
+  python bench.py --full --steps 20 --warmup 3 --no-cpu 2>/dev/null | tail -1 > $R/new_$i.json
+  FRP_LIB=$PWD/forces_resilient_planner_amd/lib_prev.so python bench.py --full --steps 20 --warmup 3 --no-cpu 2>/dev/null | tail -1 > $R/prev_$i.json
 done
 python - <<'PY'
 import json,glob

@@ -3,13 +3,13 @@
 # tools/summarize_profiles.py / tools/summarize_sq.py here in the build container.   gpurun -- 'bash tools/collect_r03.sh [quick]'
 export TMPDIR=/tmp
 R=$PWD/gpurun_out/r03; rm -rf $R; mkdir -p $R
-python bench.py --steps 20 --warmup 3 > $R/bench_default.json 2> $R/bench_default.err
-python bench.py --steps 20 --warmup 3 --no-cpu --batch 16384 > $R/bench_16k.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 3 > $R/bench_default.json 2> $R/bench_default.err
+python bench.py --full --steps 20 --warmup 3 --no-cpu --batch 16384 > $R/bench_16k.json 2>/dev/null
 # the same sources with the compiler's default code generation for the solver kernel (lib_defaultflags.so, built by build())
-FRP_LIB=$PWD/forces_resilient_planner_amd/lib_defaultflags.so python bench.py --steps 20 --warmup 3 --no-cpu > $R/bench_defaultflags.json 2>/dev/null
+FRP_LIB=$PWD/forces_resilient_planner_amd/lib_defaultflags.so python bench.py --full --steps 20 --warmup 3 --no-cpu > $R/bench_defaultflags.json 2>/dev/null
 # the other BASELINE configs and the strong-scaling form (RCCL world 1)
 for c in "--config 3" "--config 3 --scaling strong" "--config 4" "--config 2 --scaling strong"; do
-  FRP_BENCH_FORCE_DIST=$([[ "$c" == *strong* ]] && echo 1) python bench.py --steps 10 --warmup 2 --repeats 3 --no-cpu $c 2>/dev/null | tail -1 >> $R/other_configs.jsonl
+  FRP_BENCH_FORCE_DIST=$([[ "$c" == *strong* ]] && echo 1) python bench.py --full --steps 10 --warmup 2 --repeats 3 --no-cpu $c 2>/dev/null | tail -1 >> $R/other_configs.jsonl
 done
 python tools/bench_configs.py > $R/bench_configs.txt 2>&1
 if [ -f forces_resilient_planner_amd/lib_prof.so ]; then

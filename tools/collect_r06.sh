@@ -5,11 +5,11 @@
 export TMPDIR=/tmp
 ROOT=$PWD
 R=$PWD/gpurun_out/r06c; rm -rf $R; mkdir -p $R
-python bench.py --steps 20 --warmup 3 > $R/bench_default.json 2> $R/bench_default.err
-python bench.py --steps 20 --warmup 3 --no-cpu --batch 16384 > $R/bench_16k.json 2>/dev/null
-FRP_Q4=0 python bench.py --steps 20 --warmup 3 --no-cpu > $R/bench_three_per_cu.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 3 > $R/bench_default.json 2> $R/bench_default.err
+python bench.py --full --steps 20 --warmup 3 --no-cpu --batch 16384 > $R/bench_16k.json 2>/dev/null
+FRP_Q4=0 python bench.py --full --steps 20 --warmup 3 --no-cpu > $R/bench_three_per_cu.json 2>/dev/null
 for c in "--config 3" "--config 3 --scaling strong" "--config 4" "--config 2 --scaling strong"; do
-  FRP_BENCH_FORCE_DIST=$([[ "$c" == *strong* ]] && echo 1) python bench.py --steps 10 --warmup 2 --repeats 3 --no-cpu $c 2>/dev/null | tail -1 >> $R/other_configs.jsonl
+  FRP_BENCH_FORCE_DIST=$([[ "$c" == *strong* ]] && echo 1) python bench.py --full --steps 10 --warmup 2 --repeats 3 --no-cpu $c 2>/dev/null | tail -1 >> $R/other_configs.jsonl
 done
 python tools/bench_configs.py > $R/bench_configs.txt 2>&1
 if [ -f forces_resilient_planner_amd/lib_prof.so ]; then
@@ -40,7 +40,7 @@ fi
 bash tools/collect_profiles.sh > $R/collect_profiles.log 2>&1
 # the same command under --kernel-trace alone (no --stats post-processing): every dispatch's begin / end stamp -> median and mean of the solver kernel (tools/r06/kernel_trace_median.py)
 P=$PWD/gpurun_out/prof/trace; rm -rf $P; mkdir -p $P
-(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $P -o bench -- python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu --streams 1 > $P/bench_under_trace.json 2> $P/trace.log)
+(cd /tmp && rocprofv3 --kernel-trace --output-format csv -d $P -o bench -- python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu --streams 1 > $P/bench_under_trace.json 2> $P/trace.log)
 python tools/r06/kernel_trace_median.py $P > $R/kernel_trace_median.json 2> $R/kernel_trace_median.err
 bash tools/collect_sq_counters.sh > $R/collect_sq.log 2>&1
 ls $R

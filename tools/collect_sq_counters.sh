@@ -3,7 +3,7 @@
 # counters only with --kernel-trace.  -> gpurun_out/prof_sq/passN/
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_sq; rm -rf $OUT; mkdir -p $OUT
-BENCH="python $PWD/bench.py --steps 6 --warmup 2 --no-cpu --streams 1"
+BENCH="python $PWD/bench.py --full --steps 6 --warmup 2 --no-cpu --streams 1"
 cd /tmp
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM" \

@@ -14,7 +14,7 @@ for rep in 1 2; do
 for lib in libfrp_nmpc_amd lib_ff; do
   for B in 4096 16384; do
     echo -n "$lib B=$B: " >> $O
-    FRP_LIB=$P/$lib.so timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
+    FRP_LIB=$P/$lib.so timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
   done
 done
 done
@@ -26,10 +26,10 @@ timeout 300 python tools/dbg/tick_hist.py 2>/dev/null >> $O
 echo "== soak divergence" >> $O
 timeout 900 python tests/tools/soak_diverge.py >> $O 2>&1
 echo "== default bench (host path incl. pipelined)" >> $O
-timeout 600 python bench.py 2>/dev/null | tail -1 > gpurun_out/r06_s1_bench_default.json
-python - >> $O <<'PY'
-import json
-j = json.load(open("gpurun_out/r06_s1_bench_default.json"))
+timeout 600 python bench.py --full 2>/dev/null | tail -1 > ${O%.txt}_bench_default.json
+python - ${O%.txt}_bench_default.json >> $O <<'PY'
+import json, sys
+j = json.load(open(sys.argv[1]))
 print({k: j[k] for k in ("value", "ms_per_step")}, j["roofline"]["frac"], j["roofline"]["kernel_ms"])
 print(json.dumps(j.get("end_to_end"), indent=0)[:3000])
 print(j.get("dropin_latency_ms"), j.get("full_tick", {}).get("ms_per_step"), j.get("full_tick", {}).get("ms_per_tick"))

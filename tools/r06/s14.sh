@@ -17,7 +17,7 @@ for rep in 1 2; do
 for lib in libfrp_nmpc_amd lib_touch; do
   for B in 4096 16384; do
     echo -n "$lib B=$B: " >> $O
-    FRP_LIB=$P/$lib.so timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
+    FRP_LIB=$P/$lib.so timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
   done
 done
 done

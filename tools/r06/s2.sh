@@ -14,12 +14,12 @@ for rep in 1 2; do
 for lib in libfrp_nmpc_amd lib_early; do
   for B in 4096 16384; do
     echo -n "$lib B=$B: " >> $O
-    FRP_LIB=$P/$lib.so timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
+    FRP_LIB=$P/$lib.so timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
   done
   echo -n "$lib FRP_Q4=0 B=4096: " >> $O
-  FRP_Q4=0 FRP_LIB=$P/$lib.so timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu --repeats 5 2>/dev/null | tail -1 | bl >> $O
+  FRP_Q4=0 FRP_LIB=$P/$lib.so timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu --repeats 5 2>/dev/null | tail -1 | bl >> $O
   echo -n "$lib config 3: " >> $O
-  FRP_LIB=$P/$lib.so timeout 300 python bench.py --config 3 --steps 5 --warmup 1 --no-cpu --repeats 3 2>/dev/null | tail -1 | bl >> $O
+  FRP_LIB=$P/$lib.so timeout 300 python bench.py --full --config 3 --steps 5 --warmup 1 --no-cpu --repeats 3 2>/dev/null | tail -1 | bl >> $O
   echo -n "$lib " >> $O; FRP_LIB=$P/$lib.so timeout 120 python tools/r06/dropin_lat.py 2>/dev/null >> $O
   echo -n "$lib twist " >> $O; FRP_NMPC_TWIST=-1 FRP_LIB=$P/$lib.so timeout 120 python tools/r06/dropin_lat.py 2>/dev/null >> $O
 done

@@ -11,12 +11,12 @@ for rep in 1 2; do
 for lib in libfrp_nmpc_amd lib_stag1 lib_stag2 lib_stag3; do
   for B in 4096 16384; do
     echo -n "$lib B=$B: " >> $O
-    FRP_LIB=$P/$lib.so timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
+    FRP_LIB=$P/$lib.so timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu --repeats 5 --batch $B 2>/dev/null | tail -1 | bl >> $O
   done
 done
 done
 for iso in 6 8 16; do
   echo -n "FRP_ISO_IT=$iso B=4096: " >> $O
-  FRP_ISO_IT=$iso timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu --repeats 5 2>/dev/null | tail -1 | bl >> $O
+  FRP_ISO_IT=$iso timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu --repeats 5 2>/dev/null | tail -1 | bl >> $O
 done
 cat $O

@@ -11,7 +11,7 @@ j=json.loads(sys.stdin.read()); print('ms/step %.4f kernel_ms %.4f value %.0f fr
 for rep in 1 2; do
 for lib in libfrp_nmpc_amd lib_n32e lib_n32a lib_n32b lib_n32c lib_n32d; do
   echo -n "$lib config 3: " >> $O
-  FRP_LIB=$P/$lib.so timeout 300 python bench.py --config 3 --steps 5 --warmup 1 --no-cpu --repeats 3 2>/dev/null | tail -1 | bl >> $O
+  FRP_LIB=$P/$lib.so timeout 300 python bench.py --full --config 3 --steps 5 --warmup 1 --no-cpu --repeats 3 2>/dev/null | tail -1 | bl >> $O
 done
 done
 echo "== parity of the 168-register builds (N = 30 tests)" >> $O

@@ -15,7 +15,7 @@ j=json.loads(sys.stdin.read()); print('ms/step %.4f kernel_ms %.4f value %.0f fr
 for rep in 1 2; do
 for q in 0 1; do
   echo -n "FRP_Q30=$q config 3: " >> $O
-  FRP_Q30=$q timeout 300 python bench.py --config 3 --steps 5 --warmup 1 --no-cpu --repeats 3 2>/dev/null | tail -1 | bl >> $O
+  FRP_Q30=$q timeout 300 python bench.py --full --config 3 --steps 5 --warmup 1 --no-cpu --repeats 3 2>/dev/null | tail -1 | bl >> $O
 done
 done
 cat $O

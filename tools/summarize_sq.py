@@ -11,7 +11,7 @@ for f in glob.glob("gpurun_out/prof_sq/pass*/bench_counter_collection.csv"):
             tot[r["Counter_Name"]].append(float(r["Counter_Value"]))
 d = {k: sum(v) / len(v) for k, v in tot.items()}
 wc = d["SQ_WAVE_CYCLES"]
-out = {"command": "tools/collect_sq_counters.sh (rocprofv3 --pmc <8 SQ counters per pass> --kernel-trace -- python bench.py --steps 6 --warmup 2 --no-cpu), averages per launch of the dominant kernel, B = 4096",
+out = {"command": "tools/collect_sq_counters.sh (rocprofv3 --pmc <8 SQ counters per pass> --kernel-trace -- python bench.py --full --steps 6 --warmup 2 --no-cpu), averages per launch of the dominant kernel, B = 4096",
        "raw": d,
        "derived": {
            "instructions_per_ipm_iteration": d["SQ_INSTS"] / its,
