@@ -697,6 +697,20 @@ int frp_nmpc_host_unregister_all(void)
 
 int frp_nmpc_set_q4_min_batch(int min_batch) { return frp::lds_q4_set_min_batch(min_batch); }
 
+int frp_nmpc_solver_variant(const frp_nmpc_batch *batch, const frp_nmpc_options *opt, char *buf, size_t n)
+{
+    static double no_ws; // (the selection looks at the shape of the launch, never at the workspace)
+    frp::KernelArgs a;
+    if (!buf || n == 0 || !fill_args(batch, opt, &no_ws, SIZE_MAX, &a)) return FRP_ERR_ARG;
+    buf[0] = 0;
+    if (frp_nmpc_device_count() <= 0) return FRP_ERR_NO_DEVICE; // (the choice depends on the device's CU count)
+    const char *name = frp::ipm_variant_name(a);
+    if (!name) return FRP_ERR_ARG;
+    if (strlen(name) >= n) return FRP_ERR_ARG;
+    memcpy(buf, name, strlen(name) + 1);
+    return FRP_OK;
+}
+
 int frp_nmpc_kernel_timing_end(float *avg_ms, int *launches)
 {
     if (!avg_ms || !launches) return FRP_ERR_ARG;

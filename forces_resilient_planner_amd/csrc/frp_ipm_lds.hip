@@ -24,6 +24,7 @@
 #include <math.h>
 #include <cstdlib>
 #include <atomic>
+#include <cstdio>
 #include "frp_model.hpp"
 #include "../../include/frp_nmpc.h"
 #include "frp_kernels.h"
@@ -3474,9 +3475,18 @@ __global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(
     }
 }
 
+#define FRP_LR_STR_(x) #x
+#define FRP_LR_STR(x) FRP_LR_STR_(x)
 template <int NP, int FL, bool FREG, int WPE, bool TW = false>
 static hipError_t launch_variant(const KernelArgs &k, int slots, hipStream_t stream)
 {
+    if (lds_select_only) { // (ipm_variant_name: the selection of this launch without the launch -- what the kernel's symbol demangles to)
+        static char name[96];
+        static const bool once = [] { snprintf(name, sizeof name, "frp::" FRP_LR_STR(FRP_LR) "::nmpc_ipm_lds_kernel<%d, %d, %s, %d, %s>", NP, FL, FREG ? "true" : "false", WPE, TW ? "true" : "false"); return true; }();
+        (void)once;
+        lds_selected_name = name;
+        return hipSuccess;
+    }
 #ifdef FRP_DYN_LDS
     const size_t lds = (size_t)(NP * RS + X_TOTAL + (QS ? 0 : 3 * NP) + (TW ? TW_TOTAL : 1)) * 8 + sizeof(Ctl) + 5 * sizeof(int) + 16;
     static bool once = [&] { return hipFuncSetAttribute(reinterpret_cast<const void *>(&nmpc_ipm_lds_kernel<NP, FL, FREG, WPE, TW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; }();
@@ -3660,7 +3670,12 @@ static hipError_t launch_ipm_lds_mem(const KernelArgs &k, int slots, hipStream_t
 #ifndef FRP_WPE20 // experiment knob: register budget of the N <= 20 variants (3 waves per SIMD = 168 VGPRs; 4 = 128)
 #define FRP_WPE20 3
 #endif
-// counter / order already set up by launch_ipm
+thread_local bool lds_select_only = false; // (frp_kernels.h: ipm_variant_name)
+thread_local const char *lds_selected_name = nullptr;
+
+// counter / order already set up by launch_ipm.  This function is also the selection query (frp_kernels.h: ipm_variant_name): with
+// lds_select_only set, launch_variant records the name of the kernel instead of launching it.  So nothing on the way to launch_variant,
+// here or in the launch_ipm_lds_* functions of the other translation units, may launch, allocate or change state.
 hipError_t launch_ipm_lds(const KernelArgs &k0, int slots, hipStream_t stream)
 {
     KernelArgs k = k0;

@@ -88,6 +88,11 @@ size_t lds_q30_pws_doubles_per_slot();
 int lds_q4_set_min_batch(int min_b); // (frp_nmpc_set_q4_min_batch)
 bool lds_kernel_supports(int N, int MF);
 hipError_t launch_ipm_lds(const KernelArgs &k, int slots, hipStream_t stream);
+// The kernel variant a launch of `a` runs ("frp::lr::nmpc_ipm_lds_kernel<20, 2, true, 3, false>", what its symbol demangles to), or null:
+// launch_ipm's own selection, run with lds_select_only set -- launch_variant then records its name instead of launching.  Needs a device (CU count).
+const char *ipm_variant_name(const KernelArgs &a);
+extern thread_local bool lds_select_only;
+extern thread_local const char *lds_selected_name;
 hipError_t launch_stage_eval(int B, int N, int M, int model, const double *z, const double *params, double *f,
                              double *gf, double *c, double *Jc, double *h, hipStream_t stream);
 

@@ -436,16 +436,32 @@ hipError_t kernel_timing_end(float *avg_ms, int *launches)
     return rc;
 }
 
+// packed-P workspace of the high-residency variants (KernelArgs::pws; null: the launch cannot take them)
+static double *pws_of(const KernelArgs &a)
+{
+    if (!(q4_shape(a.N, a.MF) || q30_shape(a.N, a.MF))) return nullptr;
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a.ws + QUEUE_RESERVED + (size_t)a.B + ((size_t)a.B + 1) / 2);
+    return reinterpret_cast<double *>((p + 127) & ~(uintptr_t)127);
+}
+
+const char *ipm_variant_name(const KernelArgs &a)
+{
+    if (!lds_kernel_supports(a.N, a.MF)) return nullptr;
+    KernelArgs k = a;
+    k.pws = pws_of(a);
+    lds_select_only = true;
+    lds_selected_name = nullptr;
+    const hipError_t rc = launch_ipm_lds(k, 1, nullptr);
+    lds_select_only = false;
+    return rc == hipSuccess ? lds_selected_name : nullptr;
+}
+
 hipError_t launch_ipm(const KernelArgs &a, hipStream_t stream)
 {
     if (!lds_kernel_supports(a.N, a.MF)) return hipErrorInvalidValue; // (fill_args rejects these before they get here)
     KernelArgs k = a;
     double *q = a.ws;
-    k.pws = nullptr;
-    if (q4_shape(a.N, a.MF) || q30_shape(a.N, a.MF)) {
-        const uintptr_t p = reinterpret_cast<uintptr_t>(q + QUEUE_RESERVED + (size_t)a.B + ((size_t)a.B + 1) / 2);
-        k.pws = reinterpret_cast<double *>((p + 127) & ~(uintptr_t)127);
-    }
+    k.pws = pws_of(a);
     int slots = lds_resident_slots(a.B, k);
     if (a.slot_reserve > 0) { // room for another kernel's workgroups beside the persistent ones (the pipelined host path's gather)
         int lim = resident_cap(lds_workgroups_per_cu(k)) - a.slot_reserve;

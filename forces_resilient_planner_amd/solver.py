@@ -130,7 +130,8 @@ EXPORTS = ["frp_nmpc_default_options", "frp_nmpc_workspace_bytes", "frp_nmpc_sol
            "frp_nmpc_mode_batch", "frp_nmpc_astar_batch", "frp_nmpc_astar_workspace_bytes",
            "frp_nmpc_kernel_timing_begin", "frp_nmpc_kernel_timing_end", "frp_nmpc_set_q4_min_batch",
            "frp_nmpc_abi_version", "frp_nmpc_abi_check", "frp_nmpc_host_register", "frp_nmpc_host_unregister",
-           "frp_nmpc_host_registered", "frp_nmpc_host_unregister_all", "frp_nmpc_solve_batch_host_begin", "frp_nmpc_solve_batch_host_wait"]
+           "frp_nmpc_host_registered", "frp_nmpc_host_unregister_all", "frp_nmpc_solve_batch_host_begin", "frp_nmpc_solve_batch_host_wait",
+           "frp_nmpc_solver_variant"]
 
 _lib = None
 
@@ -168,6 +169,7 @@ def lib():
                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         l.frp_nmpc_solve_batch_host.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Options)]
         l.frp_nmpc_set_q4_min_batch.argtypes = [ctypes.c_int]
+        l.frp_nmpc_solver_variant.argtypes = [ctypes.POINTER(Batch), ctypes.POINTER(Options), ctypes.c_char_p, ctypes.c_size_t]
         l.frp_nmpc_host_register.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
         l.frp_nmpc_host_unregister.argtypes = [ctypes.c_void_p]
         l.frp_nmpc_host_registered.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
@@ -230,6 +232,18 @@ def solve_batch_host(w, opt: Options | None = None, MF: int | None = None, x0=No
     _check(lib().frp_nmpc_solve_batch_host(ctypes.byref(b), ctypes.byref(opt) if opt is not None else None),
            "frp_nmpc_solve_batch_host")
     return z, flag, iters, info
+
+
+def solver_variant(B, N, M, MF, model, opt: Options | None = None) -> str:
+    """The kernel instantiation a solve of B problems of this shape would launch now (frp_nmpc_solver_variant), e.g.
+    "frp::lr::nmpc_ipm_lds_kernel<20, 2, true, 3, false>".  The selection never reads the batch's arrays: any non-NULL
+    address stands in for them."""
+    one = 8
+    b = Batch(B, N, M, MF, model, one, one, one, None, one, one, one, None, None)
+    buf = ctypes.create_string_buffer(128)
+    _check(lib().frp_nmpc_solver_variant(ctypes.byref(b), ctypes.byref(opt) if opt is not None else None, buf, len(buf)),
+           "frp_nmpc_solver_variant")
+    return buf.value.decode()
 
 
 def solve_batch_host_begin(w, out, opt: Options | None = None, MF: int | None = None):

@@ -215,6 +215,14 @@ int frp_nmpc_kernel_timing_end(float *avg_ms, int *launches);
  * stage at THREE problems per CU (DESIGN 4 "Round 6"; its own default: more than two workgroups per CU worth of problems). */
 int frp_nmpc_set_q4_min_batch(int min_batch);
 
+/* Test hook: the solver kernel instantiation that frp_nmpc_solve_batch(batch, opt, ...) would launch now, as its symbol demangles,
+ * e.g. "frp::lrq::nmpc_ipm_lds_kernel<20, 2, true, 3, false>" (namespace = translation unit; template arguments = stages per
+ * workgroup, corridor rows per lane, rows in registers, waves per SIMD, twisted solve), written NUL-terminated into buf[n].  The same
+ * selection code as the launch, run without launching; it depends on the batch size, the shape, the options, the device's CU count
+ * and frp_nmpc_set_q4_min_batch.  FRP_ERR_ARG for the arguments frp_nmpc_solve_batch refuses (the workspace aside) or a buffer too
+ * small, FRP_ERR_NO_DEVICE without a device. */
+int frp_nmpc_solver_variant(const frp_nmpc_batch *batch, const frp_nmpc_options *opt, char *buf, size_t n);
+
 /* ---- (3) SURVEY 8f row f-1: the adapter's packing / result bookkeeping on the device (all pointers DEVICE) ---- */
 typedef struct frp_nmpc_pack {
     int B, N, M;   /* problems, horizon, corridor rows of the parameter layout (num_const, nmpc_utils.h:50)      */

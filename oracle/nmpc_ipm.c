@@ -572,6 +572,14 @@ static void slack_steps(solver_ws *W, const double *params, double sigmamu, int 
     *ad = a_d;
 }
 
+/* orc_solve_trace (test infrastructure): what iteration `k` of a solve factorises, recorded by orc_solve when set */
+typedef struct {
+    int k, done;
+    double *z, *y, *theta, *H;
+    int *exact;
+} orc_trace;
+static __thread orc_trace *tl_trace = 0;
+
 int orc_solve(int N, int M, int model, const double *xinit, const double *z0,
               const double *params, const int *nfaces, const orc_options *opt_in,
               double *zout, orc_info *info)
@@ -771,6 +779,20 @@ int orc_solve(int N, int M, int model, const double *xinit, const double *z0,
         } else if (want_exact) {
             theta_h = fmin(1.0, theta_h + THETA_UP);
         }
+        if (tl_trace && it == tl_trace->k) { /* the iterate, y, and each stage's Hessian as the predictor factorised it (no barrier terms) */
+            orc_trace *t = tl_trace;
+            memcpy(t->z, W.z, sizeof(double) * 17 * N);
+            memcpy(t->y, W.y, sizeof(double) * NS * N);
+            *t->exact = N > 1 && W.st[0].useH;
+            *t->theta = N > 1 ? W.st[0].thetaH : 1.0;
+            for (int k = 0; k < N; k++) {
+                stage_ws bare = W.st[k];
+                for (int i = 0; i < 17; i++) bare.PhiD[i] = bare.hd[i];
+                memset(bare.PhiPos, 0, sizeof bare.PhiPos);
+                stage_phi_dense(&bare, t->H + (size_t)k * 289);
+            }
+            t->done = 1;
+        }
         if (frc) { flag = ORC_FACTORIZATION_ERROR; break; }
         slack_steps(&W, params, 0.0, 0, &ap, &ad);
         ap = fmin(1.0, ap); ad = fmin(1.0, ad);
@@ -844,4 +866,19 @@ void orc_solve_batch(int B, int N, int M, int model, const double *xinit, const 
         if (exitflag) exitflag[b] = fl;
         if (info) info[b] = inf;
     }
+}
+
+int orc_solve_trace(int N, int M, int model, const double *xinit, const double *z0, const double *params, const int *nfaces,
+                    const orc_options *opt, int k, double *z, double *y, double *theta, int *exact, double *H)
+{
+    orc_options o;
+    if (opt) o = *opt; else orc_default_options(&o);
+    if (o.maxit > k + 1) o.maxit = k + 1; /* (nothing after iteration k is recorded) */
+    orc_trace t = {k, 0, z, y, theta, H, exact};
+    double *zo = (double *)malloc(sizeof(double) * 17 * (size_t)N);
+    tl_trace = &t;
+    orc_solve(N, M, model, xinit, z0, params, nfaces, &o, zo, 0);
+    tl_trace = 0;
+    free(zo);
+    return t.done;
 }

@@ -389,6 +389,20 @@ def test_widened_entry_points_reject_bad_arguments_before_touching_a_device():
     d3, i3 = (ctypes.c_double * 3)(0, 0, 0), (ctypes.c_int * 3)(1 << 11, 1 << 11, 2)   # 2^23 cells > FRP_CORRIDOR_MAX_CELLS
     assert l.frp_nmpc_cloud_grid_build(one, 10, d3, 0.5, i3, one, one, one, one, None) == ERR
     assert l.frp_nmpc_cloud_grid_build(one, 10, d3, 0.0, (ctypes.c_int * 3)(4, 4, 4), one, one, one, one, None) == ERR
+    # the kernel-selection query: the batch checks of frp_nmpc_solve_batch, and a buffer that holds the name
+    bt = solver.Batch(64, 20, 30, 6, 0, 8, 8, 8, None, 8, 8, 8, None, None)
+    buf = ctypes.create_string_buffer(128)
+    assert l.frp_nmpc_solver_variant(ctypes.byref(bt), None, None, 128) == ERR   # no buffer
+    assert l.frp_nmpc_solver_variant(ctypes.byref(bt), None, buf, 0) == ERR      # empty buffer
+    for field, bad in (("N", 65), ("N", 1), ("MF", 31), ("B", 0), ("model", 2), ("params", None)):
+        keep = getattr(bt, field)
+        setattr(bt, field, bad)
+        assert l.frp_nmpc_solver_variant(ctypes.byref(bt), None, buf, 128) == ERR, field
+        setattr(bt, field, keep)
+    if not _has_gpu():  # (valid arguments: the choice needs the device's CU count -- a loud failure, no guess)
+        assert l.frp_nmpc_solver_variant(ctypes.byref(bt), None, buf, 128) == -1001
+        with pytest.raises(RuntimeError):
+            solver.solver_variant(64, 20, 30, 6, 0)
 
 
 def test_product_objects_hold_no_truncated_scalar_immediates(monkeypatch):
@@ -443,3 +457,52 @@ def test_static_archives_with_the_references_file_names_link_and_fail_loudly_wit
     for exe in _build_static_dropin_programs(tmp_path):
         r = subprocess.run([str(exe)], capture_output=True, text=True)
         assert r.returncode == 0 and r.stdout.split()[:2] == ["-100", "-100"], r.stdout + r.stderr
+
+
+def _kernel_instantiations(so, tmp_path):
+    """Demangled names of the nmpc_ipm_lds_kernel instantiations in the gfx950 code objects of a built library: every
+    clang offload bundle of its .hip_fatbin section (one per translation unit) is unbundled here and its kernel descriptors
+    listed, demangled, with the ROCm LLVM tools.  Returns {name: number of bundles that hold it}."""
+    import struct
+    llvm = "/opt/rocm/llvm/bin"
+    fb = tmp_path / "fatbin"
+    subprocess.run([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", so, str(tmp_path / "discard")], check=True)
+    data = fb.read_bytes()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    names, bundles, pos = {}, 0, data.find(magic)
+    while pos >= 0:
+        n = struct.unpack_from("<Q", data, pos + 24)[0]
+        off = pos + 32
+        for _ in range(n):
+            o, size, tl = struct.unpack_from("<QQQ", data, off)
+            triple = data[off + 24:off + 24 + tl].decode()
+            off += 24 + tl
+            if "amdgcn" not in triple:
+                continue
+            assert "gfx950" in triple, triple
+            co = tmp_path / f"co{bundles}.elf"
+            co.write_bytes(data[pos + o:pos + o + size])
+            syms = subprocess.run([f"{llvm}/llvm-readelf", "-s", "-C", "--wide", str(co)], check=True, capture_output=True, text=True).stdout
+            kern = [re.search(r"void (\S+::nmpc_ipm_lds_kernel<[^>]*>)\(frp::KernelArgs\) \(\.kd\)$", ln) for ln in syms.splitlines()]
+            kern = {m.group(1) for m in kern if m}  # (.dynsym and .symtab list each descriptor)
+            for nm in kern:
+                names[nm] = names.get(nm, 0) + 1
+            bundles += bool(kern)
+        pos = data.find(magic, pos + 1)
+    return names, bundles
+
+
+@pytest.mark.parametrize("lib", ["default", "default_flags"])
+def test_step_parity_cases_cover_every_kernel_instantiation_that_ships(lib, tmp_path):
+    """The case table of tests/test_gpu_variant_steps.py names exactly the nmpc_ipm_lds_kernel instantiations of the built
+    library, read from its device code (five translation units): an instantiation added without a step-parity case, or
+    a case whose instantiation is gone, fails here."""
+    from forces_resilient_planner_amd import build
+    from .test_gpu_variant_steps import CASES
+    so = solver.LIB_PATH if lib == "default" else build.DEFAULT_FLAGS_LIB
+    if not os.path.exists(so):
+        build.build_native(force=False, verbose=False) if lib == "default" else build.build_default_flags_lib()
+    names, bundles = _kernel_instantiations(so, tmp_path)
+    assert bundles == 5, (bundles, names)
+    assert all(c == 1 for c in names.values()), names
+    assert set(names) == set(CASES), (sorted(set(names) - set(CASES)), sorted(set(CASES) - set(names)))

@@ -520,10 +520,13 @@ def test_horizon_lengths_cover_every_lane_mapping(N):
 
 @pytest.mark.parametrize("N,M,B", [(20, 6, 64), (20, 15, 64), (20, 30, 64), (30, 6, 48), (30, 15, 48), (30, 30, 48), (48, 8, 24), (48, 30, 24)])
 def test_every_kernel_variant_reports_the_oracles_numbers(N, M, B):
-    """One batch per kernel variant of the LDS-resident solver (stage stride 20 / 32 / 64 x corridor rows in registers or
-    re-read from the parameters; the variants are separate template instantiations in two translation units with their own
-    code-generation flags): flags, iteration counts, iterates AND every reported quantity -- residual norms, objective,
-    mu -- against the oracle.  `nfaces` is withheld so that the padding detection runs and MF = M selects the variant."""
+    """One batch per row layout of the LDS-resident solver (stage stride 20 / 32 / 64 x corridor rows in registers or
+    re-read from the parameters): flags, iteration counts, iterates AND every reported quantity -- residual norms, objective,
+    mu -- against the oracle.  `nfaces` is withheld so that the padding detection runs and MF = M selects the row layout.
+    Which instantiation runs also depends on the batch size: B = 64 (N = 20) and 48 (N = 30) are small launches, so the
+    N = 20 rows run the two-per-CU builds (lr2) and the N = 30 rows the two-per-CU ones of the main unit, not the
+    three-per-CU or high-residency builds.  tests/test_gpu_variant_steps.py runs every instantiation, named through
+    frp_nmpc_solver_variant, step by step."""
     w = workloads.config3(B, N=N, M=M)
     wn = dict(w); wn["nfaces"] = None
     z, fl, it, info = solver.solve_batch_host(wn)
@@ -1536,15 +1539,17 @@ def test_fleet_with_per_planner_mode_switch():
 def test_default_code_generation_build_passes_the_variant_and_horizon_tests():
     """The product compiles the solver kernel with internal code-generation switches of one compiler release (build.py:
     CODEGEN_FLAGS, +5 % speed).  No result may depend on them: the library built with the compiler's defaults
-    (lib_defaultflags.so, made by __graft_entry__.build()) passes the same per-variant and per-horizon parity tests."""
+    (lib_defaultflags.so, made by __graft_entry__.build()) passes the same per-variant and per-horizon parity tests, and the
+    step-by-step comparison of every kernel instantiation (tests/test_gpu_variant_steps.py)."""
     import subprocess
     import sys
     from forces_resilient_planner_amd import build
     lib = build.DEFAULT_FLAGS_LIB
     assert os.path.exists(lib), "run __graft_entry__.build()"
     env = dict(os.environ, FRP_LIB=lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
-                        "-k", "every_kernel_variant or horizon_lengths"], env=env, capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    steps = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_variant_steps.py")  # (every instantiation, step by step)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), steps, "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
+                        "-k", "every_kernel_variant or horizon_lengths or every_instantiation_steps or theta_path"], env=env, capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 

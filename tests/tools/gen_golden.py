@@ -8,6 +8,8 @@ copied; only NUMBERS produced by it are stored).
   G1  stage_vectors.npz   seeded (z, p, stage, model) -> f, grad f, c, Jc, h, Jh from the reference
                           callback FORCESNLPsolver_{normal,final}_casadi2forces
                           (solver/*/FORCESNLPsolver_*_casadi2forces.c:42-245).
+  G2  hessian_vectors.npz seeded edge points (z, p, stage, model, nu) -> difference Hessians of nu'c and of the cost
+                          from the same callbacks' exact Jacobians, with their error estimates (ref_hessian).
   G3  solutions_<family>.npz   independent SciPy SLSQP solutions of the reference NLP
                           (matlab_code/setup.m, mpc/normal/mpc_generator_normal.m) assembled from those
                           same callbacks (objective, dynamics, corridor + analytic Jacobians), for
@@ -194,6 +196,86 @@ def gen_stage_vectors(path, n=240, seed=W.SEED0):
     print('wrote', path)
 
 
+# ---- G2  exact second derivatives from the reference's first derivatives ------------------------------------------
+# The reference callbacks never write a Hessian (casadi2forces.c:52), so the Hessians the solver uses are pinned against
+# central differences of the callbacks' EXACT Jacobians: column j of the Hessian of nu'c(z) is d(Jc' nu)/dz_j, that of the
+# cost d(grad f)/dz_j.  Each difference quotient is Richardson-extrapolated from two step sizes (h, h/2); the same over
+# (h/2, h/4) gives the error estimate |R(h) - R(h/2)|.  Steps are scaled to each variable's range.
+HESS_STEP = np.array([0.005] * 3 + [0.0125] + [0.005] * 3 + [0.0125] + [0.0125] * 3 + [0.005] * 6)  # (estimates <= 2e-11 relative; 4x these: 1e-9)
+
+
+def _ref_grad_fn(model, p130, stage20, nu):
+    if nu is None:
+        return lambda z: ref_stage(model, z, p130, stage20, ('gf',))['gf']
+    return lambda z: ref_stage(model, z, p130, stage20, ('Jc',))['Jc'].reshape(17, 13) @ nu
+
+
+def ref_hessian(model, z, p130, stage20, nu=None, step=HESS_STEP):
+    """Difference Hessian (17 x 17) of nu'c (nu: 13 multipliers in the reference's row order [pos vel att | carry]) or, with
+    nu None, of the stage cost -- and its elementwise error estimate."""
+    g = _ref_grad_fn(model, p130, stage20, nu)
+    z = np.asarray(z, dtype=np.float64)
+
+    def dq(j, h):
+        e = np.zeros(17); e[j] = h
+        return (g(z + e) - g(z - e)) / (2.0 * h)
+    H = np.zeros((17, 17)); E = np.zeros((17, 17))
+    for j in range(17):
+        d1, d2, d4 = dq(j, step[j]), dq(j, step[j] / 2), dq(j, step[j] / 4)
+        r1, r2 = (4.0 * d2 - d1) / 3.0, (4.0 * d4 - d2) / 3.0
+        H[:, j] = r2
+        E[:, j] = np.abs(r2 - r1)
+    return H, E
+
+
+def hessian_points(n, seed):
+    """Stage points at the edges of the box and of the trigonometry: roll / pitch at -0.4 pi, 0, 0.4 pi; yaw at 0, +-pi,
+    +-2 pi; rates at +-pi/2 (the RK2 midpoint attitude e + DT w moves furthest); T at t_min / t_max; v at +-2; f_ext = 0 or
+    |f_ext| = 3; multipliers on the position rows only, the velocity rows only or both (with the linear attitude / carry
+    rows set too), magnitudes 1e-3 .. 1e3.  Yields (model, stage20, z, p130, nu)."""
+    rng = np.random.default_rng(seed)
+    lb, ub = L.bounds()
+    ang = [-0.4 * np.pi, 0.0, 0.4 * np.pi]
+    yaws = [0.0, np.pi, -np.pi, 2 * np.pi, -2 * np.pi]
+    for t in range(n):
+        model = t % 2
+        stage = [0, 7, 19][(t // 2) % 3]
+        z = lb + (ub - lb) * rng.random(17)
+        if t % 4 != 3:  # (every fourth point stays in the uniform interior)
+            z[14] = ang[t % 3]
+            z[15] = ang[(t // 3) % 3]
+            z[16] = yaws[t % 5]
+            if t % 7 < 4:
+                z[0:3] = np.pi / 2 * np.sign(rng.normal(size=3))
+            z[3] = (lb[3], ub[3])[t % 2 if t % 3 else 1 - t % 2]
+            if t % 5 < 3:
+                z[11:14] = 2.0 * np.sign(rng.normal(size=3))
+        p = np.zeros(130)
+        p[:3] = rng.uniform(-5, 5, 3)
+        f = rng.normal(size=3)
+        p[3:6] = 0.0 if t % 3 == 0 else 3.0 * f / np.linalg.norm(f)
+        p[6:9] = rng.uniform(0.5, 80, 3)
+        p[9] = rng.uniform(-3, 3)
+        nu = rng.normal(size=13) * 10.0 ** rng.uniform(-3, 3)
+        if t % 3 == 0:
+            nu[3:6] = 0.0   # position rows only
+        elif t % 3 == 1:
+            nu[0:3] = 0.0   # velocity rows only
+        yield model, stage, z, p, nu
+
+
+def gen_hessian_vectors(path, n=96, seed=W.SEED0 + 17):
+    """G2: difference Hessians of nu'c (stages with dynamics) and of the cost from the reference callbacks."""
+    rec = dict(z=[], p=[], stage=[], model=[], nu=[], Hc=[], Hc_err=[], Hf=[], Hf_err=[])
+    for model, stage, z, p, nu in hessian_points(n, seed):
+        Hf, Ef = ref_hessian(model, z, p, stage)
+        Hc, Ec = ref_hessian(model, z, p, stage, nu) if stage != 19 else (np.zeros((17, 17)), np.zeros((17, 17)))
+        for k, v in (('z', z), ('p', p[:10]), ('stage', stage), ('model', model), ('nu', nu), ('Hc', Hc), ('Hc_err', Ec), ('Hf', Hf), ('Hf_err', Ef)):
+            rec[k].append(v)
+    np.savez_compressed(path, **{k: np.array(v) for k, v in rec.items()})
+    print('wrote', path, os.path.getsize(path), 'bytes')
+
+
 def gen_solutions(outdir, workers=int(os.environ.get('GEN_WORKERS', '8'))):
     import tests.oracle_lib as OL
     fams = {
@@ -242,5 +324,7 @@ if __name__ == '__main__':
     os.makedirs(out, exist_ok=True)
     if len(sys.argv) < 2 or sys.argv[1] == 'stage':
         gen_stage_vectors(os.path.join(out, 'stage_vectors.npz'))
+    if len(sys.argv) < 2 or sys.argv[1] == 'hessian':
+        gen_hessian_vectors(os.path.join(out, 'hessian_vectors.npz'))
     if len(sys.argv) < 2 or sys.argv[1] == 'solutions':
         gen_solutions(out)
