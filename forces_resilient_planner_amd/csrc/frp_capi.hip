@@ -51,6 +51,38 @@ struct DevMem {
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
 
+// Rate of the current device's wall clock (s_memrealtime) in Hz, cached per device; 0 when it cannot be queried.
+double wall_clock_hz()
+{
+    static std::mutex m;
+    static double hz[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) { (void)hipGetLastError(); return 0.0; }
+    std::lock_guard<std::mutex> l(m);
+    if (dev < 64 && hz[dev] > 0.0) return hz[dev];
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) { (void)hipGetLastError(); return 0.0; }
+    const double r = 1e3 * (double)khz;
+    if (dev < 64) hz[dev] = r;
+    return r;
+}
+
+// frp_nmpc_options.timeout -> KernelArgs::deadline (ticks of the wall clock, rounded up; 0 = no budget) / timeout_invalid.  False only
+// when a budget is set and the clock's rate cannot be read (no device).
+bool budget_args(double timeout, frp::KernelArgs *a)
+{
+    a->deadline = 0; a->origin = nullptr; a->timeout_invalid = 0;
+    if (timeout == 0.0 || timeout == HUGE_VAL) return true;   // no budget
+    if (!(timeout > 0.0)) { a->timeout_invalid = 1; return true; } // negative or NaN
+    const double hz = wall_clock_hz();
+    if (hz <= 0.0) return false;
+    const double ticks = timeout * hz;
+    if (ticks < 1.0) { a->timeout_invalid = 1; return true; }  // shorter than one tick of the clock
+    if (ticks >= 4.6e18) return true;                          // (beyond 2^62 ticks -- centuries: no budget)
+    a->deadline = (unsigned long long)std::ceil(ticks);
+    return true;
+}
+
 bool fill_args(const frp_nmpc_batch *b, const frp_nmpc_options *opt_in, void *ws, size_t ws_bytes, frp::KernelArgs *a)
 {
     if (!b || b->B <= 0 || b->N < 2 || b->N > 64 || b->M < 0 || b->MF < 0 || b->MF > b->M || b->MF > frp::FRP_MAX_FACES) return false;
@@ -73,7 +105,7 @@ bool fill_args(const frp_nmpc_batch *b, const frp_nmpc_options *opt_in, void *ws
     a->variant_B = 0;
     a->slot_reserve = 0;
     a->done_flag = nullptr; a->done_seq = 0;
-    return true;
+    return budget_args(o.timeout, a);
 }
 
 // ---- single-problem context of the drop-in ABI: created lazily on first call, freed at unload
@@ -258,10 +290,18 @@ int forces_solve(int model, frp_forces_params *params, frp_forces_output *output
     // FORCES' entry point has no options argument: the one option a caller of a SINGLE solve may want -- the latency option
     // frp_nmpc_options.twist -- comes from the environment (FRP_NMPC_TWIST = m or -1; unset / 0: the plain solve)
     static const int env_twist = [] { const char *e = getenv("FRP_NMPC_TWIST"); return e ? atoi(e) : 0; }();
+    // ... and so does the wall-clock budget of one call, frp_nmpc_options.timeout (FRP_NMPC_TIMEOUT = seconds; unset: none)
+    static const double env_timeout = [] { const char *e = getenv("FRP_NMPC_TIMEOUT"); return e && *e ? strtod(e, nullptr) : 0.0; }();
     frp_nmpc_options opt;
     frp_nmpc_default_options(&opt);
     opt.twist = env_twist;
+    opt.timeout = env_timeout;
     if (!fill_args(&b, &opt, g_ctx.d_ws, g_ctx.ws_bytes, &a)) return FRP_EXIT_PARAM_VALUE;
+    if (a.timeout_invalid) { // nothing is solved: the initial guess comes back (FORCESNLPsolver_normal.h:136)
+        std::memcpy(output->x, params->x0, 340 * sizeof(double));
+        if (fs) fprintf(fs, "INVALID_TIMEOUT - the wall-clock budget FRP_NMPC_TIMEOUT is negative, NaN or shorter than one clock tick\n");
+        return FRP_EXIT_INVALID_TIMEOUT;
+    }
     a.self_reset = 1;
     static const bool spin_on = [] { const char *e = getenv("FRP_NMPC_DROPIN_SPIN"); return !(e && e[0] == '0'); }();
     const bool spin = zero_copy && spin_on;
@@ -414,6 +454,7 @@ struct HostPipe {
     bool ready = false;
     int device = -1;    // the device the streams, events and buffers below belong to (the one current at their creation)
     hipStream_t s_in = nullptr, s_solve = nullptr, s_out = nullptr;
+    unsigned long long *d_origin = nullptr; // origin of the wall-clock budget of a call: shared by all its chunks (KernelArgs::origin)
     static constexpr int NSLOT = 3;
     struct Slot {
         double *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr, *d_ws = nullptr;
@@ -433,7 +474,8 @@ struct HostPipe {
         if (s_in) (void)hipStreamDestroy(s_in);
         if (s_solve) (void)hipStreamDestroy(s_solve);
         if (s_out) (void)hipStreamDestroy(s_out);
-        s_in = s_solve = s_out = nullptr;
+        if (d_origin) (void)hipFree(d_origin);
+        s_in = s_solve = s_out = nullptr; d_origin = nullptr;
         ready = false; device = -1;
     }
     void drain_all()
@@ -594,6 +636,7 @@ void frp_nmpc_default_options(frp_nmpc_options *o)
     o->hessian = 1;
     o->diverge_mu = 1e3;
     o->twist = 0;
+    o->timeout = 0.0;
 }
 
 size_t frp_nmpc_workspace_bytes(int B, int N, int MF) { return frp::ws_bytes(B, N, MF); }
@@ -701,7 +744,10 @@ int frp_nmpc_solver_variant(const frp_nmpc_batch *batch, const frp_nmpc_options 
 {
     static double no_ws; // (the selection looks at the shape of the launch, never at the workspace)
     frp::KernelArgs a;
-    if (!buf || n == 0 || !fill_args(batch, opt, &no_ws, SIZE_MAX, &a)) return FRP_ERR_ARG;
+    frp_nmpc_options o; // (nor at the wall-clock budget)
+    if (opt) o = *opt; else frp_nmpc_default_options(&o);
+    o.timeout = 0.0;
+    if (!buf || n == 0 || !fill_args(batch, &o, &no_ws, SIZE_MAX, &a)) return FRP_ERR_ARG;
     buf[0] = 0;
     if (frp_nmpc_device_count() <= 0) return FRP_ERR_NO_DEVICE; // (the choice depends on the device's CU count)
     const char *name = frp::ipm_variant_name(a);
@@ -753,7 +799,8 @@ int frp_nmpc_solve_batch_host(const frp_nmpc_batch *h, const frp_nmpc_options *o
         g_pipe.ready = true; // (from here on release() owns whatever was created; a failure half way releases it again)
         bool ok = hipStreamCreateWithFlags(&g_pipe.s_in, hipStreamNonBlocking) == hipSuccess &&
                   hipStreamCreateWithFlags(&g_pipe.s_solve, hipStreamNonBlocking) == hipSuccess &&
-                  hipStreamCreateWithFlags(&g_pipe.s_out, hipStreamNonBlocking) == hipSuccess;
+                  hipStreamCreateWithFlags(&g_pipe.s_out, hipStreamNonBlocking) == hipSuccess &&
+                  hipMalloc(reinterpret_cast<void **>(&g_pipe.d_origin), 64) == hipSuccess;
         for (auto &s : g_pipe.slot)
             ok = ok && hipEventCreateWithFlags(&s.e_in, hipEventDisableTiming) == hipSuccess &&
                  hipEventCreateWithFlags(&s.e_solve, hipEventDisableTiming) == hipSuccess &&
@@ -811,6 +858,11 @@ int frp_nmpc_solve_batch_host(const frp_nmpc_batch *h, const frp_nmpc_options *o
         const int rc = pipe_reserve(s, chunk * (in_d + nf_d + md_d) * sizeof(double), chunk * out_d * sizeof(double), frp::ws_bytes((int)chunk, h->N, h->MF));
         if (rc != FRP_OK) return rc;
     }
+    // one wall-clock budget for the whole call: every chunk's launch stamps / reads the call's own origin word, zeroed here in front of
+    // the first one (a chunk's queue header is its slot's, and a slot serves several chunks)
+    frp::KernelArgs budget;
+    if (!budget_args(opt ? opt->timeout : 0.0, &budget)) return FRP_ERR_ARG;
+    if (budget.deadline) FRP_HIP(hipMemsetAsync(g_pipe.d_origin, 0, sizeof(unsigned long long), g_pipe.s_solve));
     auto drain = [&](size_t c) -> int { // chunk c's results: wait for its copy-out, unpack from the pinned block
         HostPipe::Slot &s = g_pipe.slot[c % HostPipe::NSLOT];
         FRP_HIP(hipEventSynchronize(s.e_out));
@@ -882,6 +934,7 @@ int frp_nmpc_solve_batch_host(const frp_nmpc_batch *h, const frp_nmpc_options *o
             frp::KernelArgs ka;
             if (!fill_args(&d, opt, s.d_ws, s.ws_bytes, &ka)) return FRP_ERR_ARG;
             ka.variant_B = h->B;
+            if (ka.deadline) ka.origin = g_pipe.d_origin;
             FRP_HIP(frp::launch_ipm(ka, g_pipe.s_solve));
         }
         FRP_HIP(hipEventRecord(s.e_solve, g_pipe.s_solve));

@@ -181,6 +181,15 @@ typedef __attribute__((address_space(1))) double gdouble;
 typedef __attribute__((address_space(1))) const double cgdouble;
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// The device's wall clock (constant rate: hipDeviceAttributeWallClockRate), read as ONE statement with its own lgkmcnt(0): s_memrealtime
+// is counted on lgkmcnt and returns out of order with LDS reads, so a read left to the compiler's waits would make a counted lgkmcnt(N)
+// around it wait for the wrong operation.  Used outside every section with hand-counted LDS waits (the wall-clock budget).
+__device__ __forceinline__ unsigned long long wall_now()
+{
+    unsigned long long t;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    return t;
+}
 template <typename T>
 __device__ __forceinline__ T *uni(T *p)
 {

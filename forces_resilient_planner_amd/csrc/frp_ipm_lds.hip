@@ -462,6 +462,11 @@ struct Ctl { // workgroup-shared control words
     unsigned dec_tag;
     int dec_stop, dec_flag;
     int head_first; // (Q4) >= 0: this workgroup was first on its CU and took a head-start problem (KernelArgs::head_start): its first solve holds the CU's mark
+    // wall-clock budget (KernelArgs::deadline != 0): the one decision of an iteration -- lane 0 of role 2 reads the clock once and leaves
+    // "past the deadline" here before barrier A; every wave's termination test reads it behind that barrier (a clock read is not the same
+    // in two waves: waves that decided apart would wait at different barriers)
+    int tmo;
+    unsigned long long t_end; // origin + deadline on the wall clock (kernel prologue)
 };
 
 typedef __attribute__((address_space(3))) Ctl lctl_t;
@@ -2708,6 +2713,12 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
             W1_SEG(1);
         }
         if constexpr (FACES_FIRST) { FRP_SB(); model_block(); W1_SEG(0); }
+        if constexpr (wave == 2) { // the budget's decision of this iteration (Ctl::tmo), behind no hand-counted LDS waits
+            if (a.deadline) {
+                const unsigned long long now = wall_now();
+                if (lane == 0) sh.ctl->tmo = now >= sh.ctl->t_end;
+            }
+        }
         BAR_P(0); // ------------------------------------------------------------- A
         // FRP_EARLY_FACTOR: the Riccati wave does not take part in the termination test -- ~2 k cycles of LDS reads and reductions in front of
         // its 46 k-cycle predictor, on the chain of every iteration -- but starts the factorisation at once; the helper waves, idle until
@@ -2737,6 +2748,7 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
                 if (!(nm.eq == nm.eq) || !(nm.rs == nm.rs) || !(nm.gap == nm.gap)) { stop_flag = FRP_EXIT_BADFUNCEVAL; stop = 1; }
                 else if (nm.eq <= a.tol_eq && nm.in <= a.tol_ineq && nm.rs <= a.tol_stat && nm.rc <= a.tol_comp) { stop_flag = FRP_EXIT_OPTIMAL; stop = 1; }
                 else if (it >= a.maxit) { stop_flag = FRP_EXIT_MAXIT; stop = 1; }
+                else if (uni(sh.ctl->tmo)) { stop_flag = FRP_EXIT_TIMEOUT; stop = 1; } // (Ctl::tmo: 0 without a budget)
                 else if (mu > a.diverge_mu * fmax(1.0, a.mu0) || nm.rs > DIVERGE_RS) { stop_flag = FRP_EXIT_NOPROGRESS; stop = 1; }
             }
             if constexpr (EARLY && wave == 2) {
@@ -3355,7 +3367,14 @@ __global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(
     Shared sh;
     sh.recs = (ldouble *)s_recs; sh.xs = (ldouble *)s_xs; sh.tw = (ldouble *)s_tw; sh.ctl = &s_ctl; sh.cukey = -1; sh.late = 0; sh.rsimd = -1;
     if (TW && threadIdx.x == 0) { s_tw[TW_DUMP] = 0.0; s_tw[TW_ZERO] = 0.0; s_ctl.fail1 = 0; s_ctl.fail2 = 0; }
-    if (threadIdx.x == 0) { s_xs[X_C0] = 0.0; s_xs[X_C1] = 1.0; s_ctl.dec_tag = 0xffffffffu; s_ctl.dec_stop = 0; s_ctl.head_first = -1; if constexpr (QW) s_place[3] = 1; }
+    if (threadIdx.x == 0) { s_xs[X_C0] = 0.0; s_xs[X_C1] = 1.0; s_ctl.dec_tag = 0xffffffffu; s_ctl.dec_stop = 0; s_ctl.head_first = -1; s_ctl.tmo = 0; if constexpr (QW) s_place[3] = 1; }
+    if (a.deadline) { // the origin of the budget: stamped by the first workgroup of the scope to get here (a global compare-and-swap from 0)
+        const unsigned long long now = wall_now();
+        if (threadIdx.x == 0) {
+            const unsigned long long old = atomicCAS(a.origin, 0ull, now);
+            s_ctl.t_end = (old ? old : now) + a.deadline;
+        }
+    }
     // ---- which wave plays which role.  A wavefront stays on the SIMD it was launched on, and one wavefront of every
     // resident workgroup sits on each SIMD of the CU.  The Riccati role keeps its SIMD busy for ~70 % of an iteration, the
     // three helper roles for 13-18 % each, so the iteration rate of a CU is set by the SIMD with the most work on it.  With
@@ -3462,7 +3481,7 @@ __global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(
     if (wave == 0) {
         role_loop<NP, FL, FREG, 0, TW>(a, sh);
         // (single-problem launches of the drop-in context: this wave made the last claim; the head is zero again for the next call)
-        if (a.self_reset && (threadIdx.x & 63) == 0) *a.counter = 0;
+        if (a.self_reset && (threadIdx.x & 63) == 0) { *a.counter = 0; *reinterpret_cast<unsigned long long *>(a.counter + QUEUE_ORIGIN_INT) = 0ull; } // (and the budget's origin)
     } else if (wave == 1) role_loop<NP, FL, FREG, 1, TW>(a, sh);
     else if (wave == 2 || QW) role_loop<NP, FL, FREG, 2, TW>(a, sh);
     else {

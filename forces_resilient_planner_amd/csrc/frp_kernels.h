@@ -70,7 +70,16 @@ struct KernelArgs {
                            // gather kernel beside the persistent solver workgroups (frp_nmpc_solve_batch_host_begin)
     int *done_flag;        // B == 1 only, or null: a word in host-coherent memory that receives done_seq once every output of the solve is
     int done_seq;          // visible to the host -- the drop-in call spins on it instead of paying a stream synchronisation (~10 us)
+    // wall-clock budget (frp_nmpc_options.timeout, converted by fill_args): ticks of the device's wall clock (s_memrealtime) from the origin,
+    // 0 = no budget.  The origin is stamped by the first workgroup of the scope that finds *origin == 0 (compare-and-swap); null = the
+    // word in the queue header (QUEUE_ORIGIN), zeroed with the queue head in front of every launch -- the scope of one budget is one
+    // launch.  frp_nmpc_solve_batch_host points its chunks at a word of its own: one budget for the whole call.
+    unsigned long long deadline;
+    unsigned long long *origin;
+    int timeout_invalid;   // the budget is negative, NaN or shorter than one tick: no solve -- z = x0, flag FRP_EXIT_INVALID_TIMEOUT, iters 0
 };
+// the origin word of the budget in the queue header (KernelArgs::origin): ints 4-5 (counter[0..2] are the queue's own)
+constexpr int QUEUE_ORIGIN_INT = 4;
 
 constexpr int CU_SLOT_ENTRIES = 2048; // (XCC, SE, SH, CU) of HW_ID
 size_t ws_bytes(int B, int N, int MF);

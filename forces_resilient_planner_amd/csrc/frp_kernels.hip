@@ -127,7 +127,7 @@ __global__ __launch_bounds__(1024) void order_bucket_kernel(int B, const double 
     __shared__ unsigned long long w_lo[16], w_hi[16];
     __shared__ int hist[1024], wtot[16];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (t == 0) { counter[0] = head; counter[1] = 0; counter[2] = 0; } // queue head of the solve that follows on this stream (behind the `head` problems dealt out by counter[2]: KernelArgs::head_start); CUs its long solves have to themselves
+    if (t == 0) { counter[0] = head; counter[1] = 0; counter[2] = 0; *reinterpret_cast<unsigned long long *>(counter + QUEUE_ORIGIN_INT) = 0ull; } // queue head of the solve that follows on this stream (behind the `head` problems dealt out by counter[2]: KernelArgs::head_start); CUs its long solves have to themselves
     for (int i = t; i < CU_SLOT_ENTRIES; i += 1024) cu_slots[i] = 0;
     hist[t] = 0;
     constexpr int KR = 4; // keys per thread held in registers
@@ -361,8 +361,20 @@ size_t ws_bytes(int B, int N, int MF)
 
 __global__ void reset_counter_kernel(int *counter, int *cu_slots)
 {
-    if (threadIdx.x == 0) { counter[0] = 0; counter[1] = 0; counter[2] = 0; }
+    if (threadIdx.x == 0) { counter[0] = 0; counter[1] = 0; counter[2] = 0; *reinterpret_cast<unsigned long long *>(counter + QUEUE_ORIGIN_INT) = 0ull; }
     for (int i = threadIdx.x; i < CU_SLOT_ENTRIES; i += blockDim.x) cu_slots[i] = 0;
+}
+
+// A launch whose budget is invalid (KernelArgs::timeout_invalid) solves nothing: every problem returns its initial guess with
+// FRP_EXIT_INVALID_TIMEOUT after 0 iterations, the diagnostics zero.
+__global__ __launch_bounds__(256) void invalid_timeout_kernel(int B, int N, const double *__restrict__ x0, double *__restrict__ z, int *__restrict__ exitflag,
+                                                              int *__restrict__ iters, double *__restrict__ info)
+{
+    const size_t nz = (size_t)B * N * 17, ni = info ? (size_t)B * FRP_INFO_STRIDE : 0, stride = (size_t)gridDim.x * blockDim.x;
+    const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t i = t0; i < nz; i += stride) z[i] = x0[i];
+    for (size_t i = t0; i < ni; i += stride) info[i] = 0.0;
+    for (size_t i = t0; i < (size_t)B; i += stride) { exitflag[i] = FRP_EXIT_INVALID_TIMEOUT; iters[i] = 0; }
 }
 
 static int lds_resident_slots(int B, const KernelArgs &k)
@@ -459,6 +471,11 @@ const char *ipm_variant_name(const KernelArgs &a)
 hipError_t launch_ipm(const KernelArgs &a, hipStream_t stream)
 {
     if (!lds_kernel_supports(a.N, a.MF)) return hipErrorInvalidValue; // (fill_args rejects these before they get here)
+    if (a.timeout_invalid) {
+        const unsigned blocks = (unsigned)std::min<size_t>(1024, ((size_t)a.B * a.N * 17 + 255) / 256);
+        hipLaunchKernelGGL(invalid_timeout_kernel, dim3(blocks), dim3(256), 0, stream, a.B, a.N, a.x0, a.z, a.exitflag, a.iters, a.info);
+        return hipGetLastError();
+    }
     KernelArgs k = a;
     double *q = a.ws;
     k.pws = pws_of(a);
@@ -470,6 +487,7 @@ hipError_t launch_ipm(const KernelArgs &a, hipStream_t stream)
     }
     k.counter = reinterpret_cast<int *>(q);
     k.cu_slots = reinterpret_cast<int *>(q + 32);
+    if (!k.origin) k.origin = reinterpret_cast<unsigned long long *>(k.counter + QUEUE_ORIGIN_INT); // (one launch = one budget)
     // Long solves get their CU to themselves (frp_ipm_lds.hip, Q4 variants): from iteration `iso_it` on the other workgroups of the CU
     // finish what they have and wait -- the launch ends with its longest solve, and a solve alone on a CU iterates a quarter faster.
     // At most `iso_cap` CUs at a time (a workload of long solves must not idle the chip).  FRP_ISO_IT=0 switches it off.

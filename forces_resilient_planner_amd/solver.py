@@ -15,7 +15,7 @@ from . import layout as L
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FRP_LIB") or os.path.join(_PKG, "libfrp_nmpc_amd.so")  # FRP_LIB: an experiment build (tools/build_variant.sh)
 INFO_STRIDE = 12
-ABI_VERSION = 6  # FRP_NMPC_ABI_VERSION of include/frp_nmpc.h
+ABI_VERSION = 7  # FRP_NMPC_ABI_VERSION of include/frp_nmpc.h
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -24,7 +24,8 @@ c_int_p = ctypes.POINTER(ctypes.c_int)
 class Options(ctypes.Structure):
     _fields_ = [("maxit", ctypes.c_int), ("tol_stat", ctypes.c_double), ("tol_eq", ctypes.c_double),
                 ("tol_ineq", ctypes.c_double), ("tol_comp", ctypes.c_double), ("mu0", ctypes.c_double),
-                ("ftb", ctypes.c_double), ("hessian", ctypes.c_int), ("diverge_mu", ctypes.c_double), ("twist", ctypes.c_int)]
+                ("ftb", ctypes.c_double), ("hessian", ctypes.c_int), ("diverge_mu", ctypes.c_double), ("twist", ctypes.c_int),
+                ("timeout", ctypes.c_double)]  # seconds of wall clock per scope, 0 = no budget (frp_nmpc_options.timeout)
 
 
 class Batch(ctypes.Structure):

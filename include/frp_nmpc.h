@@ -49,9 +49,12 @@ extern "C" {
 #define FRP_EXIT_BADFUNCEVAL (-6)
 #define FRP_EXIT_NOPROGRESS (-7)
 #define FRP_EXIT_PARAM_VALUE (-11)
-/* Values of the reference's list that this solver NEVER returns (FORCESNLPsolver_normal.h:110-139): 2 TIMEOUT (:118 -- there is no
-   wall-clock budget: the iteration limit `maxit` bounds a solve, and exhausting it is 0 = MAXIT), -4 (wrong number of inequalities:
-   the face counts are validated as -11), -12 PARAM_VALUE_TIMEOUT (:136).  A caller that switches on them needs no new case. */
+/* Wall-clock budget (frp_nmpc_options.timeout): the solve of a problem stopped by the budget returns 2; a budget that is negative, NaN or
+   positive but shorter than one tick of the device's wall clock makes every problem return -12 without being solved. */
+#define FRP_EXIT_TIMEOUT 2           /* FORCESNLPsolver_normal.h:118 */
+#define FRP_EXIT_INVALID_TIMEOUT (-12) /* FORCESNLPsolver_normal.h:136 */
+/* The one value of the reference's list that this solver NEVER returns (FORCESNLPsolver_normal.h:110-139): -4 (wrong number of
+   inequalities: the face counts are validated as -11).  A caller that switches on it needs no new case. */
 /* Return values of the two drop-in entry points that are NOT solver outcomes.  The reference's callers accept a plan only on
    exitflag == 1 (nmpc_solver.cpp:398) and treat every other value alike, so these are safe for them; a caller that looks
    closer can tell a machine problem from a bad parameter:
@@ -74,7 +77,7 @@ extern "C" {
  * struct of this header gains, loses or moves a field or FRP_INFO_STRIDE changes: a caller built against another header would
  * hand over short structs / a short info array.  Call FRP_NMPC_ABI_CHECK() once after loading the library (the C++ adapter and the
  * Python loader do) and refuse to continue unless it returns FRP_OK. */
-#define FRP_NMPC_ABI_VERSION 6
+#define FRP_NMPC_ABI_VERSION 7
 int frp_nmpc_abi_version(void);
 /* FRP_OK when the caller's header agrees with the library on the version, on the size of frp_nmpc_options and frp_nmpc_batch and
  * on the info stride; FRP_ERR_ARG otherwise (with one line on stderr saying what differs). */
@@ -105,6 +108,19 @@ typedef struct frp_nmpc_options {
                          once the GPU is full (+3 % at 4096 problems).  The Newton direction carries the penalty's
                          rounding (~1e-5 relative); residuals and termination tests are the plain solve's, so the
                          same KKT points are reached (oracle: orc_options.twist).  DESIGN 9.1                     */
+    double timeout;   /* 0 (default) or +inf: no budget.  > 0: wall-clock budget of ONE SCOPE in seconds, measured on the device's
+                         wall clock (hipDeviceAttributeWallClockRate) from the moment the first workgroup of the scope's first
+                         solver launch starts: one frp_nmpc_solve_batch launch, one whole frp_nmpc_solve_batch_host call (all
+                         its chunks), one _host_begin ticket.  A solve still iterating past the deadline stops at the next
+                         iteration's termination test with FRP_EXIT_TIMEOUT (precedence BADFUNCEVAL > OPTIMAL > MAXIT > TIMEOUT
+                         > NOPROGRESS); a problem taken off the queue after it stops at iteration 0.  A problem that stops
+                         with 2 after k iterations returns exactly what the same launch returns with maxit = k (z, iters,
+                         info), only the flag differs.  WHICH problems time out depends on the launch order (longest
+                         expected solve first) and on the load of the device.  Expected bound (not measured here): a launch
+                         ends by the deadline + one iteration of each solve in flight + the prologues of the problems not
+                         yet started.  Negative, NaN, or positive but below one tick: every problem gets
+                         FRP_EXIT_INVALID_TIMEOUT, iters 0, z = x0, nothing is solved, the call returns FRP_OK.
+                         The drop-in entry points read it from the environment variable FRP_NMPC_TIMEOUT.  INTEGRATION.md */
 } frp_nmpc_options;
 
 typedef struct frp_nmpc_batch {
