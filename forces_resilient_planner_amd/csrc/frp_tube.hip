@@ -13,9 +13,19 @@
 //   * the Sylvester solution of  Phi X + X Phi' = N - e^{-Phi t} N e^{-Phi' t},  N = t w^2 d d',  is the Gramian
 //     X = t w^2 int_0^t (e^{-Phi s} d)(e^{-Phi s} d)' ds  (differentiate the integrand; the Gramian always solves
 //     the equation, and the solution is unique unless two eigenvalues of Phi sum to zero).  The integrand is
-//     entire and ||Phi|| t < 2, so 8-point Gauss-Legendre is exact to rounding; the vectors e^{-Phi s_j} d are
-//     stepped node to node with a 14-term Taylor series (||Phi|| ds < 0.4);
-//   * only rows 0..2 of e^{Phi t} are used (the position block): three Taylor-stepped vectors e^{Phi' t} e_j;
+//     entire, of exponential type 2 ||Phi||: 8-node Gauss-Legendre on a panel of length tp is exact to rounding while ||Phi|| tp
+//     is small enough, and the vectors e^{-Phi s_j} d are stepped node to node with a 14-term Taylor series.  DOMAIN, measured
+//     against the 50-digit fixture tests/golden/tube_mp.npz (tests/test_oracle_tube.py, this arithmetic compiled for the CPU):
+//     with nu = ||Phi||_1 t (||Phi||_1 is 1.03 to 1.92 times ||Phi||_2 on the fixture), ONE panel gives the stage's Qd to 6e-14
+//     of its largest entry for nu < 6, 5e-12 .. 8e-12 for 6 <= nu < 8, 7e-10 at 10 .. 14 and 2e-7 at 25 .. 30.  Plans inside the
+//     stage bounds have nu 0.5 .. 2.3 at Ts = 0.05, up to 3.7 at 0.08 and 4.6 at 0.1; three times the thrust bound gives 5.3 at
+//     0.05, 8.5 at 0.08, 30 at 0.3.  So [0, t] is split into ceil(nu / 5) equal panels per stage (TB_NU0; at most
+//     FRP_TUBE_MAX_PANELS = 16), the node steps run on across the panel ends, and the fixture is met to 6e-14 (Qd) / 1.2e-13 (E)
+//     at every Ts from 0.02 to 0.3 (nu up to 30, six panels; more panels than that are not compared with anything).  A stage with
+//     nu > 80 (or not a number) is OUTSIDE the domain: the work stays bounded (16 panels) and every E of that planner is NaN --
+//     never digits lost in silence.  frp_nmpc_tube_batch refuses a Ts at which a plan inside the stage bounds could get there;
+//   * only rows 0..2 of e^{Phi t} are used (the position block): three Taylor-stepped vectors e^{Phi' t} e_j, two 24-term steps
+//     per panel (the rows agree with the fixture to 4e-16 of their largest entry over the whole range);
 //   * Phi is never formed densely: rows 0..2 are [0 I 0], rows 6..8 are the constant gain rows, so a product with
 //     Phi or Phi' is 21 variable + 15 constant multiply-adds;
 //   * sqrtm of the (symmetric positive definite) 3x3 sum by cyclic Jacobi, E = V sqrt(L) V'.
@@ -29,155 +39,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
+#include "frp_tube_math.hpp"
 
 namespace frp {
-
-#ifndef FRP_TB_GSTEPS
-#define FRP_TB_GSTEPS 2
-#define FRP_TB_GTERMS 24
-#endif
-constexpr int TB_NZ = 17, TB_SYM = 45, TB_STAGES_PER_WAVE = 21, TB_TAYLOR = 14, TB_GSTEPS = FRP_TB_GSTEPS, TB_GTERMS = FRP_TB_GTERMS;
-
-// K rows 0..2 (nmpc_solver.cpp:28-30); row 3 = [0 0 -8 0 0 -6 0 0 0] (:31) is folded into PhiS::b8 / m3.
-#define TB_K(a, j) (tb_gain[(a) * 9 + (j)])
-__device__ constexpr double tb_gain[27] = {-2.0, 5.0, 0.0, -1.0, 4.0, 0.0, -8.0, 0.0, 0.0,
-                                           -5.0, -2.0, 0.0, -4.0, -1.0, 0.0, 0.0, -8.0, 0.0,
-                                           -2.0, -2.0, 0.0, -1.0, -1.0, 0.0, 0.0, 0.0, -8.0};
-__device__ constexpr double tb_glx[8] = {-0.9602898564975362, -0.7966664774136267, -0.525532409916329, -0.18343464249564978,
-                                         0.18343464249564978, 0.525532409916329,   0.7966664774136267, 0.9602898564975362};
-__device__ constexpr double tb_glw[8] = {0.10122853629037669, 0.22238103445337434, 0.31370664587788705, 0.36268378337836177,
-                                         0.36268378337836177, 0.31370664587788705, 0.22238103445337434, 0.10122853629037669};
-
-struct PhiS {          // the variable rows 3..5 of Phi = A + B K
-    double b8[3];      // column 2:  -8 * B(3+a, 3)
-    double m3[3][3];   // columns 3..5: R drag R' with -6 * B(3+a, 3) added to column 5
-    double m6[3][3];   // columns 6..8: d a / d (roll, pitch, yaw)
-};
-
-__device__ __forceinline__ int sym_index(int m, int n) { return m * 9 - (m * (m - 1)) / 2 + (n - m); } // m <= n
-
-// updateMatrix (:615-699) + eulerToRot (:554-565); R out row-major
-__device__ void build_phi(const double *z, double mass, double drag, PhiS &P, double R[9])
-{
-    const double thrust = z[3], v1 = z[11], v2 = z[12], v3 = z[13], roll = z[14], pitch = z[15], yaw = z[16];
-    double sr, cr, sp, cp, sy, cy;
-    sincos(roll, &sr, &cr); sincos(pitch, &sp, &cp); sincos(yaw, &sy, &cy);
-    const double c0 = thrust / mass;
-    const double c5 = cp * sp, c6 = cp * sr, c7 = cp * cr, c8 = sp * cr, c9 = sp * sr;
-    const double c1 = cr * sy - c9 * cy, c2 = sr * cy - c8 * sy, c3 = cr * cy + c9 * sy, c4 = sr * sy + c8 * cy;
-    // R = Rz Ry Rx
-    R[0] = cy * cp; R[1] = cy * c9 - sy * cr; R[2] = cy * c8 + sy * sr;
-    R[3] = sy * cp; R[4] = sy * c9 + cy * cr; R[5] = sy * c8 - cy * sr;
-    R[6] = -sp;     R[7] = c6;                R[8] = c7;
-    const double t10 = c6 * c4 - c7 * c1, t11 = c3 * c4 + c1 * c2, t12 = c6 * c2 - c7 * c3;
-    P.m6[0][0] = c0 * c1 + drag * (v3 * t10 + v2 * t11 - 2 * v1 * c4 * c1);
-    P.m6[1][0] = -c0 * c3 + drag * (v1 * t11 - v3 * t12 - 2 * v2 * c3 * c2);
-    P.m6[2][0] = -c0 * c6 + drag * (v1 * t10 - v2 * t12 + 2 * v3 * c7 * c6);
-    const double sr2 = sr * sr, cp2 = cp * cp, sp2 = sp * sp;
-    const double t20 = cy * (sp2 - cp2 + cp2 * sr2) + c9 * c1;
-    const double t21 = 2 * c5 * cy * sy - c6 * (cy * c3 + sy * c1);
-    const double t22 = sy * (cp2 - sp2 - cp2 * sr2) + c9 * c3;
-    P.m6[0][1] = c0 * c7 * cy + drag * (v3 * t20 - v2 * t21 - v1 * 2 * (c5 * cy * cy + c6 * c1 * cy));
-    P.m6[1][1] = c0 * c7 * sy - drag * (v3 * t22 - v1 * t21 - v2 * 2 * (c5 * sy * sy - c6 * c3 * sy));
-    P.m6[2][1] = -c0 * c8 + drag * (v1 * t20 - v2 * t22 + v3 * 2 * (c5 - c5 * sr2));
-    const double t30 = 2 * drag * (c3 * c1 - cp2 * cy * sy), t31 = drag * (c6 * c3 - c5 * sy);
-    const double t32 = drag * (c3 * c3 - c1 * c1 - cp2 * cy * cy + cp2 * sy * sy), t33 = drag * (c6 * c1 + c5 * cy);
-    P.m6[0][2] = c0 * c2 + v1 * t30 - v3 * t31 - v2 * t32;
-    P.m6[1][2] = c0 * c4 - v1 * t32 - v3 * t33 - v2 * t30;
-    P.m6[2][2] = -v2 * t33 - v1 * t31;
-    // R diag(drag, drag, 0) R'
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) P.m3[a][c] = drag * (R[3 * a] * R[3 * c] + R[3 * a + 1] * R[3 * c + 1]);
-    const double bt[3] = {c4 / mass, -c2 / mass, c7 / mass}; // Bt_(3..5, 3) (:692-694)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { P.b8[a] = -8.0 * bt[a]; P.m3[a][2] += -6.0 * bt[a]; }
-}
-
-__device__ __forceinline__ void phi_mul(const PhiS &P, const double v[9], double o[9])
-{
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        o[a] = v[3 + a];
-        double s = P.b8[a] * v[2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s += P.m3[a][c] * v[3 + c] + P.m6[a][c] * v[6 + c];
-        o[3 + a] = s;
-        double g = 0.0;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) if (TB_K(a, j) != 0.0) g += TB_K(a, j) * v[j];
-        o[6 + a] = g;
-    }
-}
-
-__device__ __forceinline__ void phiT_mul(const PhiS &P, const double v[9], double o[9])
-{
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double s0 = 0.0, s3 = v[c], s6 = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (TB_K(a, c) != 0.0) s0 += TB_K(a, c) * v[6 + a];
-            s3 += P.m3[a][c] * v[3 + a];
-            if (TB_K(a, 3 + c) != 0.0) s3 += TB_K(a, 3 + c) * v[6 + a];
-            s6 += P.m6[a][c] * v[3 + a];
-            if (TB_K(a, 6 + c) != 0.0) s6 += TB_K(a, 6 + c) * v[6 + a];
-        }
-        if (c == 2) s0 += P.b8[0] * v[3] + P.b8[1] * v[4] + P.b8[2] * v[5];
-        o[c] = s0; o[3 + c] = s3; o[6 + c] = s6;
-    }
-}
-
-// v <- exp(h Phi) v  (TRANSPOSED: exp(h Phi') v), |h| ||Phi|| < 0.5: the TB_TAYLOR-term series in Horner form,
-// v + h Phi (v + h/2 Phi (v + h/3 Phi (...))) -- one product with Phi and nine multiply-adds per term (round 5; the term-by-term sum
-// cost a scaling and an addition per entry on top: 0.20 -> 0.18 ms per 4096 planners, same values to rounding)
-template <bool TRANSPOSED, int TERMS = TB_TAYLOR>
-__device__ __forceinline__ void expm_step(const PhiS &P, double h, double v[9])
-{
-    double y[9], nxt[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) y[j] = v[j];
-    for (int n = TERMS; n >= 1; --n) {
-        if (TRANSPOSED) phiT_mul(P, y, nxt); else phi_mul(P, y, nxt);
-        const double f = h / (double)n;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) y[j] = __builtin_fma(f, nxt[j], v[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < 9; ++j) v[j] = y[j];
-}
-
-// principal square root of a symmetric positive definite 3x3 (q = xx xy xz yy yz zz), cyclic Jacobi; out row-major
-__device__ void sqrt_sym3(const double q[6], double E[9])
-{
-    double a00 = q[0], a01 = q[1], a02 = q[2], a11 = q[3], a12 = q[4], a22 = q[5];
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-#define TB_ROT(app, aqq, apq, arp, arq, p, q_)                                                   \
-    if (apq != 0.0) {                                                                            \
-        const double th = (aqq - app) / (2.0 * apq);                                             \
-        const double t = copysign(1.0, th) / (fabs(th) + sqrt(th * th + 1.0));                   \
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;                                     \
-        app -= t * apq; aqq += t * apq; apq = 0.0;                                               \
-        const double rp = arp, rq = arq;                                                         \
-        arp = c * rp - s * rq; arq = s * rp + c * rq;                                            \
-        _Pragma("unroll") for (int i = 0; i < 3; ++i) {                                          \
-            const double vp = V[i][p], vq = V[i][q_];                                            \
-            V[i][p] = c * vp - s * vq; V[i][q_] = s * vp + c * vq;                               \
-        }                                                                                        \
-    }
-    for (int sweep = 0; sweep < 8; ++sweep) {
-        TB_ROT(a00, a11, a01, a02, a12, 0, 1)
-        TB_ROT(a00, a22, a02, a01, a12, 0, 2)
-        TB_ROT(a11, a22, a12, a01, a02, 1, 2)
-    }
-#undef TB_ROT
-    const double l[3] = {sqrt(fmax(a00, 0.0)), sqrt(fmax(a11, 0.0)), sqrt(fmax(a22, 0.0))};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) E[3 * i + j] = l[0] * V[i][0] * V[j][0] + l[1] * V[i][1] * V[j][1] + l[2] * V[i][2] * V[j][2];
-}
 
 // LDS per stage: Qd (45) | G rows 0..2 of exp(Phi t) (27) | Q1 (6) | Q2 (6) | tr Qd (1)
 constexpr int TS_QD = 0, TS_G = 45, TS_Q1 = 72, TS_Q2 = 78, TS_TR = 84, TS_STRIDE = 85;
@@ -199,6 +63,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int e = 0; e < TB_SYM; ++e) X[e] = 0.0;
     double rootTr = 0.0;
+    bool outside = false; // a stage of this planner lies outside the kernel's domain (see the header comment)
     if (live) {
         PhiS P;
         {
@@ -216,26 +81,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         st[TS_Q1 + e++] = er * (R[3 * a] * R[3 * c] + R[3 * a + 1] * R[3 * c + 1]) + eh * R[3 * a + 2] * R[3 * c + 2];
             }
         }
-        double v[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) v[j] = (j == ch) ? 1.0 : 0.0;
-        // (rows of exp(Phi t): TB_GSTEPS equal steps.  Eight 14-term steps covered |h| ||Phi|| < 0.5 to rounding; two 24-term steps cover the
-        // same range of ||Phi|| t (< 4: 2^25 / 25! = 2e-18) with 48 products instead of 112, at exp(2) ~ 7 roundings of cancellation instead of 2)
-        for (int n = 0; n < TB_GSTEPS; ++n) expm_step<true, TB_GTERMS>(P, t / TB_GSTEPS, v);
-#pragma unroll
-        for (int j = 0; j < 9; ++j) { st[TS_G + 9 * ch + j] = v[j]; v[j] = (j == 3 + ch) ? 1.0 : 0.0; }
-        double s_prev = 0.0;
-        for (int n = 0; n < 8; ++n) {
-            const double s = 0.5 * t * (1.0 + tb_glx[n]);
-            expm_step<false>(P, -(s - s_prev), v);
-            s_prev = s;
-            const double wgt = 0.5 * t * tb_glw[n];
-            int e = 0;
-#pragma unroll
-            for (int m = 0; m < 9; ++m)
-#pragma unroll
-                for (int nn = m; nn < 9; ++nn) X[e++] += wgt * v[m] * v[nn];
-        }
+        // panels of this stage's quadrature (and, times TB_GSTEPS, steps of its rows of exp(Phi t)) from nu = ||Phi||_1 t: one panel up to
+        // TB_NU0, which covers every plan inside the stage bounds at Ts <= 0.1
+        int panels = tube_panels(phi_norm1(P) * t);
+        if (panels == 0) { outside = true; panels = TB_MAX_PANELS; } // bounded work for an absurd plan; its output is marked below
+        tube_lane(P, t, panels, ch, st + TS_G + 9 * ch, X);
         const double scale = t * p.noise[ch] * p.noise[ch]; // N = t w^2 d d' (:591)
         double tr = 0.0;
 #pragma unroll
@@ -254,7 +104,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (live && e % 3 == ch) st[TS_QD + e] = q;
     }
     if (live && ch == 0) st[TS_TR] = temp * temp; // tr Qd = temp * sum_i tr(X_i)/sqrt(tr X_i) = temp^2
-    __syncthreads();
+    const int refused = __syncthreads_or(outside);
 
     // ---- the stage recursion of getDistrEllipsoid's Q_origin (:603-608), 45 lanes ------------------------------
     int em = 0, en = 0; // (row, col) of packed entry tid
@@ -314,7 +164,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int j = 0; j < 9; ++j) s_out[9 * tid + j] = E[j];
     }
     __syncthreads();
-    for (int e = tid; e < 9 * p.N; e += blockDim.x) p.ellipsoid[(size_t)b * 9 * p.N + e] = s_out[e];
+    // a planner with a stage outside the domain gets NaN in every E: loud, where lost digits would be silent
+    for (int e = tid; e < 9 * p.N; e += blockDim.x) p.ellipsoid[(size_t)b * 9 * p.N + e] = refused ? __builtin_nan("") : s_out[e];
 }
 
 } // namespace frp
@@ -324,6 +175,13 @@ extern "C" int frp_nmpc_tube_batch(const frp_nmpc_tube *p, void *stream)
     if (!p || p->B <= 0 || p->N < 1 || p->N > 64 || !p->mpc_output || !p->ellipsoid) return FRP_ERR_ARG;
     if (!(p->mass > 0.0) || !(p->Ts > 0.0) || !(p->epsilon > 0.0) || !(p->ego_r > 0.0) || !(p->ego_h > 0.0)) return FRP_ERR_ARG;
     for (int i = 0; i < 3; ++i) if (!(p->noise[i] > 0.0)) return FRP_ERR_ARG;
+    // Ts so large that a plan INSIDE the stage bounds could leave the kernel's domain (include/frp_nmpc.h has the derivation): the
+    // largest absolute column sum of Phi over those plans, column by column
+    const double r3 = sqrt(3.0), dr = fabs(p->drag);
+    double phi1 = fmax(9.0, 8.0 * r3 / p->mass);                                                              // columns 0, 1; 2
+    phi1 = fmax(phi1, fmax(7.0 + r3 * dr, 1.0 + r3 * (dr + 6.0 / p->mass)));                                  // columns 3, 4; 5
+    phi1 = fmax(phi1, 8.0 + r3 * (FRP_TUBE_THRUST_MAX / p->mass + 2.0 * dr * FRP_TUBE_SPEED_MAX));            // columns 6 .. 8
+    if (!(p->Ts * phi1 <= frp::TB_NU0 * frp::TB_MAX_PANELS)) return FRP_ERR_ARG;
     const int waves = (p->N + frp::TB_STAGES_PER_WAVE - 1) / frp::TB_STAGES_PER_WAVE;
     const int tail = 9 * p->N > frp::TB_SYM ? 9 * p->N : frp::TB_SYM;
     const size_t lds = ((size_t)p->N * frp::TS_STRIDE + tail + 54) * sizeof(double);

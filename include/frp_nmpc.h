@@ -283,6 +283,9 @@ int frp_nmpc_pack_batch(const frp_nmpc_pack *p, void *stream);
 int frp_nmpc_update_batch(int B, int N, const double *z, const int *exitflag, double *mpc_output, void *stream);
 
 /* ---- (4) SURVEY 8f row f-2: tube (ego + disturbance ellipsoid) propagation on the device ---- */
+#define FRP_TUBE_MAX_PANELS 16            /* quadrature panels per stage, at most (see frp_nmpc_tube_batch)               */
+#define FRP_TUBE_THRUST_MAX 14.62315878   /* stage bound of the thrust, 2 g m of the model (mpc_generator_normal.m:33-46) */
+#define FRP_TUBE_SPEED_MAX 3.4641016151377544 /* |v|_2 with every component at its stage bound of 2                     */
 typedef struct frp_nmpc_tube {
     int B, N;                 /* planners, horizon (planning_horizon_, <= 64)                                      */
     const double *mpc_output; /* [B][N+1][17]  plan deque; rows 0..N-1 are linearised (nmpc_solver.cpp:498-501)    */
@@ -295,7 +298,19 @@ typedef struct frp_nmpc_tube {
 
 /* NMPCSolver::setFORCESParams' tube part (nmpc_solver.cpp:484-521) with updateMatrix (:615-699) and
  * getDistrEllipsoid (:567-611) for B planners.  The feedback gain K is the reference's constant (:28-31).
- * Asynchronous on `stream`. */
+ * Asynchronous on `stream`.
+ * DOMAIN.  Per stage the kernel bounds nu = ||Phi||_1 Ts (largest absolute column sum of the closed-loop matrix) and splits
+ * [0, Ts] into ceil(nu / 5) Gauss-Legendre panels, at most FRP_TUBE_MAX_PANELS, which covers nu <= 80.  Measured up to nu = 30
+ * (six panels): agreement with a 50-digit evaluation to 1.2e-13 relative (tests/golden/tube_mp.npz; Ts 0.02 .. 0.3, thrust up
+ * to three times its bound).  Between 30 and 80 the same rule applies but nothing is compared.  A planner
+ * with a stage beyond that (a diverged plan; a NaN) gets NaN in all its E_i; the others of the batch are not affected.
+ * FRP_ERR_ARG for a Ts at which a plan INSIDE the stage bounds could get there:  Ts * phi1 > 80, with
+ *   phi1 = max(9, 8 r / mass, 7 + r drag, 1 + r (drag + 6 / mass), 8 + r (FRP_TUBE_THRUST_MAX / mass + 2 drag FRP_TUBE_SPEED_MAX)),
+ * r = sqrt(3): the column sums of |Phi|.  Rows 6..8 are the gain rows (sums 9 9 0 6 6 0 8 8 8), rows 0..2 add 1 to columns
+ * 3..5, and a column of rows 3..5 is a 3-vector whose 1-norm is at most r times its 2-norm: 8/mass resp. 6/mass times a unit
+ * vector (the thrust direction) in columns 2 and 5, drag R diag(1,1,0) R' (2-norm <= drag) in columns 3..5, and in columns
+ * 6..8 thrust/mass times the derivative of a unit vector by an Euler angle (<= 1) plus drag times the derivative of
+ * R diag(1,1,0) R' v (<= 2 |v|).  With the defaults phi1 = 46.2: Ts <= 1.73. */
 int frp_nmpc_tube_batch(const frp_nmpc_tube *p, void *stream);
 
 /* ---- (5) SURVEY 8f row f-3: corridor generation / selection on the device ---- */

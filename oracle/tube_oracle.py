@@ -18,13 +18,15 @@ before each NLP solve (reference: src/resilient_planner/plan_manage/src/nmpc_sol
 The same numerical methods as the reference's Eigen calls are used (complex Schur + triangular Sylvester =
 Bartels-Stewart via scipy.linalg.solve_sylvester, Pade expm, general eigendecomposition for sqrtm).
 
-PARITY UNPINNED: Eigen (and its unsupported MatrixFunctions module) is not in this image and nmpc_solver.cpp
-needs ROS, so the reference cannot be run here and its tests hold no vectors for this function.  The pin that IS
-available: every step is a mathematically defined quantity (the Sylvester solution is unique whenever no two eigenvalues of Phi
-sum to zero -- Phi is Hurwitz near zero yaw, where the reference's gain was designed -- and the square root is the
-principal one), so any FP64 method must agree to rounding; tests check the GPU kernel -- which uses a
-different method (Gauss-Legendre quadrature of the Gramian integral, Jacobi eigen-solver) -- against this
-restatement at 1e-9 relative.
+WHAT IS PINNED: the mathematics.  Every step after updateMatrix is a mathematically defined quantity (the Sylvester solution is
+unique whenever no two eigenvalues of Phi sum to zero -- Phi is Hurwitz near zero yaw, where the reference's gain was designed --
+and the square root is the principal one); tests/tools/gen_tube_mp.py evaluates all of tube_one with mpmath at 80 digits by a
+third method (the Gramian integral) into tests/golden/tube_mp.npz, and tests/test_oracle_tube.py holds this file to it: measured
+error 2e-14 .. 3.4e-12 relative per Ts group (Ts 0.02 .. 0.3, thrust up to three times its bound), asserted at ten times that.
+The GPU kernel -- a different method again (Gauss-Legendre panels, Jacobi) -- is held to the same fixture at the same bound.
+WHAT IS NOT: the transcription of updateMatrix / eulerToRot.  Eigen (and its unsupported MatrixFunctions module) is not in this
+image and nmpc_solver.cpp needs ROS, so the reference cannot be run here and its tests hold no vectors for this function; the
+generator restates the same closed forms, so a slip in them made here would be made there.
 
 Two deliberate deviations from the letter of the reference, both reference defects that make its output depend on
 memory garbage / call history and therefore cannot be a batched, stateless function:
