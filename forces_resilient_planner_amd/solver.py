@@ -90,6 +90,17 @@ class Astar(ctypes.Structure):  # frp_nmpc_astar (include/frp_nmpc.h)
                 ("path_nodes", ctypes.c_void_p), ("retry_pt", ctypes.c_void_p), ("retry_vel", ctypes.c_void_p)]
 
 
+class OccMap(ctypes.Structure):  # frp_nmpc_occmap (include/frp_nmpc.h)
+    _fields_ = [("origin", ctypes.c_double * 3), ("map_size", ctypes.c_double * 3), ("resolution", ctypes.c_double), ("grid", ctypes.c_int * 3),
+                ("clamp_min_log", ctypes.c_double), ("clamp_max_log", ctypes.c_double), ("min_occupancy_log", ctypes.c_double),
+                ("local_radius", ctypes.c_double * 3), ("log_odds", ctypes.c_void_p), ("occ", ctypes.c_void_p)]
+
+
+class OccMapView(ctypes.Structure):  # frp_nmpc_occmap_view (include/frp_nmpc.h)
+    _fields_ = [("B", ctypes.c_int), ("centre", ctypes.c_void_p), ("P", ctypes.c_int), ("local_box", ctypes.c_void_p),
+                ("cloud", ctypes.c_void_p), ("cloud_count", ctypes.c_void_p)]
+
+
 ASTAR_MAX_PATH = 256
 ASTAR_REACH_HORIZON, ASTAR_REACH_END, ASTAR_NO_PATH, ASTAR_REACH_END_BUT_SHOT_FAILS = 1, 2, 3, 4
 
@@ -98,6 +109,10 @@ REFERENCE_PI = 3.1415926  # nmpc_solver.cpp:3
 # getSikangConst's constants (nmpc_solver.cpp:302, :318, :323)
 CORRIDOR_DEFAULTS = dict(bbox=(2.0, 2.0, 1.0), seed_len=0.1, inflation=1.1, offset_x=0.0)
 CORRIDOR_MAX_F = 64
+CORRIDOR_MAX_POINTS = 65536
+
+# OccMap's ROS parameter defaults (occ_map.cpp:752-754) and the local range of the reference's launch files
+OCCMAP_DEFAULTS = dict(clamp_min_log=0.12, clamp_max_log=0.97, min_occupancy_log=0.80, local_radius=(6.0, 6.0, 3.0))
 
 # ROS parameter defaults of the tube model (nmpc_solver.cpp:68-74, nmpc_utils.h:188-189)
 TUBE_DEFAULTS = dict(mass=0.74, drag=0.33, ego_r=0.27, ego_h=0.0425, noise=(0.5, 0.5, 0.5), epsilon=0.06, Ts=0.05)
@@ -132,7 +147,8 @@ EXPORTS = ["frp_nmpc_default_options", "frp_nmpc_workspace_bytes", "frp_nmpc_sol
            "frp_nmpc_kernel_timing_begin", "frp_nmpc_kernel_timing_end", "frp_nmpc_set_q4_min_batch",
            "frp_nmpc_abi_version", "frp_nmpc_abi_check", "frp_nmpc_host_register", "frp_nmpc_host_unregister",
            "frp_nmpc_host_registered", "frp_nmpc_host_unregister_all", "frp_nmpc_solve_batch_host_begin", "frp_nmpc_solve_batch_host_wait",
-           "frp_nmpc_solver_variant"]
+           "frp_nmpc_solver_variant", "frp_nmpc_occmap_workspace_bytes", "frp_nmpc_occmap_reset", "frp_nmpc_occmap_clear_box",
+           "frp_nmpc_occmap_insert_cloud", "frp_nmpc_occmap_refresh", "frp_nmpc_occmap_local_view", "frp_nmpc_occmap_query"]
 
 _lib = None
 
@@ -193,6 +209,18 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        for name in EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+            if not hasattr(l, name):
+                raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
+        pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
+        l.frp_nmpc_occmap_workspace_bytes.restype = ctypes.c_size_t
+        l.frp_nmpc_occmap_workspace_bytes.argtypes = [pm]
+        l.frp_nmpc_occmap_reset.argtypes = [pm, vp, sz, vp]
+        l.frp_nmpc_occmap_refresh.argtypes = [pm, vp, sz, vp]
+        l.frp_nmpc_occmap_clear_box.argtypes = [pm, c_double_p, c_double_p, vp, sz, vp]
+        l.frp_nmpc_occmap_insert_cloud.argtypes = [pm, vp, ctypes.c_int, vp, sz, vp]
+        l.frp_nmpc_occmap_local_view.argtypes = [pm, ctypes.POINTER(OccMapView), vp, sz, vp]
+        l.frp_nmpc_occmap_query.argtypes = [pm, ctypes.c_int, vp, vp, vp, vp, vp, sz, vp]
         _lib = l
     return _lib
 
@@ -453,10 +481,152 @@ def reference_batch_host(kino_path, time_offset, mpc_output, kino_size=None, Ts=
     return rp.cpu().numpy(), ry.cpu().numpy(), fl.cpu().numpy()
 
 
+class LocalView:
+    """What OccupancyMap.local_view returns (device tensors): local_box [B,6] int32 for AstarPlanner.plan / DeviceFleet.replan,
+    cloud [B,P,3] f64 + cloud_count [B] int32 for corridor_batch_device / DeviceFleet.full_tick."""
+
+    def __init__(self, local_box, cloud, cloud_count):
+        self.local_box, self.cloud, self.cloud_count = local_box, cloud, cloud_count
+
+    def overflowed(self):
+        """Planners with more occupied voxels in range than the view stores (their count is minus the true one)."""
+        return self.cloud_count < 0
+
+
+class OccupancyMap:
+    """The reference's OccMap (occ_grid/src/occ_map.cpp) in HBM, shared by all planners (frp_nmpc_occmap_*): the log-odds buffer,
+    the byte grid the A* searches (.occ) and, per planner, the local box and the local obstacle cloud the corridor takes.
+    world: the dict of workloads.astar_world -- its geometry, and its occ as the initial content (occupied voxels at
+    clamp_max_log, the others at clamp_min_log); or explicit origin / map_size / resolution for an empty map.  Depth-image fusion is
+    not part of it (include/frp_nmpc.h (8)): a caller with its own fusion writes .log_odds and calls refresh()."""
+
+    def __init__(self, world=None, origin=None, map_size=None, resolution=None, local_radius=None, clamp_min_log=None,
+                 clamp_max_log=None, min_occupancy_log=None, device="cuda:0"):
+        import torch
+        lib()
+        self.torch = torch
+        self.device = torch.device(device)
+        d = dict(OCCMAP_DEFAULTS)
+        for k, v in (("local_radius", local_radius), ("clamp_min_log", clamp_min_log), ("clamp_max_log", clamp_max_log),
+                     ("min_occupancy_log", min_occupancy_log)):
+            if v is not None:
+                d[k] = v
+        if world is not None:
+            origin = world["origin"] if origin is None else origin
+            map_size = world["map_size"] if map_size is None else map_size
+            resolution = world["resolution"] if resolution is None else resolution
+        self.origin = tuple(float(v) for v in origin); self.map_size = tuple(float(v) for v in map_size)
+        self.resolution = float(resolution)
+        self.local_radius = tuple(float(v) for v in d["local_radius"])
+        self.clamp_min_log, self.clamp_max_log, self.min_occupancy_log = float(d["clamp_min_log"]), float(d["clamp_max_log"]), float(d["min_occupancy_log"])
+        self.grid = tuple(int(np.ceil(m / self.resolution)) for m in self.map_size)  # occ_map.cpp:789
+        self.world = world
+        self.log_odds = torch.empty(self.grid, dtype=torch.float64, device=self.device)
+        self.occ = torch.empty(self.grid, dtype=torch.uint8, device=self.device)
+        m = self._map()
+        self.ws_bytes = int(lib().frp_nmpc_occmap_workspace_bytes(ctypes.byref(m)))
+        if self.ws_bytes == 0:
+            raise ValueError("frp_nmpc_occmap refuses this map description (resolution, map_size, grid)")
+        self.ws = torch.empty((self.ws_bytes // 4 + 1,), dtype=torch.int32, device=self.device)
+        if world is not None and world.get("occ") is not None:
+            o = torch.from_numpy(np.ascontiguousarray(world["occ"], dtype=np.uint8)).to(self.device)
+            assert tuple(o.shape) == self.grid, (tuple(o.shape), self.grid)
+            self.log_odds.fill_(self.clamp_min_log)
+            self.log_odds.masked_fill_(o != 0, self.clamp_max_log)
+            self.refresh()
+        else:
+            self.reset()
+
+    def _map(self):
+        return OccMap((ctypes.c_double * 3)(*self.origin), (ctypes.c_double * 3)(*self.map_size), self.resolution, (ctypes.c_int * 3)(*self.grid),
+                      self.clamp_min_log, self.clamp_max_log, self.min_occupancy_log, (ctypes.c_double * 3)(*self.local_radius),
+                      self.log_odds.data_ptr(), self.occ.data_ptr())
+
+    def _call(self, name, *args, stream=None):
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        m = self._map()
+        _check(getattr(lib(), name)(ctypes.byref(m), *args, ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes, ctypes.c_void_p(s.cuda_stream)), name)
+
+    def _dev(self, a, dtype):
+        t = self.torch
+        if not t.is_tensor(a):
+            a = t.from_numpy(np.ascontiguousarray(a, dtype={t.float64: np.float64, t.float32: np.float32, t.int32: np.int32}[dtype]))
+        a = a.to(self.device, dtype=dtype).contiguous()
+        return a
+
+    def astar_world(self):
+        """The constants AstarPlanner reads: the world this map was built from, or the launch-file defaults around its geometry."""
+        if self.world is not None:
+            return self.world
+        from . import workloads
+        w = dict(workloads.ASTAR_DEFAULTS)
+        w.update(origin=self.origin, map_size=self.map_size, resolution=self.resolution)
+        return w
+
+    def reset(self, stream=None):
+        """Every voxel back to clamp_min_log (occ_map.cpp:831)."""
+        self._call("frp_nmpc_occmap_reset", stream=stream)
+
+    def refresh(self, stream=None):
+        """occ and the bit plane from log_odds, after the caller wrote log_odds itself."""
+        self._call("frp_nmpc_occmap_refresh", stream=stream)
+
+    def clear_box(self, min_pos, max_pos, stream=None):
+        """resetBuffer(min_pos, max_pos) (occ_map.cpp:15-36); host positions."""
+        self._call("frp_nmpc_occmap_clear_box", (ctypes.c_double * 3)(*[float(v) for v in min_pos]), (ctypes.c_double * 3)(*[float(v) for v in max_pos]),
+                   stream=stream)
+
+    def insert_cloud(self, points, stream=None):
+        """globalCloudCallback (occ_map.cpp:600-622): points [P,3] float32 (pcl::PointXYZ; anything else is converted to it first)."""
+        pts = self._dev(points, self.torch.float32)
+        assert pts.dim() == 2 and pts.shape[1] == 3
+        self._call("frp_nmpc_occmap_insert_cloud", ctypes.c_void_p(pts.data_ptr()) if pts.shape[0] else None, int(pts.shape[0]), stream=stream)
+        if stream is not None:
+            pts.record_stream(stream)
+
+    def local_view(self, centres, P, out=None, stream=None):
+        """local_box + localOccVisCallback's cloud (occ_map.cpp:177-215) of every planner: centres [B,3] f64 (device tensor or
+        array), P points stored per planner.  centres = None: the whole map as one cloud (globalOccVisCallback, :150-175), B = 1.
+        out: a LocalView of the same shapes to write into (a captured graph replays into the same buffers).  Nothing is
+        synchronised: cloud_count (negative = overflow, LocalView.overflowed()) is a device tensor."""
+        t = self.torch
+        c = None if centres is None else self._dev(centres, t.float64)
+        B = 1 if c is None else int(c.shape[0])
+        assert c is None or tuple(c.shape) == (B, 3)
+        if out is None:
+            out = LocalView(t.zeros((B, 6), dtype=t.int32, device=self.device), t.zeros((B, P, 3), dtype=t.float64, device=self.device),
+                            t.zeros((B,), dtype=t.int32, device=self.device))
+        assert tuple(out.cloud.shape) == (B, P, 3) and out.cloud.is_contiguous() and tuple(out.local_box.shape) == (B, 6)
+        v = OccMapView(B, c.data_ptr() if c is not None else None, P, out.local_box.data_ptr(), out.cloud.data_ptr() if P else None,
+                       out.cloud_count.data_ptr())
+        self._call("frp_nmpc_occmap_local_view", ctypes.byref(v), stream=stream)
+        if stream is not None and c is not None and c is not centres:
+            c.record_stream(stream)
+        return out
+
+    def query(self, pos, local_box=None, planner=None, stream=None):
+        """getVoxelState (occ_map.cpp:95-106) of pos [Q,3]: int32 [Q] device tensor, -1 outside the map, 0 free or outside the local
+        map, 1 occupied.  local_box [.,6] of a local view with planner [Q] = its row per query (None: row 0)."""
+        t = self.torch
+        q = self._dev(pos, t.float64)
+        Q = int(q.shape[0])
+        st = t.zeros((Q,), dtype=t.int32, device=self.device)
+        pl = None if planner is None else self._dev(planner, t.int32)
+        lb = None if local_box is None else self._dev(local_box, t.int32)
+        self._call("frp_nmpc_occmap_query", Q, ctypes.c_void_p(q.data_ptr()) if Q else None, pl.data_ptr() if pl is not None else None,
+                   lb.data_ptr() if lb is not None else None, ctypes.c_void_p(st.data_ptr()), stream=stream)
+        if stream is not None:
+            for a in (q, pl, lb):
+                if a is not None:
+                    a.record_stream(stream)
+        return st
+
+
 class AstarPlanner:
     """SURVEY 8f row f-4 (second half): the kinodynamic A* of NMPCSolver::getKinoPath for B planners on the device
     (frp_nmpc_astar_batch).  `world`: occupancy grid occ[x][y][z] (uint8) + the map / search constants of the reference's launch
-    files (forces_resilient_planner_amd.workloads.astar_world).  Outputs stay in HBM: kino_path [B,K,3] / kino_size [B] are what
+    files (forces_resilient_planner_amd.workloads.astar_world), or an OccupancyMap: the planner then searches the map's own occ
+    buffer (no copy: later inserts are seen) -- pass the local_box of the map's local view to plan().  Outputs stay in HBM: kino_path [B,K,3] / kino_size [B] are what
     DeviceFleet.references() takes as a per-planner path."""
 
     def __init__(self, world, B, K=1024, Ts=0.05, device="cuda:0", want_path_nodes=False, allocate_num=None):
@@ -465,10 +635,14 @@ class AstarPlanner:
         self.torch = torch
         self.B, self.K, self.Ts = B, K, Ts
         self.device = torch.device(device)
+        self.map = world if isinstance(world, OccupancyMap) else None
+        if self.map is not None:
+            assert self.map.device == self.device
+            world = self.map.astar_world()
         self.world = world
         f64 = dict(dtype=torch.float64, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
-        self.occ = torch.from_numpy(np.ascontiguousarray(world["occ"], dtype=np.uint8)).to(self.device)
+        self.occ = self.map.occ if self.map is not None else torch.from_numpy(np.ascontiguousarray(world["occ"], dtype=np.uint8)).to(self.device)
         self.kino_path = torch.zeros((B, K, 3), **f64)
         self.kino_size = torch.zeros((B,), **i32)
         self.status = torch.zeros((B,), **i32)
@@ -724,7 +898,7 @@ class DeviceFleet:
         reference_batch_device(kino_path, time_offset, self.mpc_output, ref_pos, ref_yaw, replan, kino_size, Ts, stream)
 
     def replan(self, planner, end_pt, external_acc, replan, time_offset=None, end_vel=None, init=True, mass=0.74, g=9.81, stream=None,
-               t_cur=None, odom=None, Ts=0.05):
+               t_cur=None, odom=None, Ts=0.05, local_box=None):
         """The FSM's REPLAN_TRAJ step (nmpc_manage.cpp:215-235 -> NMPCSolver::getKinoPath, nmpc_solver.cpp:145-223) for the planners
         whose tick raised kino_replan_ (`replan` [B] int32, as written by references() / full_tick): a kinodynamic A* to end_pt
         [B,3] with external_acc [B,3] in the primitives, on the device (AstarPlanner = frp_nmpc_astar_batch).
@@ -736,6 +910,8 @@ class DeviceFleet:
         plan's stage-1 state (a warning is issued once); a caller that has odometry passes it.
         The planner object owns the per-planner paths (planner.kino_path / kino_size): pass them to references() / full_tick as the
         path.  Planners that found a path get time_offset = 0 (kino_start_time_ = now, :219) and go back to the normal solver (:218).
+        local_box: int32 [B,6] of OccupancyMap.local_view for a planner built on that map (voxels outside a planner's box read as free,
+        occ_map.cpp:101-102); None: the whole map is local.
         Returns the mask (bool [B]) of planners that received a new path.  Everything here -- the state gather, the search, the
         masks -- is enqueued on `stream` (torch's current stream when None)."""
         t = self.torch
@@ -768,7 +944,7 @@ class DeviceFleet:
             ev = end_vel if end_vel is not None else t.zeros_like(end_pt)
             planner.upload(s_pt.contiguous(), s_v.contiguous(), s_a.contiguous(), end_pt, ev, external_acc,
                            retry=(o_pt.contiguous(), o_v.contiguous()))
-            planner.plan(init=init, active=replan, stream=s)
+            planner.plan(init=init, local_box=local_box, active=replan, stream=s)
             ok = (replan != 0) & (planner.status != ASTAR_NO_PATH)
             if time_offset is not None:
                 time_offset.masked_fill_(ok, 0.0)
@@ -777,17 +953,18 @@ class DeviceFleet:
         return ok
 
     def full_tick(self, external_acc, kino_path, time_offset, cloud, ref_pos, ref_yaw, stream=None, replan=None,
-                  kino_size=None, tube_consts=None, corridor_consts=None, Ts=0.05, coldstart=True, state=None, grid=None):
+                  kino_size=None, tube_consts=None, corridor_consts=None, Ts=0.05, coldstart=True, state=None, grid=None, cloud_count=None):
         """The reference's whole per-tick computation downstream of the A* (NMPCSolver::solveNMPC,
         nmpc_solver.cpp:351-482) for B planners, asynchronous on `stream`, nothing touching the host:
         stage references (f-4) -> tube (f-2) -> corridor (f-3) -> parameter packing (f-1) -> NLP solve -> result
         bookkeeping.  ref_pos [B,N,3] / ref_yaw [B,N] are caller-owned scratch that receives the references.
-        With coldstart (default) planners whose previous solve failed first restart from the constant plan (:363-364)."""
+        With coldstart (default) planners whose previous solve failed first restart from the constant plan (:363-364).
+        cloud [B,P,3] with cloud_count [B]: per-planner clouds, as OccupancyMap.local_view exports them."""
         if coldstart:
             self.coldstart(state, True, stream=stream)
         self.references(kino_path, time_offset, ref_pos, ref_yaw, replan, kino_size, Ts, stream)
         self.tube(tube_consts, stream)
-        self.corridor(cloud, ref_pos, ref_yaw, corridor_consts, stream, grid=grid)
+        self.corridor(cloud, ref_pos, ref_yaw, corridor_consts, stream, cloud_count=cloud_count, grid=grid)
         self.pack(external_acc, ref_pos, ref_yaw, stream)
         self.solver.solve(stream)
         self.update(stream)

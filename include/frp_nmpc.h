@@ -450,6 +450,77 @@ size_t frp_nmpc_astar_workspace_bytes(const frp_nmpc_astar *p);
  * the external acceleration in the primitives, the retry on NO_PATH, getKinoTraj(Ts).  Asynchronous on `stream`. */
 int frp_nmpc_astar_batch(const frp_nmpc_astar *p, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- (8) the occupancy map on the device: one map feeds the A*, the corridor and point queries ---- */
+/* OccMap (occ_grid/src/occ_map.cpp) as the reference's simulation uses it (use_global_map: filled from a cloud by
+ * globalCloudCallback, :600-622).  The caller owns three device buffers: log_odds and occ below, and a workspace of
+ * frp_nmpc_occmap_workspace_bytes() bytes that holds a bit plane of occ (one bit per voxel, packed along z).  The workspace is
+ * PART OF THE MAP: it is written by reset / clear_box / insert_cloud / refresh and read by local_view, and stays with the map for
+ * as long as the map lives.  A caller that writes log_odds itself (its own sensor fusion) calls frp_nmpc_occmap_refresh afterwards.
+ * NOT here: projectDepthImage / raycastProcess (:314-533).  Their cache_rayend_ / cache_traverse_ early exits make the result
+ * depend on the order in which the pixels of a frame are visited, so a frame is a serial computation, and their input is an
+ * OpenCV depth image.
+ * Every call is asynchronous on `stream`, synchronises nothing, returns no host-side count, and can be captured into a hipGraph
+ * (the struct is read during the call; the device arrays it points to are read when the kernels run).  FRP_ERR_ARG is returned
+ * before anything is launched; FRP_ERR_NO_DEVICE without a device.
+ * Where the reference converts a floored double to int unchecked (a NaN, a coordinate beyond int: undefined there) the tests are
+ * made on the double: such a point is outside the map, such a local range is clamped to the map like any other. */
+typedef struct frp_nmpc_occmap {
+    double origin[3];          /* occ_map/origin_* (min_range_, :800)                                                       */
+    double map_size[3];        /* occ_map/map_size_*                                                                        */
+    double resolution;         /* occ_map/resolution; resolution_inv_ = 1 / resolution (:787)                               */
+    int grid[3];               /* grid_size_ = ceil(map_size / resolution) (:789); anything else is FRP_ERR_ARG; at most 65536
+                                  per axis and 2^30 voxels                                                                  */
+    double clamp_min_log, clamp_max_log, min_occupancy_log; /* 0.12, 0.97, 0.80 (:752-754)                                   */
+    double local_radius[3];    /* sensor_range_ = occ_map/local_radius_* (:730-732); a negative radius gives an empty range  */
+    double *log_odds;          /* [gx][gy][gz] occupancy_buffer_, index x * gy * gz + y * gz + z (:104)                      */
+    unsigned char *occ;        /* [gx][gy][gz] != 0 <=> log_odds > min_occupancy_log: what frp_nmpc_astar.occ takes          */
+} frp_nmpc_occmap;
+
+/* Bytes of the map's workspace (the bit plane); 0 for a map description that the calls below refuse. */
+size_t frp_nmpc_occmap_workspace_bytes(const frp_nmpc_occmap *map);
+
+/* Every voxel <- clamp_min_log (OccMap::init, :831). */
+int frp_nmpc_occmap_reset(const frp_nmpc_occmap *map, void *workspace, size_t workspace_bytes, void *stream);
+/* resetBuffer(min_pos, max_pos) (:15-36): the positions (HOST arrays) are clamped to the map, the voxels from posToIndex(min_pos)
+ * to posToIndex(max_pos - resolution / 2), both INCLUSIVE, <- clamp_min_log.  A NaN is FRP_ERR_ARG. */
+int frp_nmpc_occmap_clear_box(const frp_nmpc_occmap *map, const double min_pos[3], const double max_pos[3], void *workspace,
+                              size_t workspace_bytes, void *stream);
+/* globalCloudCallback's loop (:612-619): setOccupancy (:84-93) for P points [P][3] of FLOAT (pcl::PointXYZ), each promoted to
+ * double: voxel floor((p - origin) * (1 / resolution)) <- clamp_max_log; points outside the map (isInMap, :66-69), NaNs included,
+ * are dropped.  log_odds, occ and the bit plane are updated together. */
+int frp_nmpc_occmap_insert_cloud(const frp_nmpc_occmap *map, const float *points, int P, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+/* occ and the bit plane <- log_odds, for a caller that wrote log_odds itself. */
+int frp_nmpc_occmap_refresh(const frp_nmpc_occmap *map, void *workspace, size_t workspace_bytes, void *stream);
+
+typedef struct frp_nmpc_occmap_view {
+    int B;                /* planners                                                                                       */
+    const double *centre; /* [B][3] camera / odometry position: local_range_min_ / max_ = centre -/+ local_radius (:273-274,
+                             :580-581).  NULL with B = 1: the whole map (globalOccVisCallback, :150-175) -- a cloud that can be
+                             shared by all planners and binned by frp_nmpc_cloud_grid_build, but that holds points the
+                             reference's local cut would have hidden from a planner                                          */
+    int P;                /* points stored per planner, <= FRP_CORRIDOR_MAX_POINTS                                           */
+    int *local_box;       /* [B][6] out or NULL: min_id(3), max_id(3) as isInLocalMap clamps them -- max(0, .), min(grid_size, .)
+                             (:47-55) -- and tests them INCLUSIVELY (:56): the array frp_nmpc_astar.local_box takes          */
+    double *cloud;        /* [B][P][3] out, and                                                                              */
+    int *cloud_count;     /* [B] out (both, or both NULL): localOccVisCallback's cloud (:177-215) = the vec_obs_ of
+                             NMPCSolver::cloudCallback (nmpc_solver.cpp:990-995): for x, y, z from min_id to max_id EXCLUSIVE
+                             (:192-194, unlike the test above), in that order, the centre origin + (id + 0.5) * resolution
+                             (:77-82) of every occupied voxel, rounded to float and widened.  The arrays frp_nmpc_corridor
+                             takes with cloud_per_planner != 0.  A planner with more than P occupied voxels keeps the first P
+                             in loop order and gets MINUS its true count (as poly_count and the A* stats flag a loss): the
+                             corridor reads a count below 1 as an empty cloud, so check the sign before relying on it.
+                             Storage beyond the count is not written                                                        */
+} frp_nmpc_occmap_view;
+
+int frp_nmpc_occmap_local_view(const frp_nmpc_occmap *map, const frp_nmpc_occmap_view *view, void *workspace, size_t workspace_bytes,
+                               void *stream);
+
+/* getVoxelState(pos) (:95-106) for Q positions [Q][3]: state[q] = -1 outside the map, 0 outside the local map or free, 1 occupied.
+ * local_box [.][6] (of a local view) or NULL: the whole map is local; planner [Q] = row of local_box for each query, or NULL: row 0. */
+int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, const int *planner, const int *local_box, int *state,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 

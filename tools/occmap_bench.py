@@ -1,0 +1,124 @@
+"""Timings of the occupancy map on the device (include/frp_nmpc.h (8), solver.OccupancyMap) -> profiles/occmap_bench.json:
+  * insert of a cloud, ms per call;
+  * the local view at B = 1 / 1024 / 4096, on the pillar world (20 x 20 x 4 m) and on a map of the reference's size
+    (40 x 40 x 5 m at 0.1 m, local radius 6 / 6 / 3 m), with the bytes it must touch (bit-plane words in range + points written)
+    and the bytes/s that implies;
+  * the corridor step fed from per-planner clouds of the local view against the shared whole-map cloud + uniform grid
+    (the route of tools/full_tick_bench.py), same planners, same session.
+Reported, not gated.   python tools/occmap_bench.py [reps=20]"""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from forces_resilient_planner_amd import solver, workloads  # noqa: E402
+
+REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+DEV = "cuda:0"
+
+
+def timed(fn, reps=REPS):
+    fn(); torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def pillar_cloud(rng, n_pillars, lo, hi, top):
+    """Points on a 0.05 m lattice inside random vertical boxes: every voxel of a box is hit."""
+    out = []
+    for _ in range(n_pillars):
+        cx, cy = rng.uniform(lo[0], hi[0]), rng.uniform(lo[1], hi[1])
+        hx, hy = rng.uniform(0.15, 0.6, 2)
+        g = np.mgrid[cx - hx:cx + hx:0.05, cy - hy:cy + hy:0.05, 0.0:top:0.05].reshape(3, -1).T
+        out.append(g)
+    return np.concatenate(out).astype(np.float32)
+
+
+def view_bench(dm, centres, P):
+    B = len(centres)
+    c = torch.from_numpy(np.ascontiguousarray(centres)).to(DEV)
+    view = dm.local_view(c, P)
+    torch.cuda.synchronize()
+    n = view.cloud_count.cpu().numpy()
+    box = view.local_box.cpu().numpy().astype(np.int64)
+    ext = np.maximum(box[:, 3:] - box[:, :3], 0)
+    wz_in_range = np.where(ext[:, 2] > 0, (box[:, 5] - 1) // 32 - box[:, 2] // 32 + 1, 0)
+    plane_bytes = int((ext[:, 0] * ext[:, 1] * wz_in_range * 4).sum())
+    point_bytes = int(np.minimum(np.abs(n), P).sum()) * 24
+    ms = timed(lambda: dm.local_view(c, P, out=view))
+    return dict(B=B, P=P, ms=ms, overflowed=int((n < 0).sum()), points_mean=float(np.abs(n).mean()), points_max=int(np.abs(n).max()),
+                plane_bytes=plane_bytes, point_bytes=point_bytes, GBps=(plane_bytes + point_bytes) / ms / 1e6), view
+
+
+def main():
+    rng = np.random.default_rng(0)
+    res = {"device": torch.cuda.get_device_name(0), "reps": REPS, "local_view": {}, "insert": {}}
+    worlds = {}
+    w = workloads.astar_world(2, "pillars", n_obstacles=12)
+    worlds["pillars_20x20x4"] = (solver.OccupancyMap(w), None)
+    ref_map = solver.OccupancyMap(origin=(-20.0, -20.0, 0.0), map_size=(40.0, 40.0, 5.0), resolution=0.1)
+    cloud = pillar_cloud(rng, 25, (-18, -18), (18, 18), 3.0)
+    d_cloud = torch.from_numpy(cloud).to(DEV)
+    res["insert"] = dict(points=len(cloud), ms=timed(lambda: ref_map.insert_cloud(d_cloud)), map="40x40x5")
+    res["reset_ms"] = timed(lambda: (ref_map.reset(), ref_map.insert_cloud(d_cloud))) - res["insert"]["ms"]
+    res["refresh_ms"] = timed(ref_map.refresh)
+    worlds["reference_40x40x5"] = (ref_map, None)
+    for name, (dm, _) in worlds.items():
+        lo = np.array(dm.origin) + 1.0; hi = np.array(dm.origin) + np.array(dm.map_size) - 1.0
+        occupied = int(dm.occ.sum())
+        res["local_view"][name] = {"grid": dm.grid, "occupied_voxels": occupied, "runs": []}
+        for B in (1, 1024, 4096):
+            c = rng.uniform(lo, hi, (B, 3)); c[:, 2] = rng.uniform(0.5, 2.0, B)
+            probe = dm.local_view(c, 0); torch.cuda.synchronize()
+            P = int(min(solver.CORRIDOR_MAX_POINTS, max(1, -int(probe.cloud_count.min()))))
+            r, _ = view_bench(dm, c, P)
+            res["local_view"][name]["runs"].append(r)
+            print(name, r, flush=True)
+    # corridor: per-planner clouds (local cut, as the reference) vs the shared whole-map cloud + grid
+    B, N, F = 4096, 20, 64
+    dm = worlds["reference_40x40x5"][0]
+    s = np.linspace(0, 5, N)
+    path = np.c_[s, 0.4 * np.sin(0.8 * s), 1.0 + 0.1 * np.cos(s)]
+    start = np.c_[rng.uniform(-15, 10, B), rng.uniform(-15, 15, B), np.zeros(B)]
+    ref = path[None] + start[:, None, :] + rng.normal(0, 0.03, (B, N, 3))
+    yaw = np.arctan2(np.gradient(path[:, 1]), np.gradient(path[:, 0]))[None] + rng.normal(0, 0.05, (B, N))
+    z = np.zeros((B, N, 17)); z[..., 3] = 7.3; z[..., 8:11] = ref; z[..., 16] = yaw
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(DEV)
+    mo = torch.zeros((B, N + 1, 17), dtype=torch.float64, device=DEV); mo[:, :N] = up(z)
+    E = torch.empty((B, N, 3, 3), dtype=torch.float64, device=DEV)
+    solver.tube_batch_device(mo, E)
+    d_ref, d_yaw = up(ref), up(yaw)
+    out = (torch.zeros((B, N, F, 3), dtype=torch.float64, device=DEV), torch.zeros((B, N, F), dtype=torch.float64, device=DEV),
+           torch.zeros((B, N), dtype=torch.int32, device=DEV), torch.zeros((B, N), dtype=torch.int32, device=DEV), torch.zeros((B,), dtype=torch.int32, device=DEV))
+    probe = dm.local_view(ref[:, 0], 0); torch.cuda.synchronize()
+    P = int(min(solver.CORRIDOR_MAX_POINTS, max(1, -int(probe.cloud_count.min()))))
+    rv, view = view_bench(dm, ref[:, 0], P)
+    ms_local = timed(lambda: solver.corridor_batch_device(view.cloud, d_ref, d_yaw, E, *out, cloud_count=view.cloud_count), max(3, REPS // 4))
+    whole = dm.local_view(None, solver.CORRIDOR_MAX_POINTS); torch.cuda.synchronize()
+    nw = int(whole.cloud_count[0])
+    cor = {"B": B, "per_planner": {"P": P, "local_view_ms": rv["ms"], "corridor_ms": ms_local}}
+    if nw > 0:
+        shared = whole.cloud[0, :nw].contiguous()
+        grid = solver.CloudGrid(shared, 0.5, dm.origin, tuple(int(np.ceil(m / 0.5)) for m in dm.map_size))
+        ms_grid = timed(lambda: solver.corridor_batch_device(shared, d_ref, d_yaw, E, *out, grid=grid))
+        cor["shared_cloud_grid"] = {"points": nw, "corridor_ms": ms_grid}
+        cor["per_planner_over_shared"] = ms_local / ms_grid
+    else:
+        cor["shared_cloud_grid"] = {"skipped": f"the whole map holds {-nw} occupied voxels, more than FRP_CORRIDOR_MAX_POINTS"}
+    res["corridor"] = cor
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "occmap_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res["corridor"]))
+
+
+if __name__ == "__main__":
+    main()
