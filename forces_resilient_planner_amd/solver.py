@@ -69,6 +69,10 @@ class Corridor(ctypes.Structure):  # frp_nmpc_corridor (include/frp_nmpc.h)
                 ("grid_points", ctypes.c_void_p), ("grid_index", ctypes.c_void_p), ("grid_start", ctypes.c_void_p)]
 
 
+class CorridorCut(ctypes.Structure):  # frp_nmpc_corridor_cut (include/frp_nmpc.h); the tensor behind .box is kept alive on ._box
+    _fields_ = [("box", ctypes.c_void_p), ("origin", ctypes.c_double * 3), ("resolution", ctypes.c_double)]
+
+
 class Reference(ctypes.Structure):  # frp_nmpc_reference (include/frp_nmpc.h)
     _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("kino_path", ctypes.c_void_p),
                 ("path_per_planner", ctypes.c_int), ("kino_size", ctypes.c_void_p), ("time_offset", ctypes.c_void_p),
@@ -141,7 +145,7 @@ EXPORTS = ["frp_nmpc_default_options", "frp_nmpc_workspace_bytes", "frp_nmpc_sol
            "frp_nmpc_solve_batch_host", "frp_nmpc_stage_eval", "frp_nmpc_stage_eval_host", "frp_nmpc_time_solve",
            "frp_nmpc_version", "frp_nmpc_device_count", "FORCESNLPsolver_normal_solve",
            "FORCESNLPsolver_final_solve", "frp_nmpc_pack_batch", "frp_nmpc_update_batch", "frp_nmpc_tube_batch",
-           "frp_nmpc_corridor_batch", "frp_nmpc_reference_batch",
+           "frp_nmpc_corridor_batch", "frp_nmpc_corridor_batch_cut", "frp_nmpc_reference_batch",
            "frp_nmpc_coldstart_batch", "frp_nmpc_cloud_grid_build",
            "frp_nmpc_mode_batch", "frp_nmpc_astar_batch", "frp_nmpc_astar_workspace_bytes",
            "frp_nmpc_kernel_timing_begin", "frp_nmpc_kernel_timing_end", "frp_nmpc_set_q4_min_batch",
@@ -200,6 +204,8 @@ def lib():
         l.frp_nmpc_tube_batch.argtypes = [ctypes.POINTER(Tube), ctypes.c_void_p]
         l.frp_nmpc_corridor_batch.argtypes = [ctypes.POINTER(Corridor), ctypes.c_void_p]
         l.frp_nmpc_reference_batch.argtypes = [ctypes.POINTER(Reference), ctypes.c_void_p]
+        if hasattr(l, "frp_nmpc_corridor_batch_cut"):  # (a library without it is refused by the EXPORTS check below)
+            l.frp_nmpc_corridor_batch_cut.argtypes = [ctypes.POINTER(Corridor), ctypes.POINTER(CorridorCut), ctypes.c_void_p]
         l.frp_nmpc_cloud_grid_build.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         l.frp_nmpc_mode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -588,7 +594,9 @@ class OccupancyMap:
         """local_box + localOccVisCallback's cloud (occ_map.cpp:177-215) of every planner: centres [B,3] f64 (device tensor or
         array), P points stored per planner.  centres = None: the whole map as one cloud (globalOccVisCallback, :150-175), B = 1.
         out: a LocalView of the same shapes to write into (a captured graph replays into the same buffers).  Nothing is
-        synchronised: cloud_count (negative = overflow, LocalView.overflowed()) is a device tensor."""
+        synchronised: cloud_count (negative = overflow, LocalView.overflowed()) is a device tensor.
+        P = 0 stores no cloud: local_box alone (cloud_count = minus each planner's count).  That is the per-tick call of the
+        shared-cloud route -- shared_view() once per map change, then per tick local_view(centres, 0) and cut(view.local_box)."""
         t = self.torch
         c = None if centres is None else self._dev(centres, t.float64)
         B = 1 if c is None else int(c.shape[0])
@@ -603,6 +611,36 @@ class OccupancyMap:
         if stream is not None and c is not None and c is not centres:
             c.record_stream(stream)
         return out
+
+    def cut(self, local_box):
+        """The visibility cut of frp_nmpc_corridor_batch_cut for local_box [B,6] int32 (device tensor, LocalView.local_box): what
+        corridor_batch_device / DeviceFleet.corridor / full_tick take as `cut` beside the shared cloud of shared_view().  Planner b
+        then sees the points with origin + min_id * resolution <= q < origin + max_id * resolution per axis -- its local cloud."""
+        t = self.torch
+        assert t.is_tensor(local_box) and local_box.dtype == t.int32 and local_box.dim() == 2 and local_box.shape[1] == 6 and local_box.is_contiguous()
+        assert local_box.device == self.log_odds.device
+        c = CorridorCut(local_box.data_ptr(), (ctypes.c_double * 3)(*self.origin), self.resolution)
+        c._box = local_box
+        return c
+
+    def shared_view(self, cell=0.5, stream=None):
+        """The whole-map cloud (local_view(None, .), every occupied voxel's centre in x, y, z order) trimmed to its count, and a
+        CloudGrid over it: (cloud [n,3] f64, grid).  The grid is laid over the map itself -- origin = the map's, dims =
+        ceil(map_size / cell) -- so nothing is read back to find its bounds.  ONE synchronisation, to read the count: call it
+        when the map changes (insert_cloud / clear_box / refresh), not per tick.  A shared cloud holds at most
+        FRP_CORRIDOR_MAX_POINTS points; a map with more occupied voxels raises ValueError (use per-planner clouds)."""
+        t = self.torch
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        v = self.local_view(None, CORRIDOR_MAX_POINTS, stream=stream)
+        with t.cuda.stream(s):
+            n = int(v.cloud_count[0].item())   # the one synchronisation
+        if n < 0:
+            raise ValueError(f"the map holds {-n} occupied voxels, a shared cloud at most FRP_CORRIDOR_MAX_POINTS = {CORRIDOR_MAX_POINTS}: "
+                             "use per-planner clouds (local_view(centres, P))")
+        with t.cuda.stream(s):
+            cloud = v.cloud[0, :n].clone()
+        dims = tuple(max(1, int(np.ceil(m / float(cell)))) for m in self.map_size)
+        return cloud, CloudGrid(cloud, cell, origin=self.origin, dims=dims, stream=stream)
 
     def query(self, pos, local_box=None, planner=None, stream=None):
         """getVoxelState (occ_map.cpp:95-106) of pos [Q,3]: int32 [Q] device tensor, -1 outside the map, 0 free or outside the local
@@ -728,9 +766,11 @@ class CloudGrid:
 
 
 def corridor_batch_device(cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b, poly_nfaces, poly_index, poly_count=None,
-                          cloud_count=None, consts=None, stream=None, grid=None):
+                          cloud_count=None, consts=None, stream=None, grid=None, cut=None):
     """frp_nmpc_corridor_batch on device tensors.  cloud [P,3] (shared) or [B,P,3]; ref_pos [B,N,3]; ref_yaw [B,N];
-    ellipsoid [B,N,3,3]; outputs poly_A [B,N,F,3], poly_b [B,N,F], poly_nfaces / poly_index [B,N] int32."""
+    ellipsoid [B,N,3,3]; outputs poly_A [B,N,F,3], poly_b [B,N,F], poly_nfaces / poly_index [B,N] int32.
+    cut (OccupancyMap.cut, a CorridorCut): frp_nmpc_corridor_batch_cut -- every planner sees only the points of the SHARED cloud
+    inside its own local box."""
     import torch
     c = dict(CORRIDOR_DEFAULTS)
     c.update(consts or {})
@@ -750,6 +790,11 @@ def corridor_batch_device(cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b, po
         assert per == 0, "the grid belongs to a shared cloud"
         cr.grid_origin = (ctypes.c_double * 3)(*grid.origin); cr.grid_cell = grid.cell; cr.grid_dims = (ctypes.c_int * 3)(*grid.dims)
         cr.grid_points = grid.points.data_ptr(); cr.grid_index = grid.index.data_ptr(); cr.grid_start = grid.start.data_ptr()
+    if cut is not None:
+        assert per == 0, "the cut belongs to a shared cloud"
+        assert getattr(cut, "_box", None) is None or cut._box.shape[0] == B, "one local_box row per planner"
+        _check(lib().frp_nmpc_corridor_batch_cut(ctypes.byref(cr), ctypes.byref(cut), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_corridor_batch_cut")
+        return
     _check(lib().frp_nmpc_corridor_batch(ctypes.byref(cr), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_corridor_batch")
 
 
@@ -868,15 +913,16 @@ class DeviceFleet:
         s = stream if stream is not None else self.torch.cuda.current_stream(self.solver.device)
         tube_batch_device(self.mpc_output, self.ellipsoid, consts, s)
 
-    def corridor(self, cloud, ref_pos, ref_yaw, consts=None, stream=None, cloud_count=None, grid=None):
+    def corridor(self, cloud, ref_pos, ref_yaw, consts=None, stream=None, cloud_count=None, grid=None, cut=None):
         """polytopes and poly_indices of all B planners from the obstacle cloud, the stage
-        references and the current tube (getSikangConst, nmpc_solver.cpp:288-332) -> self.poly_*, on the device."""
+        references and the current tube (getSikangConst, nmpc_solver.cpp:288-332) -> self.poly_*, on the device.
+        cut: OccupancyMap.cut(local_box) with the shared cloud and grid of OccupancyMap.shared_view()."""
         t = self.torch
         assert self.NPOLY == self.N
         if self.poly_index is None:
             self.poly_index = t.zeros((self.B, self.N), dtype=t.int32, device=self.solver.device)
         corridor_batch_device(cloud, ref_pos, ref_yaw, self.ellipsoid, self.poly_A, self.poly_b, self.poly_nfaces,
-                              self.poly_index, self.poly_count, cloud_count, consts, stream, grid)
+                              self.poly_index, self.poly_count, cloud_count, consts, stream, grid, cut)
 
     def overflowed(self):
         """Planners whose last corridor() truncated a polytope to F rows (device tensor of bool; all False before the first
@@ -953,18 +999,19 @@ class DeviceFleet:
         return ok
 
     def full_tick(self, external_acc, kino_path, time_offset, cloud, ref_pos, ref_yaw, stream=None, replan=None,
-                  kino_size=None, tube_consts=None, corridor_consts=None, Ts=0.05, coldstart=True, state=None, grid=None, cloud_count=None):
+                  kino_size=None, tube_consts=None, corridor_consts=None, Ts=0.05, coldstart=True, state=None, grid=None, cloud_count=None, cut=None):
         """The reference's whole per-tick computation downstream of the A* (NMPCSolver::solveNMPC,
         nmpc_solver.cpp:351-482) for B planners, asynchronous on `stream`, nothing touching the host:
         stage references (f-4) -> tube (f-2) -> corridor (f-3) -> parameter packing (f-1) -> NLP solve -> result
         bookkeeping.  ref_pos [B,N,3] / ref_yaw [B,N] are caller-owned scratch that receives the references.
         With coldstart (default) planners whose previous solve failed first restart from the constant plan (:363-364).
-        cloud [B,P,3] with cloud_count [B]: per-planner clouds, as OccupancyMap.local_view exports them."""
+        cloud [B,P,3] with cloud_count [B]: per-planner clouds, as OccupancyMap.local_view exports them; or the shared cloud and grid
+        of OccupancyMap.shared_view() with cut = OccupancyMap.cut(local_box): the same polytopes without the per-planner copies."""
         if coldstart:
             self.coldstart(state, True, stream=stream)
         self.references(kino_path, time_offset, ref_pos, ref_yaw, replan, kino_size, Ts, stream)
         self.tube(tube_consts, stream)
-        self.corridor(cloud, ref_pos, ref_yaw, corridor_consts, stream, cloud_count=cloud_count, grid=grid)
+        self.corridor(cloud, ref_pos, ref_yaw, corridor_consts, stream, cloud_count=cloud_count, grid=grid, cut=cut)
         self.pack(external_acc, ref_pos, ref_yaw, stream)
         self.solver.solve(stream)
         self.update(stream)

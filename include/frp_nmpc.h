@@ -358,6 +358,37 @@ int frp_nmpc_cloud_grid_build(const double *cloud, int P, const double origin[3]
  * EllipsoidDecomp3D::dilate is run on the seed segment (decomp_util/line_segment.h:31-35).  Asynchronous on `stream`. */
 int frp_nmpc_corridor_batch(const frp_nmpc_corridor *p, void *stream);
 
+/* A per-planner visibility cut on a SHARED cloud: every planner scans the same cloud (and its uniform grid), but sees only the points
+ * inside its own axis-aligned box.  With the whole-map cloud of frp_nmpc_occmap_local_view(centre = NULL) and the local_box rows of the
+ * per-planner view, planner b sees exactly the cloud localOccVisCallback would have given it (occ_map.cpp:177-215), without a
+ * [B][P][3] copy: the polytopes are bit-identical to those of the per-planner clouds (both views emit in x, y, z loop order, so the
+ * visible points are an order-preserving subsequence and first-minimum ties fall the same way).
+ *   Planner b sees cloud point q  iff  lo[k] <= q[k] && q[k] < hi[k] for k = 0, 1, 2, with
+ *       lo[k] = origin[k] + box[b][k] * resolution,   hi[k] = origin[k] + box[b][3 + k] * resolution
+ *   (one multiply and one add each, not fused).  Lower bound inclusive, upper bound EXCLUSIVE, as the loops of localOccVisCallback
+ *   (:192-194) -- the A* tests the same array inclusively (frp_nmpc_occmap_view.local_box); that difference is the reference's.
+ *   A point with a NaN coordinate is invisible.  A row with min > max on some axis sees nothing: its result is that of an empty
+ *   cloud (the six rows of the local box per polytope).
+ * For a cloud of voxel centres (the whole-map view) the position test equals the index test min_id <= id < max_id: a centre sits
+ * half a voxel from every bound, and its float32 rounding moves it by at most |centre| * 2^-24, so the two agree as long as
+ *       (max_k |origin[k]| + max_k map_size[k]) * 2^-23 < resolution / 2
+ * (0.1 m voxels: maps up to 400 km from the origin).  Any other double cloud is cut by position, as stated.
+ * A shared cloud holds at most FRP_CORRIDOR_MAX_POINTS points (the LDS masks of the plain-cloud kernel); a map with more occupied
+ * voxels keeps using per-planner clouds. */
+typedef struct frp_nmpc_corridor_cut {
+    const int *box;     /* [B][6] device: min_id(3), max_id(3) -- frp_nmpc_occmap_view.local_box */
+    double origin[3];   /* frp_nmpc_occmap.origin */
+    double resolution;  /* frp_nmpc_occmap.resolution */
+} frp_nmpc_corridor_cut;
+
+/* frp_nmpc_corridor_batch with the cut applied in every first scan (one-wavefront kernel, grid kernel, plain-cloud kernel: the
+ * hand-over chain carries it through all three launches).  cut == NULL: exactly frp_nmpc_corridor_batch(p, stream).  Otherwise
+ * FRP_ERR_ARG before anything is launched for box == NULL, a resolution that is not finite and positive, a non-finite origin, or
+ * p->cloud_per_planner != 0 (the cut belongs to a shared cloud).  cloud_count ([1], e.g. the whole-map view's device-side count)
+ * stays allowed: as without a cut it turns the grid off and the plain kernel honours it.  Asynchronous on `stream`, allocates
+ * nothing, can be captured into a hipGraph (the structs are read during the call, the device arrays when the kernels run). */
+int frp_nmpc_corridor_batch_cut(const frp_nmpc_corridor *p, const frp_nmpc_corridor_cut *cut, void *stream);
+
 /* ---- (6) SURVEY 8f row f-4 (first half): stage references from the kinodynamic path, on the device ---- */
 typedef struct frp_nmpc_reference {
     int B, N, K;               /* planners, horizon, samples stored per path                                        */

@@ -4,7 +4,8 @@
     (40 x 40 x 5 m at 0.1 m, local radius 6 / 6 / 3 m), with the bytes it must touch (bit-plane words in range + points written)
     and the bytes/s that implies;
   * the corridor step fed from per-planner clouds of the local view against the shared whole-map cloud + uniform grid
-    (the route of tools/full_tick_bench.py), same planners, same session.
+    (the route of tools/full_tick_bench.py) and against the same shared cloud + grid CUT to each planner's local box
+    (frp_nmpc_corridor_batch_cut: box-only view + corridor), same planners, same session, with the bytes each route allocates.
 Reported, not gated.   python tools/occmap_bench.py [reps=20]"""
 import json
 import os
@@ -104,13 +105,32 @@ def main():
     ms_local = timed(lambda: solver.corridor_batch_device(view.cloud, d_ref, d_yaw, E, *out, cloud_count=view.cloud_count), max(3, REPS // 4))
     whole = dm.local_view(None, solver.CORRIDOR_MAX_POINTS); torch.cuda.synchronize()
     nw = int(whole.cloud_count[0])
-    cor = {"B": B, "per_planner": {"P": P, "local_view_ms": rv["ms"], "corridor_ms": ms_local}}
+    cor = {"B": B, "per_planner": {"P": P, "local_view_ms": rv["ms"], "corridor_ms": ms_local,
+                                   "bytes": view.cloud.numel() * 8 + view.cloud_count.numel() * 4 + view.local_box.numel() * 4}}
     if nw > 0:
         shared = whole.cloud[0, :nw].contiguous()
         grid = solver.CloudGrid(shared, 0.5, dm.origin, tuple(int(np.ceil(m / 0.5)) for m in dm.map_size))
         ms_grid = timed(lambda: solver.corridor_batch_device(shared, d_ref, d_yaw, E, *out, grid=grid))
-        cor["shared_cloud_grid"] = {"points": nw, "corridor_ms": ms_grid}
+        grid_bytes = shared.numel() * 8 + grid.points.numel() * 8 + grid.index.numel() * 4 + grid.start.numel() * 4
+        cor["shared_cloud_grid"] = {"points": nw, "corridor_ms": ms_grid, "bytes": grid_bytes,
+                                    "note": "no local cut: planners see points the reference hides, other polytopes"}
         cor["per_planner_over_shared"] = ms_local / ms_grid
+        # the cut route: per tick the box-only view, then the corridor on the shared cloud + grid cut to each planner's box (same
+        # polytopes as per_planner, to the bit); the three corridor timings alternate once more so that none owns a warmer device
+        c0 = up(ref[:, 0])
+        boxes = dm.local_view(c0, 0)
+        ms_boxes = timed(lambda: dm.local_view(c0, 0, out=boxes))
+        cut = dm.cut(boxes.local_box)
+        run_cut = lambda: solver.corridor_batch_device(shared, d_ref, d_yaw, E, *out, grid=grid, cut=cut)
+        ms_cut = timed(run_cut)
+        again = {"per_planner": timed(lambda: solver.corridor_batch_device(view.cloud, d_ref, d_yaw, E, *out, cloud_count=view.cloud_count), max(3, REPS // 4)),
+                 "shared_cloud_grid": timed(lambda: solver.corridor_batch_device(shared, d_ref, d_yaw, E, *out, grid=grid)),
+                 "shared_cut": timed(run_cut)}
+        cor["shared_cut"] = {"points": nw, "local_view_ms": ms_boxes, "corridor_ms": ms_cut, "bytes": grid_bytes + boxes.local_box.numel() * 4 + boxes.cloud_count.numel() * 4}
+        cor["second_pass_corridor_ms"] = again
+        tick = {"per_planner": rv["ms"] + ms_local, "shared_cut": ms_boxes + ms_cut}
+        cor["view_plus_corridor_ms"] = tick
+        cor["reference_equivalent_winner"] = min(tick, key=tick.get)
     else:
         cor["shared_cloud_grid"] = {"skipped": f"the whole map holds {-nw} occupied voxels, more than FRP_CORRIDOR_MAX_POINTS"}
     res["corridor"] = cor
