@@ -15,33 +15,12 @@
 //     (pcl::PointXYZ).
 //   * where the reference converts a double to int without looking (NaN, beyond int: undefined there), the tests are made on the
 //     floored double: such a point is outside the map, such a local range is clamped like any other.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-
-#include "frp_nmpc.h"
+#include "frp_occmap.hpp"
 
 namespace frp {
 namespace occmap {
 
 constexpr int LV_THREADS = 256;
-constexpr double ID_LIM = 1073741824.0; // 2^30: floored indices are clamped here before they become int
-
-struct Geo {
-    double origin[3], res, res_inv;
-    int grid[3], wz;
-    double thr;
-};
-
-__host__ __device__ inline double floored(double p, double origin, double res_inv) { return floor((p - origin) * res_inv); } // posToIndex, :71-75
-
-__host__ __device__ inline int clamp_id(double f)
-{
-    if (!(f >= -ID_LIM)) f = -ID_LIM; // NaN as well
-    if (f > ID_LIM) f = ID_LIM;
-    return (int)f;
-}
 
 // fill: log_odds and occ of every voxel (OccMap::init, :831)
 __global__ __launch_bounds__(256) void fill_kernel(double *log_odds, unsigned char *occ, size_t n, double v, unsigned char o)
@@ -210,44 +189,6 @@ __global__ __launch_bounds__(256) void query_kernel(Geo g, int Q, const double *
             if (id[k] < bx[k] || id[k] > bx[3 + k]) { state[q] = 0; return; }
     }
     state[q] = occ[((size_t)id[0] * g.grid[1] + id[1]) * g.grid[2] + id[2]] ? 1 : 0;
-}
-
-static size_t plane_bytes(const frp_nmpc_occmap *m) { return (size_t)m->grid[0] * m->grid[1] * ((m->grid[2] + 31) / 32) * sizeof(uint32_t); }
-
-static bool valid(const frp_nmpc_occmap *m)
-{
-    if (!m || !m->log_odds || !m->occ || !(m->resolution > 0.0) || !std::isfinite(m->resolution)) return false;
-    for (int k = 0; k < 3; k++) {
-        if (!(m->map_size[k] > 0.0) || !std::isfinite(m->map_size[k]) || !std::isfinite(m->origin[k])) return false;
-        const double n = std::ceil(m->map_size[k] / m->resolution); // grid_size_, :789
-        if (!(n >= 1.0 && n <= 65536.0) || m->grid[k] != (int)n) return false;
-    }
-    if ((size_t)m->grid[0] * m->grid[1] * m->grid[2] >= ((size_t)1 << 30)) return false; // voxel and column counts are int
-    return std::isfinite(m->clamp_min_log) && std::isfinite(m->clamp_max_log) && std::isfinite(m->min_occupancy_log);
-}
-
-static bool args_ok(const frp_nmpc_occmap *m, const void *ws, size_t ws_bytes) { return valid(m) && ws && ws_bytes >= plane_bytes(m); }
-
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static Geo geo(const frp_nmpc_occmap *m)
-{
-    Geo g;
-    for (int k = 0; k < 3; k++) { g.origin[k] = m->origin[k]; g.grid[k] = m->grid[k]; }
-    g.res = m->resolution; g.res_inv = 1 / m->resolution; // resolution_inv_, :787
-    g.wz = (m->grid[2] + 31) / 32;
-    g.thr = m->min_occupancy_log;
-    return g;
-}
-
-static unsigned blocks_for(size_t n, unsigned cap = 8192)
-{
-    const size_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
 }
 
 static int repack(const frp_nmpc_occmap *m, void *ws, hipStream_t st)

@@ -105,6 +105,16 @@ class OccMapView(ctypes.Structure):  # frp_nmpc_occmap_view (include/frp_nmpc.h)
                 ("cloud", ctypes.c_void_p), ("cloud_count", ctypes.c_void_p)]
 
 
+class OccMapFuse(ctypes.Structure):  # frp_nmpc_occmap_fuse (include/frp_nmpc_occmap_fuse.h)
+    _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("depth", ctypes.c_void_p), ("last_depth", ctypes.c_void_p),
+                ("last_T_wc", ctypes.c_double * 16), ("K", ctypes.c_double * 9), ("T_wc", ctypes.c_double * 16),
+                ("depth_scale", ctypes.c_double), ("depth_filter_mindist", ctypes.c_double), ("depth_filter_tolerance", ctypes.c_double),
+                ("depth_filter_margin", ctypes.c_int), ("skip_pixel", ctypes.c_int),
+                ("prob_hit_log", ctypes.c_double), ("prob_miss_log", ctypes.c_double),
+                ("min_ray_length", ctypes.c_double), ("max_ray_length", ctypes.c_double),
+                ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
+
+
 ASTAR_MAX_PATH = 256
 ASTAR_REACH_HORIZON, ASTAR_REACH_END, ASTAR_NO_PATH, ASTAR_REACH_END_BUT_SHOT_FAILS = 1, 2, 3, 4
 
@@ -117,6 +127,14 @@ CORRIDOR_MAX_POINTS = 65536
 
 # OccMap's ROS parameter defaults (occ_map.cpp:752-754) and the local range of the reference's launch files
 OCCMAP_DEFAULTS = dict(clamp_min_log=0.12, clamp_max_log=0.97, min_occupancy_log=0.80, local_radius=(6.0, 6.0, 3.0))
+
+# depth fusion: the occ_map/* values of the reference's launch file (plan_manage/launch/advanced_param.xml:69-92); max_rounds 0 = the
+# library's default number of relaxation rounds (FRP_OCCMAP_FUSE_DEFAULT_ROUNDS)
+OCCMAP_FUSE_DEFAULTS = dict(depth_scale=1000.0, depth_filter_mindist=0.1, depth_filter_tolerance=0.2, depth_filter_margin=1, skip_pixel=2,
+                            prob_hit_log=1.2, prob_miss_log=-0.5, min_ray_length=0.1, max_ray_length=6.0, max_rounds=0)
+OCCMAP_FUSE_DEFAULT_ROUNDS = 128  # FRP_OCCMAP_FUSE_DEFAULT_ROUNDS
+# section (8)'s second header (include/frp_nmpc_occmap_fuse.h): checked at load time like EXPORTS
+FUSE_EXPORTS = ["frp_nmpc_occmap_fuse_workspace_bytes", "frp_nmpc_occmap_fuse_depth"]
 
 # ROS parameter defaults of the tube model (nmpc_solver.cpp:68-74, nmpc_utils.h:188-189)
 TUBE_DEFAULTS = dict(mass=0.74, drag=0.33, ego_r=0.27, ego_h=0.0425, noise=(0.5, 0.5, 0.5), epsilon=0.06, Ts=0.05)
@@ -215,7 +233,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -227,6 +245,9 @@ def lib():
         l.frp_nmpc_occmap_insert_cloud.argtypes = [pm, vp, ctypes.c_int, vp, sz, vp]
         l.frp_nmpc_occmap_local_view.argtypes = [pm, ctypes.POINTER(OccMapView), vp, sz, vp]
         l.frp_nmpc_occmap_query.argtypes = [pm, ctypes.c_int, vp, vp, vp, vp, vp, sz, vp]
+        l.frp_nmpc_occmap_fuse_workspace_bytes.restype = ctypes.c_size_t
+        l.frp_nmpc_occmap_fuse_workspace_bytes.argtypes = [pm, ctypes.POINTER(OccMapFuse)]
+        l.frp_nmpc_occmap_fuse_depth.argtypes = [pm, ctypes.POINTER(OccMapFuse), vp, sz, vp, sz, vp]
         _lib = l
     return _lib
 
@@ -503,8 +524,9 @@ class OccupancyMap:
     """The reference's OccMap (occ_grid/src/occ_map.cpp) in HBM, shared by all planners (frp_nmpc_occmap_*): the log-odds buffer,
     the byte grid the A* searches (.occ) and, per planner, the local box and the local obstacle cloud the corridor takes.
     world: the dict of workloads.astar_world -- its geometry, and its occ as the initial content (occupied voxels at
-    clamp_max_log, the others at clamp_min_log); or explicit origin / map_size / resolution for an empty map.  Depth-image fusion is
-    not part of it (include/frp_nmpc.h (8)): a caller with its own fusion writes .log_odds and calls refresh()."""
+    clamp_max_log, the others at clamp_min_log); or explicit origin / map_size / resolution for an empty map.  fuse_depth() fuses a
+    camera frame by ray casting (projectDepthImage / raycastProcess, include/frp_nmpc_occmap_fuse.h) with the reference's serial
+    result to the bit; a caller with another fusion of its own writes .log_odds and calls refresh()."""
 
     def __init__(self, world=None, origin=None, map_size=None, resolution=None, local_radius=None, clamp_min_log=None,
                  clamp_max_log=None, min_occupancy_log=None, device="cuda:0"):
@@ -534,6 +556,9 @@ class OccupancyMap:
         if self.ws_bytes == 0:
             raise ValueError("frp_nmpc_occmap refuses this map description (resolution, map_size, grid)")
         self.ws = torch.empty((self.ws_bytes // 4 + 1,), dtype=torch.int32, device=self.device)
+        self.fuse_ws = None          # the fusion workspace: allocated by fuse_depth, grown when a larger frame needs it
+        self._last_frame = None      # (depth, T_wc) of the previous filtered frame (last_depth_image, last_T_wc: occ_map.cpp:423-424)
+        self._fusing_against = None  # the frame the latest filtered call reads on its stream: kept alive until the next call
         if world is not None and world.get("occ") is not None:
             o = torch.from_numpy(np.ascontiguousarray(world["occ"], dtype=np.uint8)).to(self.device)
             assert tuple(o.shape) == self.grid, (tuple(o.shape), self.grid)
@@ -589,6 +614,75 @@ class OccupancyMap:
         self._call("frp_nmpc_occmap_insert_cloud", ctypes.c_void_p(pts.data_ptr()) if pts.shape[0] else None, int(pts.shape[0]), stream=stream)
         if stream is not None:
             pts.record_stream(stream)
+
+    def fuse_depth(self, depth, K, T_wc, *, shift_filter=False, status=None, stream=None, **params):
+        """One camera frame into the map (OccMap::depthCallback's projectDepthImage + raycastProcess, occ_map.cpp:291-292):
+        depth [rows, cols] uint16 (device tensor or array), K 3 x 3 intrinsics, T_wc 4 x 4 camera-to-world pose (host values).
+        params: the keys of OCCMAP_FUSE_DEFAULTS.  log_odds, occ and the bit plane follow together -- no refresh().
+        Returns the status tensor (int32 [2], device; nothing is synchronised): [0] relaxation rounds used, or minus max_rounds when
+        the frame did not converge and the map was left untouched; [1] rays cast.
+        shift_filter: the depth filter of :364-419 against the previous filtered frame, which the map keeps (with its pose)
+        itself; the first filtered frame fuses nothing (has_first_depth_, :360-361) and returns [0, 0].
+        status: a tensor to write into (a captured graph replays into the same buffer)."""
+        t = self.torch
+        unknown = set(params) - set(OCCMAP_FUSE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"fuse_depth: unknown parameters {sorted(unknown)}")
+        d = dict(OCCMAP_FUSE_DEFAULTS); d.update(params)
+        if not t.is_tensor(depth):
+            a = np.ascontiguousarray(depth)
+            if a.dtype != np.uint16:
+                raise TypeError("depth must be uint16 (the reference's depth_image.at<uint16_t>)")
+            depth = t.from_numpy(a.view(np.int16)).to(self.device).view(t.uint16)
+        if depth.dtype != t.uint16 or depth.dim() != 2 or depth.device != self.log_odds.device:
+            raise TypeError("depth must be a [rows, cols] uint16 tensor on the map's device")
+        depth = depth.contiguous()
+        T = np.ascontiguousarray(T_wc, dtype=np.float64).reshape(4, 4)
+        Kh = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        if status is None:
+            status = t.zeros((2,), dtype=t.int32, device=self.device)
+        assert status.dtype == t.int32 and status.numel() >= 2 and status.is_contiguous() and status.device == self.log_odds.device
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        last = None
+        if shift_filter:
+            # The copy kept for the next frame is made on the stream of the call, behind whatever produced `depth` there (the caller
+            # may reuse its tensor).  The previous frame stays referenced (_fusing_against) until the next call replaces it, so its
+            # memory cannot go back to the allocator while this call's kernels, which read it, are still queued.
+            with t.cuda.stream(s):
+                keep = depth.clone()
+            last, self._last_frame = self._last_frame, (keep, T.copy())
+            self._fusing_against = last
+            if last is None:
+                status.zero_()
+                return status
+            if tuple(last[0].shape) != tuple(depth.shape):
+                raise ValueError("shift_filter: the frame size changed")
+        f = OccMapFuse()
+        f.rows, f.cols = int(depth.shape[0]), int(depth.shape[1])
+        f.depth = depth.data_ptr()
+        f.last_depth = last[0].data_ptr() if last is not None else None
+        if last is not None:
+            f.last_T_wc[:] = [float(v) for v in last[1].ravel()]
+        f.K[:] = [float(v) for v in Kh.ravel()]
+        f.T_wc[:] = [float(v) for v in T.ravel()]
+        for k in ("depth_scale", "depth_filter_mindist", "depth_filter_tolerance", "prob_hit_log", "prob_miss_log", "min_ray_length", "max_ray_length"):
+            setattr(f, k, float(d[k]))
+        f.depth_filter_margin, f.skip_pixel, f.max_rounds = int(d["depth_filter_margin"]), int(d["skip_pixel"]), int(d["max_rounds"])
+        f.status = status.data_ptr()
+        m = self._map()
+        need = int(lib().frp_nmpc_occmap_fuse_workspace_bytes(ctypes.byref(m), ctypes.byref(f)))
+        if need == 0:
+            raise ValueError("frp_nmpc_occmap_fuse_depth refuses this frame description (see include/frp_nmpc_occmap_fuse.h)")
+        if self.fuse_ws is None or self.fuse_ws.numel() < need:
+            self.fuse_ws = t.empty((need,), dtype=t.uint8, device=self.device)
+        _check(lib().frp_nmpc_occmap_fuse_depth(ctypes.byref(m), ctypes.byref(f), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
+                                                ctypes.c_void_p(self.fuse_ws.data_ptr()), int(self.fuse_ws.numel()), ctypes.c_void_p(s.cuda_stream)),
+               "frp_nmpc_occmap_fuse_depth")
+        if stream is not None:
+            depth.record_stream(stream)
+            if last is not None:
+                last[0].record_stream(stream)
+        return status
 
     def local_view(self, centres, P, out=None, stream=None):
         """local_box + localOccVisCallback's cloud (occ_map.cpp:177-215) of every planner: centres [B,3] f64 (device tensor or

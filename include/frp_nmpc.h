@@ -487,9 +487,8 @@ int frp_nmpc_astar_batch(const frp_nmpc_astar *p, void *workspace, size_t worksp
  * frp_nmpc_occmap_workspace_bytes() bytes that holds a bit plane of occ (one bit per voxel, packed along z).  The workspace is
  * PART OF THE MAP: it is written by reset / clear_box / insert_cloud / refresh and read by local_view, and stays with the map for
  * as long as the map lives.  A caller that writes log_odds itself (its own sensor fusion) calls frp_nmpc_occmap_refresh afterwards.
- * NOT here: projectDepthImage / raycastProcess (:314-533).  Their cache_rayend_ / cache_traverse_ early exits make the result
- * depend on the order in which the pixels of a frame are visited, so a frame is a serial computation, and their input is an
- * OpenCV depth image.
+ * A caller with a depth camera calls frp_nmpc_occmap_fuse_depth per frame instead (below, frp_nmpc_occmap_fuse.h): projectDepthImage
+ * / raycastProcess (:314-533) on the device, with the serial result of their cache_rayend_ / cache_traverse_ early exits to the bit.
  * Every call is asynchronous on `stream`, synchronises nothing, returns no host-side count, and can be captured into a hipGraph
  * (the struct is read during the call; the device arrays it points to are read when the kernels run).  FRP_ERR_ARG is returned
  * before anything is launched; FRP_ERR_NO_DEVICE without a device.
@@ -551,6 +550,10 @@ int frp_nmpc_occmap_local_view(const frp_nmpc_occmap *map, const frp_nmpc_occmap
  * local_box [.][6] (of a local view) or NULL: the whole map is local; planner [Q] = row of local_box for each query, or NULL: row 0. */
 int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, const int *planner, const int *local_box, int *state,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* Depth-image ray-cast log-odds fusion (projectDepthImage / raycastProcess, :314-563): frp_nmpc_occmap_fuse, its workspace size
+ * and the per-frame call.  A header of its own, part of this section and of this ABI version. */
+#include "frp_nmpc_occmap_fuse.h"
 
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
