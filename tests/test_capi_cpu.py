@@ -506,3 +506,15 @@ def test_step_parity_cases_cover_every_kernel_instantiation_that_ships(lib, tmp_
     assert bundles == 5, (bundles, names)
     assert all(c == 1 for c in names.values()), names
     assert set(names) == set(CASES), (sorted(set(names) - set(CASES)), sorted(set(CASES) - set(names)))
+
+
+def test_slot_reuse_cases_cover_every_kernel_instantiation_that_ships(tmp_path):
+    """The launches of tests/test_gpu_slot_reuse.py name exactly the nmpc_ipm_lds_kernel instantiations of the built library: a
+    new variant cannot ship without a slot-reuse case."""
+    from forces_resilient_planner_amd import build
+    from .test_gpu_slot_reuse import LAUNCHES
+    if not os.path.exists(solver.LIB_PATH):
+        build.build_native(force=False, verbose=False)
+    names, _ = _kernel_instantiations(solver.LIB_PATH, tmp_path)
+    covered = {l[1] for l in LAUNCHES}
+    assert set(names) == covered, (sorted(set(names) - covered), sorted(covered - set(names)))

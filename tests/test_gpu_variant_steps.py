@@ -115,11 +115,11 @@ def _rel(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-12)))
 
 
-def measure(name):
-    """Runs one case.  Returns (selected kernel name, {k: maxima}, GN distance at k = 3, oracle fallbacks, {k: agreement}):
+def measure(name, case=None):
+    """Runs one case (CASES[name], or `case`: another launch that selects the instantiation).  Returns (selected kernel name, {k: maxima}, GN distance at k = 3, oracle fallbacks, {k: agreement}):
     agreement = the fraction of problems whose flag, iteration count and redo counter equal the oracle's; the maxima are
     taken over those problems."""
-    kind, N, M, model, bfun, tw, q4 = CASES[name]
+    kind, N, M, model, bfun, tw, q4 = CASES[name] if case is None else case
     B = bfun(_cus())
     w, wn, MF = _workload(kind, N, M, model, B)
     m = 9 * N // 20 if B <= 1024 else 3 * N // 10  # (the kernel's rule for twist = -1, frp_ipm_lds.hip: twist_stages)
