@@ -115,6 +115,10 @@ class OccMapFuse(ctypes.Structure):  # frp_nmpc_occmap_fuse (include/frp_nmpc_oc
                 ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
 
 
+class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
+    _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
+
+
 ASTAR_MAX_PATH = 256
 ASTAR_REACH_HORIZON, ASTAR_REACH_END, ASTAR_NO_PATH, ASTAR_REACH_END_BUT_SHOT_FAILS = 1, 2, 3, 4
 
@@ -135,6 +139,48 @@ OCCMAP_FUSE_DEFAULTS = dict(depth_scale=1000.0, depth_filter_mindist=0.1, depth_
 OCCMAP_FUSE_DEFAULT_ROUNDS = 128  # FRP_OCCMAP_FUSE_DEFAULT_ROUNDS
 # section (8)'s second header (include/frp_nmpc_occmap_fuse.h): checked at load time like EXPORTS
 FUSE_EXPORTS = ["frp_nmpc_occmap_fuse_workspace_bytes", "frp_nmpc_occmap_fuse_depth"]
+
+# section (8)'s third header (include/frp_nmpc_occmap_check.h): the safety timer's checks, checked at load time like EXPORTS
+CHECK_EXPORTS = ["frp_nmpc_occmap_check_surround", "frp_nmpc_occmap_check_paths", "frp_nmpc_occmap_check_goals"]
+OCCMAP_BODY = (0.27, 0.0425)  # occ_map/ego_r, ego_h of the reference's launch file
+SAFETY_INFLATE_CHECK, SAFETY_INFLATE_SEARCH = 1.2, 1.5  # checkReplanCallback's two ratios (nmpc_manage.cpp:291, :308, :333)
+
+
+def goal_search_table():
+    """The candidate offsets of checkReplanCallback's goal search (plan_manage/src/nmpc_manage.cpp:295-305), from its three loops run
+    as written: r and nz are accumulated in double (r += dr, nz += dz) against `r <= 5 * dr + 1e-3` and `nz <= 1.6`, and theta
+    runs over DEGREES (-90 ... 270 in steps of 30) but is handed to cos / sin as it is, i.e. as RADIANS -- that is the reference's
+    behaviour, kept.  Row c is (r * cos(theta), r * sin(theta), nz): the device adds the first two to the goal and takes the third
+    as the new z.  Returns (table [n_groups * group_size, 3] float64, n_groups, group_size); a group is one (r, theta) pair's nz
+    loop, the loop the reference's `break` leaves.  The counts come from the loops (5 * 13 groups of 4 in IEEE double)."""
+    import math
+    dr, dtheta, dz = 0.2, 30.0, 0.2                                       # :295
+    rows, sizes = [], []
+    r = dr
+    while r <= 5 * dr + 1e-3:                                             # :299
+        theta = -90.0
+        while theta <= 270:                                               # :300
+            n = 0
+            nz = 1.0
+            while nz <= 1.6:                                              # :301
+                rows.append((r * math.cos(theta), r * math.sin(theta), nz))  # :303-305
+                n += 1
+                nz += dz
+            sizes.append(n)
+            theta += dtheta
+        r += dr
+    assert len(set(sizes)) == 1, sizes
+    return np.array(rows, dtype=np.float64).reshape(-1, 3), len(sizes), sizes[0]
+
+
+class SafetyCheck:
+    """What OccupancyMap.safety_check returns (int32 [B] device tensors): goal_blocked (the goal collided at ratio 1.2), goal_hits (how
+    often the search moved it), first_hit (smallest colliding path sample, -1: none) and replan = goal_blocked | (first_hit >= 0),
+    the mask DeviceFleet.replan(replan=...) and AstarPlanner.plan(active=...) take."""
+
+    def __init__(self, goal_blocked, goal_hits, first_hit, replan):
+        self.goal_blocked, self.goal_hits, self.first_hit, self.replan = goal_blocked, goal_hits, first_hit, replan
+
 
 # ROS parameter defaults of the tube model (nmpc_solver.cpp:68-74, nmpc_utils.h:188-189)
 TUBE_DEFAULTS = dict(mass=0.74, drag=0.33, ego_r=0.27, ego_h=0.0425, noise=(0.5, 0.5, 0.5), epsilon=0.06, Ts=0.05)
@@ -233,7 +279,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + CHECK_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -248,6 +294,10 @@ def lib():
         l.frp_nmpc_occmap_fuse_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_occmap_fuse_workspace_bytes.argtypes = [pm, ctypes.POINTER(OccMapFuse)]
         l.frp_nmpc_occmap_fuse_depth.argtypes = [pm, ctypes.POINTER(OccMapFuse), vp, sz, vp, sz, vp]
+        pb, ci, cd = ctypes.POINTER(OccMapBody), ctypes.c_int, ctypes.c_double
+        l.frp_nmpc_occmap_check_surround.argtypes = [pm, pb, cd, ci, vp, vp, vp, vp, vp, sz, vp]
+        l.frp_nmpc_occmap_check_paths.argtypes = [pm, pb, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
+        l.frp_nmpc_occmap_check_goals.argtypes = [pm, pb, cd, cd, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, sz, vp]
         _lib = l
     return _lib
 
@@ -559,6 +609,7 @@ class OccupancyMap:
         self.fuse_ws = None          # the fusion workspace: allocated by fuse_depth, grown when a larger frame needs it
         self._last_frame = None      # (depth, T_wc) of the previous filtered frame (last_depth_image, last_T_wc: occ_map.cpp:423-424)
         self._fusing_against = None  # the frame the latest filtered call reads on its stream: kept alive until the next call
+        self._goal_table = None      # (table, n_groups, group_size) of goal_search_table() on the device: made by the first safety_check
         if world is not None and world.get("occ") is not None:
             o = torch.from_numpy(np.ascontiguousarray(world["occ"], dtype=np.uint8)).to(self.device)
             assert tuple(o.shape) == self.grid, (tuple(o.shape), self.grid)
@@ -752,6 +803,65 @@ class OccupancyMap:
                 if a is not None:
                     a.record_stream(stream)
         return st
+
+
+    def check_surround(self, pos, inflate_ratio, local_box=None, planner=None, body=OCCMAP_BODY, stream=None):
+        """checkPosSurround(pos, inflate_ratio) (occ_map.cpp:625-643) of pos [Q,3]: int32 [Q] device tensor, 1 = free (every probe of
+        the inflated body is 0), 0 = collision (a probe is occupied or outside the map).  local_box / planner as in query()."""
+        t = self.torch
+        q = self._dev(pos, t.float64)
+        Q = int(q.shape[0])
+        assert tuple(q.shape) == (Q, 3)
+        out = t.zeros((Q,), dtype=t.int32, device=self.device)
+        pl = None if planner is None else self._dev(planner, t.int32)
+        lb = None if local_box is None else self._dev(local_box, t.int32)
+        bd = OccMapBody(float(body[0]), float(body[1]))
+        self._call("frp_nmpc_occmap_check_surround", ctypes.byref(bd), float(inflate_ratio), Q, q.data_ptr() if Q else None,
+                   pl.data_ptr() if pl is not None else None, lb.data_ptr() if lb is not None else None, out.data_ptr(), stream=stream)
+        if stream is not None:
+            for a in (q, pl, lb):
+                if a is not None:
+                    a.record_stream(stream)
+        return out
+
+    def safety_check(self, end_pt, kino_path, kino_size, have_target=None, have_traj=None, local_box=None, stride=5, stream=None,
+                     body=OCCMAP_BODY, out=None):
+        """One tick of the safety timer (NMPCManage::checkReplanCallback, nmpc_manage.cpp:285-341) for B planners, on the live bit
+        plane: the goal test and search (frp_nmpc_occmap_check_goals; end_pt [B,3] f64 device tensor, UPDATED IN PLACE where the
+        search moves a blocked goal) and the path walk (frp_nmpc_occmap_check_paths; kino_path [B,K,3] f64 / kino_size [B] int32 as
+        AstarPlanner keeps them, every stride-th sample).  have_target / have_traj: int32 [B] or None (all set); local_box [B,6] of
+        a local view or None.  Returns a SafetyCheck; nothing is synchronised.  out: a SafetyCheck to write into (a captured
+        graph replays into the same buffers).  The FSM transitions stay with the caller."""
+        t = self.torch
+        dev = self.log_odds.device
+        for a, dt in ((end_pt, t.float64), (kino_path, t.float64), (kino_size, t.int32)):
+            assert t.is_tensor(a) and a.dtype == dt and a.is_contiguous() and a.device == dev
+        B, K = int(kino_path.shape[0]), int(kino_path.shape[1])
+        assert tuple(kino_path.shape) == (B, K, 3) and tuple(end_pt.shape) == (B, 3) and tuple(kino_size.shape) == (B,)
+        opt = [None if a is None else self._dev(a, t.int32) for a in (have_target, have_traj, local_box)]
+        ht, hj, lb = opt
+        assert lb is None or tuple(lb.shape) == (B, 6)
+        if out is None:
+            z = lambda: t.zeros((B,), dtype=t.int32, device=self.device)
+            out = SafetyCheck(z(), z(), z(), z())
+        if self._goal_table is None:
+            tab, ng, gs = goal_search_table()
+            self._goal_table = (t.from_numpy(tab).to(self.device), ng, gs)
+        tab, ng, gs = self._goal_table
+        bd = OccMapBody(float(body[0]), float(body[1]))
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        self._call("frp_nmpc_occmap_check_goals", ctypes.byref(bd), SAFETY_INFLATE_CHECK, SAFETY_INFLATE_SEARCH, B, end_pt.data_ptr(), ptr(ht), ptr(lb),
+                   ng, gs, tab.data_ptr(), out.goal_blocked.data_ptr(), out.goal_hits.data_ptr(), stream=stream)
+        self._call("frp_nmpc_occmap_check_paths", ctypes.byref(bd), SAFETY_INFLATE_CHECK, B, K, int(stride), kino_path.data_ptr(), kino_size.data_ptr(),
+                   ptr(hj), ptr(lb), out.first_hit.data_ptr(), stream=stream)
+        with t.cuda.stream(s):
+            t.bitwise_or(out.goal_blocked, (out.first_hit >= 0).to(t.int32), out=out.replan)
+        if stream is not None:
+            for a in (end_pt, kino_path, kino_size, tab, out.goal_blocked, out.goal_hits, out.first_hit, out.replan) + tuple(opt):
+                if a is not None:
+                    a.record_stream(stream)
+        return out
 
 
 class AstarPlanner:

@@ -5,8 +5,12 @@
     and the bytes/s that implies;
   * the corridor step fed from per-planner clouds of the local view against the shared whole-map cloud + uniform grid
     (the route of tools/full_tick_bench.py) and against the same shared cloud + grid CUT to each planner's local box
-    (frp_nmpc_corridor_batch_cut: box-only view + corridor), same planners, same session, with the bytes each route allocates.
-Reported, not gated.   python tools/occmap_bench.py [reps=20]"""
+    (frp_nmpc_corridor_batch_cut: box-only view + corridor), same planners, same session, with the bytes each route allocates;
+  * `safety`: one tick of the safety timer (OccupancyMap.safety_check: goal test + search, path walk) for 4096 planners with
+    200-sample paths, stride 5, on the reference-sized map with 25 pillars, against the only other device route: the same probes
+    (243 per checked position) generated on the device with torch and pushed through frp_nmpc_occmap_query, then reduced.  The
+    query route has no goal SEARCH (its candidates depend on one another); safety_check's time includes it.
+Reported, not gated.   python tools/occmap_bench.py [reps=20] [safety]   (`safety`: that leg alone, merged into the existing file)"""
 import json
 import os
 import sys
@@ -57,6 +61,65 @@ def view_bench(dm, centres, P):
     ms = timed(lambda: dm.local_view(c, P, out=view))
     return dict(B=B, P=P, ms=ms, overflowed=int((n < 0).sum()), points_mean=float(np.abs(n).mean()), points_max=int(np.abs(n).max()),
                 plane_bytes=plane_bytes, point_bytes=point_bytes, GBps=(plane_bytes + point_bytes) / ms / 1e6), view
+
+
+def safety_bench(dm, rng, B=4096, K=200, stride=5):
+    """ms of safety_check and of the query route on the same planners; the two routes' goal_blocked and first_hit must agree."""
+    ratio, (ego_r, ego_h) = solver.SAFETY_INFLATE_CHECK, solver.OCCMAP_BODY
+    start = np.c_[rng.uniform(-17, 17, B), rng.uniform(-17, 17, B), rng.uniform(0.8, 1.6, B)]
+    ang = rng.uniform(-np.pi, np.pi, B)
+    step = 0.05 * np.arange(K)                                                  # samples 0.05 m apart: 10 m of path
+    path = start[:, None, :] + np.stack([np.cos(ang)[:, None] * step, np.sin(ang)[:, None] * step, np.zeros((B, K))], -1)
+    path[..., :2] = np.clip(path[..., :2], -19.0, 19.0)
+    kp = torch.from_numpy(np.ascontiguousarray(path)).to(DEV)
+    sz = torch.full((B,), K, dtype=torch.int32, device=DEV)
+    end0 = kp[:, -1, :].clone()
+    end = end0.clone()
+    out = dm.safety_check(end, kp, sz, stride=stride)
+    torch.cuda.synchronize()
+
+    def run_check():
+        end.copy_(end0)                                                         # (a moved goal would make the next repetition another problem)
+        dm.safety_check(end, kp, sz, stride=stride, out=out)
+
+    h = [int(np.ceil(e * ratio / dm.resolution)) for e in (ego_r, ego_r, ego_h)]
+    off = torch.tensor([[i, j, k] for i in range(-h[0], h[0] + 1) for j in range(-h[1], h[1] + 1) for k in range(-h[2], h[2] + 1)],
+                       dtype=torch.float64, device=DEV) * dm.resolution         # Vector3d(i, j, k) * resolution_
+    S = len(range(0, K, stride))
+    state = {}
+
+    def run_query():
+        pos = torch.cat([end0[:, None, :], kp[:, ::stride, :]], 1)              # [B, 1 + S, 3]: the goal, then the checked samples
+        probes = (pos[:, :, None, :] + off[None, None, :, :]).reshape(-1, 3)    # pos + offset, one rounding: the reference's probes
+        st = dm.query(probes)
+        hit = (st != 0).view(B, 1 + S, -1).any(-1)
+        idx = torch.where(hit[:, 1:].any(1), hit[:, 1:].int().argmax(1) * stride, torch.full((B,), -1, device=DEV))
+        state["blocked"], state["first_hit"] = hit[:, 0].int(), idx.int()
+
+    ms_check = timed(run_check)
+    ms_query = timed(run_query, max(3, REPS // 4))
+    ms_check2 = timed(run_check)
+    run_check(); run_query(); torch.cuda.synchronize()
+    agree = bool(torch.equal(out.goal_blocked, state["blocked"]) and torch.equal(out.first_hit, state["first_hit"]))
+    return dict(B=B, K=K, stride=stride, probes_per_position=int(off.shape[0]), positions=B * (1 + S), map="40x40x5", pillars=25,
+                safety_check_ms=ms_check, safety_check_ms_second_pass=ms_check2, query_route_ms=ms_query, query_route_over_safety_check=ms_query / ms_check,
+                query_route_note="goal test + path walk only, no goal search; includes generating the probes and reducing the states with torch",
+                goal_blocked=int(out.goal_blocked.sum()), goals_moved=int((out.goal_hits > 0).sum()), paths_hit=int((out.first_hit >= 0).sum()),
+                routes_agree=agree)
+
+
+def safety_only():
+    rng = np.random.default_rng(0)
+    ref_map = solver.OccupancyMap(origin=(-20.0, -20.0, 0.0), map_size=(40.0, 40.0, 5.0), resolution=0.1)
+    ref_map.insert_cloud(torch.from_numpy(pillar_cloud(rng, 25, (-18, -18), (18, 18), 3.0)).to(DEV))
+    r = safety_bench(ref_map, rng)
+    r["device"] = torch.cuda.get_device_name(0); r["reps"] = REPS
+    path = os.path.join(ROOT, "profiles", "occmap_bench.json")
+    res = json.load(open(path)) if os.path.exists(path) else {}
+    res["safety"] = r
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(r))
 
 
 def main():
@@ -134,6 +197,8 @@ def main():
     else:
         cor["shared_cloud_grid"] = {"skipped": f"the whole map holds {-nw} occupied voxels, more than FRP_CORRIDOR_MAX_POINTS"}
     res["corridor"] = cor
+    res["safety"] = safety_bench(dm, rng)
+    print(json.dumps(res["safety"]))
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "occmap_bench.json"), "w") as f:
         json.dump(res, f, indent=1)
@@ -141,4 +206,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "safety" in sys.argv[2:]:
+        safety_only()
+    else:
+        main()
