@@ -115,6 +115,16 @@ class OccMapFuse(ctypes.Structure):  # frp_nmpc_occmap_fuse (include/frp_nmpc_oc
                 ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
 
 
+class OccMapFuseBatch(ctypes.Structure):  # frp_nmpc_occmap_fuse_batch (include/frp_nmpc_occmap_fuse_batch.h)
+    _fields_ = [("frames", ctypes.c_int), ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("depth", ctypes.c_void_p), ("last_depth", ctypes.c_void_p),
+                ("T_wc", ctypes.c_void_p), ("last_T_wc", ctypes.c_void_p), ("active", ctypes.c_void_p), ("K", ctypes.c_double * 9),
+                ("depth_scale", ctypes.c_double), ("depth_filter_mindist", ctypes.c_double), ("depth_filter_tolerance", ctypes.c_double),
+                ("depth_filter_margin", ctypes.c_int), ("skip_pixel", ctypes.c_int),
+                ("prob_hit_log", ctypes.c_double), ("prob_miss_log", ctypes.c_double),
+                ("min_ray_length", ctypes.c_double), ("max_ray_length", ctypes.c_double),
+                ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -139,6 +149,10 @@ OCCMAP_FUSE_DEFAULTS = dict(depth_scale=1000.0, depth_filter_mindist=0.1, depth_
 OCCMAP_FUSE_DEFAULT_ROUNDS = 128  # FRP_OCCMAP_FUSE_DEFAULT_ROUNDS
 # section (8)'s second header (include/frp_nmpc_occmap_fuse.h): checked at load time like EXPORTS
 FUSE_EXPORTS = ["frp_nmpc_occmap_fuse_workspace_bytes", "frp_nmpc_occmap_fuse_depth"]
+# ... and its batched form (include/frp_nmpc_occmap_fuse_batch.h): F frames per call, poses read on the device
+FUSE_BATCH_EXPORTS = ["frp_nmpc_occmap_fuse_batch_workspace_bytes", "frp_nmpc_occmap_fuse_depth_batch"]
+OCCMAP_FUSE_MAX_FRAMES = 64     # FRP_OCCMAP_FUSE_MAX_FRAMES
+OCCMAP_FUSE_REFUSED = -256      # FRP_OCCMAP_FUSE_REFUSED: status[f][0] of a frame whose pose the device refuses
 
 # section (8)'s third header (include/frp_nmpc_occmap_check.h): the safety timer's checks, checked at load time like EXPORTS
 CHECK_EXPORTS = ["frp_nmpc_occmap_check_surround", "frp_nmpc_occmap_check_paths", "frp_nmpc_occmap_check_goals"]
@@ -279,7 +293,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + CHECK_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -294,6 +308,9 @@ def lib():
         l.frp_nmpc_occmap_fuse_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_occmap_fuse_workspace_bytes.argtypes = [pm, ctypes.POINTER(OccMapFuse)]
         l.frp_nmpc_occmap_fuse_depth.argtypes = [pm, ctypes.POINTER(OccMapFuse), vp, sz, vp, sz, vp]
+        l.frp_nmpc_occmap_fuse_batch_workspace_bytes.restype = ctypes.c_size_t
+        l.frp_nmpc_occmap_fuse_batch_workspace_bytes.argtypes = [pm, ctypes.POINTER(OccMapFuseBatch)]
+        l.frp_nmpc_occmap_fuse_depth_batch.argtypes = [pm, ctypes.POINTER(OccMapFuseBatch), vp, sz, vp, sz, vp]
         pb, ci, cd = ctypes.POINTER(OccMapBody), ctypes.c_int, ctypes.c_double
         l.frp_nmpc_occmap_check_surround.argtypes = [pm, pb, cd, ci, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_paths.argtypes = [pm, pb, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -607,6 +624,7 @@ class OccupancyMap:
             raise ValueError("frp_nmpc_occmap refuses this map description (resolution, map_size, grid)")
         self.ws = torch.empty((self.ws_bytes // 4 + 1,), dtype=torch.int32, device=self.device)
         self.fuse_ws = None          # the fusion workspace: allocated by fuse_depth, grown when a larger frame needs it
+        self.fuse_batch_ws = None    # the batched fusion's workspace: allocated by fuse_depth_batch, grown when a larger batch needs it
         self._last_frame = None      # (depth, T_wc) of the previous filtered frame (last_depth_image, last_T_wc: occ_map.cpp:423-424)
         self._fusing_against = None  # the frame the latest filtered call reads on its stream: kept alive until the next call
         self._goal_table = None      # (table, n_groups, group_size) of goal_search_table() on the device: made by the first safety_check
@@ -733,6 +751,87 @@ class OccupancyMap:
             depth.record_stream(stream)
             if last is not None:
                 last[0].record_stream(stream)
+        return status
+
+    def fuse_depth_batch(self, depth, K, T_wc, *, last_depth=None, last_T_wc=None, active=None, status=None, stream=None, **params):
+        """F camera frames into the map in one call (include/frp_nmpc_occmap_fuse_batch.h): the map afterwards is, to the bit, what
+        fuse_depth leaves after frames 0 ... F - 1 in that order; frames that are inactive, refused or not converged are skipped.
+        depth [F, rows, cols] uint16, T_wc [F, 4, 4] float64; with the shift filter last_depth and last_T_wc of the same shapes (the
+        caller keeps the previous frames; None: the unfiltered loops); active [F] int32 or None, 0 = the frame is not fused.  Each
+        may be a numpy array, which is uploaded, or a device tensor, which is used IN PLACE: the poses are read by the kernels, so a
+        captured call replays with whatever the caller has written into its tensors since.  K 3 x 3 (host) and params (the keys of
+        OCCMAP_FUSE_DEFAULTS) are shared by the frames.
+        Returns the status tensor (int32 [F, 2], device; nothing is synchronised): per frame [rounds used, rays cast] as fuse_depth
+        reports them, [-max_rounds, rays] for a frame that did not converge (it contributes nothing, the others are fused),
+        [0, 0] for an inactive frame, [OCCMAP_FUSE_REFUSED, 0] for a pose fuse_depth would refuse (non-finite, singular last rotation).
+        status: a tensor to write into.  ValueError: a description the library refuses."""
+        t = self.torch
+        unknown = set(params) - set(OCCMAP_FUSE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"fuse_depth_batch: unknown parameters {sorted(unknown)}")
+        d = dict(OCCMAP_FUSE_DEFAULTS); d.update(params)
+
+        def image(a, what):
+            if not t.is_tensor(a):
+                a = np.ascontiguousarray(a)
+                if a.dtype != np.uint16:
+                    raise TypeError(f"{what} must be uint16 (the reference's depth_image.at<uint16_t>)")
+                a = t.from_numpy(a.view(np.int16)).to(self.device).view(t.uint16)
+            if a.dtype != t.uint16 or a.dim() != 3 or a.device != self.log_odds.device or not a.is_contiguous():
+                raise TypeError(f"{what} must be a contiguous [F, rows, cols] uint16 tensor on the map's device")
+            return a
+
+        def poses(a, what):
+            if not t.is_tensor(a):
+                a = t.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)
+            if a.dtype != t.float64 or tuple(a.shape) != (F, 4, 4) or a.device != self.log_odds.device or not a.is_contiguous():
+                raise TypeError(f"{what} must be a contiguous [F, 4, 4] float64 tensor on the map's device")
+            return a
+
+        depth = image(depth, "depth")
+        F = int(depth.shape[0])
+        T = poses(T_wc, "T_wc")
+        if (last_depth is None) != (last_T_wc is None):
+            raise ValueError("fuse_depth_batch: last_depth and last_T_wc go together")
+        last = lastT = None
+        if last_depth is not None:
+            last, lastT = image(last_depth, "last_depth"), poses(last_T_wc, "last_T_wc")
+            if tuple(last.shape) != tuple(depth.shape):
+                raise ValueError("fuse_depth_batch: last_depth has another shape than depth")
+        if active is not None:
+            if not t.is_tensor(active):
+                active = t.from_numpy(np.ascontiguousarray(active, dtype=np.int32)).to(self.device)
+            if active.dtype != t.int32 or tuple(active.shape) != (F,) or active.device != self.log_odds.device or not active.is_contiguous():
+                raise TypeError("active must be a contiguous [F] int32 tensor on the map's device")
+        if status is None:
+            status = t.zeros((F, 2), dtype=t.int32, device=self.device)
+        if status.dtype != t.int32 or tuple(status.shape) != (F, 2) or status.device != self.log_odds.device or not status.is_contiguous():
+            raise TypeError("status must be a contiguous [F, 2] int32 tensor on the map's device")
+        Kh = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        f = OccMapFuseBatch()
+        f.frames, f.rows, f.cols = F, int(depth.shape[1]), int(depth.shape[2])
+        f.depth, f.T_wc, f.status = depth.data_ptr(), T.data_ptr(), status.data_ptr()
+        f.last_depth = last.data_ptr() if last is not None else None
+        f.last_T_wc = lastT.data_ptr() if lastT is not None else None
+        f.active = active.data_ptr() if active is not None else None
+        f.K[:] = [float(v) for v in Kh.ravel()]
+        for k in ("depth_scale", "depth_filter_mindist", "depth_filter_tolerance", "prob_hit_log", "prob_miss_log", "min_ray_length", "max_ray_length"):
+            setattr(f, k, float(d[k]))
+        f.depth_filter_margin, f.skip_pixel, f.max_rounds = int(d["depth_filter_margin"]), int(d["skip_pixel"]), int(d["max_rounds"])
+        m = self._map()
+        need = int(lib().frp_nmpc_occmap_fuse_batch_workspace_bytes(ctypes.byref(m), ctypes.byref(f)))
+        if need == 0:
+            raise ValueError("frp_nmpc_occmap_fuse_depth_batch refuses this batch description (see include/frp_nmpc_occmap_fuse_batch.h)")
+        if self.fuse_batch_ws is None or self.fuse_batch_ws.numel() < need:
+            self.fuse_batch_ws = t.empty((need,), dtype=t.uint8, device=self.device)
+        _check(lib().frp_nmpc_occmap_fuse_depth_batch(ctypes.byref(m), ctypes.byref(f), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
+                                                      ctypes.c_void_p(self.fuse_batch_ws.data_ptr()), int(self.fuse_batch_ws.numel()),
+                                                      ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_occmap_fuse_depth_batch")
+        if stream is not None:
+            for a in (depth, T, last, lastT, active):
+                if a is not None:
+                    a.record_stream(stream)
         return status
 
     def local_view(self, centres, P, out=None, stream=None):

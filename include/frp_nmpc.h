@@ -555,6 +555,10 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * and the per-frame call.  A header of its own, part of this section and of this ABI version. */
 #include "frp_nmpc_occmap_fuse.h"
 
+/* The same fusion for a batch of frames in one call, poses read on the device: a captured tick replays it with new poses.  A header
+ * of its own, part of this section and of this ABI version. */
+#include "frp_nmpc_occmap_fuse_batch.h"
+
 /* The safety timer's collision checks (checkPosSurround, :625-643, and the goal and path loops of checkReplanCallback,
  * plan_manage/src/nmpc_manage.cpp:285-341) on the bit plane.  A header of its own, part of this section and of this ABI version. */
 #include "frp_nmpc_occmap_check.h"

@@ -10,9 +10,14 @@ Per scene:
 The share of the mark pass needs per-kernel times: run `--profile N` (N frames per scene, nothing timed) under
 rocprofv3 --kernel-trace --stats --output-format csv, then `--merge-stats <..._kernel_stats.csv>` adds the shares to the JSON.
 Reported, not gated: there is no earlier device number to hold these against.
-   python tools/fusion_bench.py [--reps 50] [--windows 5] | --cpu-only | --profile N | --merge-stats CSV"""
+`--frames F` (device): F frames (the scenes in turn, cameras on a circle of 3 m, each turned 0.3 rad off its radius, so that neighbouring ray boxes
+overlap) through ONE solver.OccupancyMap.fuse_depth_batch call and through F fuse_depth calls, each path in a child process of its
+own under its own time limit, one after the other; ms per F frames, the round counts and whether both maps are the same bytes go
+under the key "batch" of the JSON (the rest of the file is kept).
+   python tools/fusion_bench.py [--reps 50] [--windows 5] | --cpu-only | --profile N | --merge-stats CSV | --frames F"""
 import argparse
 import csv
+import hashlib
 import json
 import os
 import struct
@@ -120,6 +125,91 @@ def device_scene(name, port, reps, windows):
     return res
 
 
+def keep_batch(res):
+    """The "batch" key of an earlier --frames run survives a rewrite of the rest of the file."""
+    if os.path.exists(OUT):
+        with open(OUT) as f:
+            old = json.load(f)
+        if "batch" in old:
+            res["batch"] = old["batch"]
+    return res
+
+
+def batch_frames(F):
+    """F frames for the --frames mode: [(depth, T_wc)]."""
+    out = []
+    for k in range(F):
+        a = 2.0 * np.pi * k / F
+        out.append((scene(SCENES[k % len(SCENES)]), FO.pose((3.0 * np.cos(a), 3.0 * np.sin(a), 1.61), yaw=a + 0.3)))
+    return out
+
+
+def frames_step(path, F, reps, windows):
+    """One path of the --frames mode (a process of its own): "batch" = one fuse_depth_batch call, "single" = F fuse_depth calls.
+    Prints one JSON line."""
+    import torch
+    frames = batch_frames(F)
+    dm = device_map()
+    T = np.ascontiguousarray(np.stack([t for _, t in frames]))
+    if path == "batch":
+        depth = to_device(dm, np.ascontiguousarray(np.stack([d for d, _ in frames])))
+        Td = torch.from_numpy(T).to(dm.device)
+        status = torch.zeros((F, 2), dtype=torch.int32, device=dm.device)
+
+        def run(**kw):
+            dm.fuse_depth_batch(depth, K, Td, status=status, **kw)
+    else:
+        depth = [to_device(dm, d) for d, _ in frames]
+        status = torch.zeros((F, 2), dtype=torch.int32, device=dm.device)
+
+        def run(**kw):
+            for k in range(F):
+                dm.fuse_depth(depth[k], K, T[k], status=status[k], **kw)
+    run()
+    torch.cuda.synchronize()
+    st = status.cpu().numpy()
+    res = dict(path=path, rounds=[int(v) for v in st[:, 0]], rays=[int(v) for v in st[:, 1]],
+               map_sha256=hashlib.sha256(dm.log_odds.cpu().numpy().tobytes() + dm.occ.cpu().numpy().tobytes() + dm.ws.cpu().numpy().tobytes()).hexdigest(),
+               launches_default=(2 * solver.OCCMAP_FUSE_DEFAULT_ROUNDS + 7) if path == "batch" else F * (2 * solver.OCCMAP_FUSE_DEFAULT_ROUNDS + 6))
+    res["ms_default_cap"] = windows_ms(run, reps, windows)
+    top = max(res["rounds"])
+    if top > 0:
+        res["ms_cap_at_largest_rounds"] = windows_ms(lambda: run(max_rounds=top), reps, windows)
+    g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    with torch.cuda.graph(g, stream=side):
+        run(stream=torch.cuda.current_stream())
+    res["ms_graph_default_cap"] = windows_ms(g.replay, reps, windows)
+    print(json.dumps(res), flush=True)
+
+
+def frames_mode(F, reps, windows, limit):
+    """Both paths one after the other, each in a child under its own time limit; the second is not started when the first failed."""
+    out = {}
+    for path in ("batch", "single"):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--frames", str(F), "--frames-step", path, "--reps", str(reps), "--windows", str(windows)],
+                           capture_output=True, text=True, timeout=limit)
+        if r.returncode != 0:
+            raise SystemExit(f"--frames: the {path} step failed ({r.returncode}), nothing more is started\n{r.stdout}\n{r.stderr}")
+        out[path] = json.loads(r.stdout.strip().splitlines()[-1])
+        print(path, json.dumps(out[path]), flush=True)
+    b, s = out["batch"], out["single"]
+    res = dict(F=F, image=[ROWS, COLS], grid=[400, 400, 50], reps=reps, windows=windows, rounds=b["rounds"], rays=b["rays"],
+               same_status=bool(b["rounds"] == s["rounds"] and b["rays"] == s["rays"]), same_map=bool(b["map_sha256"] == s["map_sha256"]),
+               what="ms per F frames: one fuse_depth_batch call against F fuse_depth calls, same session, one process each", batch=b, single=s)
+    for k in ("ms_default_cap", "ms_cap_at_largest_rounds", "ms_graph_default_cap"):
+        if k in b and k in s:
+            res["batch_over_single_" + k[3:]] = b[k]["median"] / s[k]["median"]
+    full = {}
+    if os.path.exists(OUT):
+        with open(OUT) as f:
+            full = json.load(f)
+    full["batch"] = res
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "w") as f:
+        json.dump(full, f, indent=1)
+    print(json.dumps({k: v for k, v in res.items() if k not in ("batch", "single")}))
+
+
 def merge_stats(path):
     """Per-kernel totals of a rocprofv3 kernel-stats CSV -> the share of every fusion kernel among the fusion kernels."""
     with open(path, newline="") as f:
@@ -152,7 +242,14 @@ def main():
     ap.add_argument("--cpu-only", action="store_true", help="the counts and the port's host time only (no device needed)")
     ap.add_argument("--profile", type=int, default=0, metavar="N", help="fuse N frames per scene and exit (for a run under the profiler)")
     ap.add_argument("--merge-stats", metavar="CSV")
+    ap.add_argument("--frames", type=int, default=0, metavar="F", help="F frames through fuse_depth_batch and through F fuse_depth calls -> the key \"batch\"")
+    ap.add_argument("--frames-step", choices=("batch", "single"), help="(what --frames starts: one of its two paths, in this process)")
+    ap.add_argument("--step-limit", type=float, default=240.0, help="time limit of each --frames step in seconds")
     a = ap.parse_args()
+    if a.frames:
+        if a.frames_step:
+            return frames_step(a.frames_step, a.frames, a.reps, a.windows)
+        return frames_mode(a.frames, a.reps, a.windows, a.step_limit)
     if a.merge_stats:
         return merge_stats(a.merge_stats)
     if a.profile:
@@ -170,7 +267,7 @@ def main():
         res = {"device": "not measured (--cpu-only)", "scenes": {name: {"cpu_port": port[name]} for name in SCENES},
                "largest_rounds": max(p["rounds"] for p in port.values())}
         with open(OUT, "w") as f:
-            json.dump(res, f, indent=1)
+            json.dump(keep_batch(res), f, indent=1)
         return
     import torch
     scanned = len(range(1, ROWS - 1, 2)) * len(range(1, COLS - 1, 2))
@@ -187,7 +284,7 @@ def main():
     res["largest_rounds"] = max(r["rounds"] for r in res["scenes"].values())
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     with open(OUT, "w") as f:
-        json.dump(res, f, indent=1)
+        json.dump(keep_batch(res), f, indent=1)
 
 
 if __name__ == "__main__":
