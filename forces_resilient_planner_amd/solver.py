@@ -125,6 +125,12 @@ class OccMapFuseBatch(ctypes.Structure):  # frp_nmpc_occmap_fuse_batch (include/
                 ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
 
 
+class OccMapRender(ctypes.Structure):  # frp_nmpc_occmap_render (include/frp_nmpc_occmap_render.h)
+    _fields_ = [("frames", ctypes.c_int), ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("T_wc", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("K", ctypes.c_double * 9), ("depth_scale", ctypes.c_double), ("max_range", ctypes.c_double),
+                ("depth", ctypes.c_void_p), ("voxel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -153,6 +159,9 @@ FUSE_EXPORTS = ["frp_nmpc_occmap_fuse_workspace_bytes", "frp_nmpc_occmap_fuse_de
 FUSE_BATCH_EXPORTS = ["frp_nmpc_occmap_fuse_batch_workspace_bytes", "frp_nmpc_occmap_fuse_depth_batch"]
 OCCMAP_FUSE_MAX_FRAMES = 64     # FRP_OCCMAP_FUSE_MAX_FRAMES
 OCCMAP_FUSE_REFUSED = -256      # FRP_OCCMAP_FUSE_REFUSED: status[f][0] of a frame whose pose the device refuses
+
+# section (8)'s fifth header (include/frp_nmpc_occmap_render.h): depth images rendered from the map, camera poses from planner states
+RENDER_EXPORTS = ["frp_nmpc_occmap_render_depth", "frp_nmpc_occmap_camera_poses"]
 
 # section (8)'s third header (include/frp_nmpc_occmap_check.h): the safety timer's checks, checked at load time like EXPORTS
 CHECK_EXPORTS = ["frp_nmpc_occmap_check_surround", "frp_nmpc_occmap_check_paths", "frp_nmpc_occmap_check_goals"]
@@ -293,7 +302,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -311,6 +320,8 @@ def lib():
         l.frp_nmpc_occmap_fuse_batch_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_occmap_fuse_batch_workspace_bytes.argtypes = [pm, ctypes.POINTER(OccMapFuseBatch)]
         l.frp_nmpc_occmap_fuse_depth_batch.argtypes = [pm, ctypes.POINTER(OccMapFuseBatch), vp, sz, vp, sz, vp]
+        l.frp_nmpc_occmap_render_depth.argtypes = [pm, ctypes.POINTER(OccMapRender), vp, sz, vp]
+        l.frp_nmpc_occmap_camera_poses.argtypes = [ctypes.c_int, vp, c_double_p, vp, vp]
         pb, ci, cd = ctypes.POINTER(OccMapBody), ctypes.c_int, ctypes.c_double
         l.frp_nmpc_occmap_check_surround.argtypes = [pm, pb, cd, ci, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_paths.argtypes = [pm, pb, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -593,7 +604,8 @@ class OccupancyMap:
     world: the dict of workloads.astar_world -- its geometry, and its occ as the initial content (occupied voxels at
     clamp_max_log, the others at clamp_min_log); or explicit origin / map_size / resolution for an empty map.  fuse_depth() fuses a
     camera frame by ray casting (projectDepthImage / raycastProcess, include/frp_nmpc_occmap_fuse.h) with the reference's serial
-    result to the bit; a caller with another fusion of its own writes .log_odds and calls refresh()."""
+    result to the bit; a caller with another fusion of its own writes .log_odds and calls refresh().  render_depth() is the other
+    direction: the depth images cameras at given poses see of this map (a ground-truth world feeding a belief map's fuse_depth_batch)."""
 
     def __init__(self, world=None, origin=None, map_size=None, resolution=None, local_radius=None, clamp_min_log=None,
                  clamp_max_log=None, min_occupancy_log=None, device="cuda:0"):
@@ -833,6 +845,78 @@ class OccupancyMap:
                 if a is not None:
                     a.record_stream(stream)
         return status
+
+    def render_depth(self, T_wc, K, rows, cols, *, max_range, depth_scale=1000.0, active=None, out=None, voxel=None, status=None, stream=None):
+        """What F cameras at the poses T_wc see of THIS map (include/frp_nmpc_occmap_render.h): the depth images
+        [F, rows, cols] uint16 that fuse_depth_batch takes, one ray per pixel walked through the bit plane.  T_wc [F, 4, 4] float64
+        and active [F] int32 (or None) may be numpy arrays, which are uploaded, or device tensors, which are used IN PLACE: the
+        kernels read them, so a captured call replays with whatever the caller has written since.  K 3 x 3 (host), max_range in
+        metres along the ray.  out: the depth tensor to write into (an inactive frame's image keeps what it holds; a fresh one is
+        zero); voxel: an int32 tensor [F, rows, cols] for the linear voxel index of every return (-1: none), or None; status: an
+        int32 tensor [F, 2] for {1, returns} / {0, 0} inactive / {OCCMAP_FUSE_REFUSED, 0} a non-finite pose.  Returns the depth
+        tensor; nothing is synchronised.  ValueError: a description the library refuses."""
+        t = self.torch
+        dev = self.log_odds.device
+        if not t.is_tensor(T_wc):
+            T_wc = t.from_numpy(np.ascontiguousarray(T_wc, dtype=np.float64)).to(self.device)
+        if T_wc.dtype != t.float64 or T_wc.dim() != 3 or tuple(T_wc.shape[1:]) != (4, 4) or T_wc.device != dev or not T_wc.is_contiguous():
+            raise TypeError("T_wc must be a contiguous [F, 4, 4] float64 tensor on the map's device")
+        F, rows, cols = int(T_wc.shape[0]), int(rows), int(cols)
+        if active is not None:
+            if not t.is_tensor(active):
+                active = t.from_numpy(np.ascontiguousarray(active, dtype=np.int32)).to(self.device)
+            if active.dtype != t.int32 or tuple(active.shape) != (F,) or active.device != dev or not active.is_contiguous():
+                raise TypeError("active must be a contiguous [F] int32 tensor on the map's device")
+        if F < 1 or rows < 1 or cols < 1:
+            raise ValueError("render_depth: at least one frame, one row and one column")
+        if out is None:
+            out = t.zeros((F, rows, cols), dtype=t.int16, device=self.device).view(t.uint16)
+        if out.dtype != t.uint16 or tuple(out.shape) != (F, rows, cols) or out.device != dev or not out.is_contiguous():
+            raise TypeError("out must be a contiguous [F, rows, cols] uint16 tensor on the map's device")
+        if voxel is not None and (voxel.dtype != t.int32 or tuple(voxel.shape) != (F, rows, cols) or voxel.device != dev or not voxel.is_contiguous()):
+            raise TypeError("voxel must be a contiguous [F, rows, cols] int32 tensor on the map's device")
+        if status is None:
+            status = t.zeros((F, 2), dtype=t.int32, device=self.device)
+        if status.dtype != t.int32 or tuple(status.shape) != (F, 2) or status.device != dev or not status.is_contiguous():
+            raise TypeError("status must be a contiguous [F, 2] int32 tensor on the map's device")
+        r = OccMapRender()
+        r.frames, r.rows, r.cols = F, rows, cols
+        r.T_wc, r.active = T_wc.data_ptr(), active.data_ptr() if active is not None else None
+        r.K[:] = [float(v) for v in np.ascontiguousarray(K, dtype=np.float64).reshape(9)]
+        r.depth_scale, r.max_range = float(depth_scale), float(max_range)
+        r.depth, r.voxel, r.status = out.data_ptr(), voxel.data_ptr() if voxel is not None else None, status.data_ptr()
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        m = self._map()
+        rc = lib().frp_nmpc_occmap_render_depth(ctypes.byref(m), ctypes.byref(r), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes, ctypes.c_void_p(s.cuda_stream))
+        if rc == -1003:  # FRP_ERR_ARG
+            raise ValueError("frp_nmpc_occmap_render_depth refuses this description (see include/frp_nmpc_occmap_render.h)")
+        _check(rc, "frp_nmpc_occmap_render_depth")
+        if stream is not None:
+            for a in (T_wc, active, out, voxel, status):
+                if a is not None:
+                    a.record_stream(stream)
+        return out
+
+    def camera_poses(self, state, T_bc, out=None, stream=None):
+        """T_wc [B, 4, 4] = T_wb(state) T_bc for planner states [B, 9] (position, velocity, Euler angles; device tensor, used in
+        place, or array) and the body-to-camera transform T_bc 4 x 4 (host): what render_depth and fuse_depth_batch take as poses,
+        computed where the states are (frp_nmpc_occmap_camera_poses).  out: the tensor to write into."""
+        t = self.torch
+        st = state if t.is_tensor(state) else self._dev(state, t.float64)
+        if st.dtype != t.float64 or st.dim() != 2 or st.shape[1] != 9 or st.device != self.log_odds.device or not st.is_contiguous():
+            raise TypeError("state must be a contiguous [B, 9] float64 tensor on the map's device")
+        B = int(st.shape[0])
+        if out is None:
+            out = t.zeros((B, 4, 4), dtype=t.float64, device=self.device)
+        if out.dtype != t.float64 or tuple(out.shape) != (B, 4, 4) or out.device != self.log_odds.device or not out.is_contiguous():
+            raise TypeError("out must be a contiguous [B, 4, 4] float64 tensor on the map's device")
+        Tb = (ctypes.c_double * 16)(*[float(v) for v in np.ascontiguousarray(T_bc, dtype=np.float64).reshape(16)])
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        _check(lib().frp_nmpc_occmap_camera_poses(B, ctypes.c_void_p(st.data_ptr()) if B else None, Tb, ctypes.c_void_p(out.data_ptr()) if B else None,
+                                                  ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_occmap_camera_poses")
+        if stream is not None:
+            st.record_stream(stream); out.record_stream(stream)
+        return out
 
     def local_view(self, centres, P, out=None, stream=None):
         """local_box + localOccVisCallback's cloud (occ_map.cpp:177-215) of every planner: centres [B,3] f64 (device tensor or

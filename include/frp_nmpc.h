@@ -563,6 +563,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * plan_manage/src/nmpc_manage.cpp:285-341) on the bit plane.  A header of its own, part of this section and of this ABI version. */
 #include "frp_nmpc_occmap_check.h"
 
+/* The sensor: depth images rendered from the map's bit plane for a batch of camera poses, and the poses from planner states.  No
+ * counterpart in the reference (its images come from a simulator).  A header of its own, part of this section and of this ABI
+ * version. */
+#include "frp_nmpc_occmap_render.h"
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 
