@@ -7,10 +7,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfrp_nmpc_amd.so")
-SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_check.hip", "frp_occmap_render.hip"]
+SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_view.hip"]
 HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_batch.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_check.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_occmap_render.h")]
+           os.path.join(ROOT, "include", "frp_nmpc_occmap_render.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_view.h")]
 
 
 def hipcc():
@@ -124,7 +124,9 @@ PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS + ["-DFRP_LDS_SPLIT_TU"],
                     "frp_occmap_check.hip": ["-ffp-contract=off"],
                     # the renderer agrees with its specification (tests/occmap_render_oracle.py) to the bit: the direction, the face
                     # crossings and the midpoint are products and sums rounded one by one
-                    "frp_occmap_render.hip": ["-ffp-contract=off"]}
+                    "frp_occmap_render.hip": ["-ffp-contract=off"],
+                    # the shared view's cloud is the local view's to the bit: the same voxel centres, one rounding per operation
+                    "frp_occmap_view.hip": ["-ffp-contract=off"]}
 OBJDIR = os.path.join(PKG, "_build")
 
 

@@ -1193,7 +1193,10 @@ extern "C" int frp_nmpc_cloud_grid_build(const double *cloud, int P, const doubl
     return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
 }
 
-static int corridor_launch(const frp_nmpc_corridor *p, const frp_nmpc_corridor_cut *cut, void *stream)
+// counted_grid (frp_nmpc_corridor_batch_view): the caller asserts that the grid was built for exactly cloud_count[0] points, so a count
+// does not turn it off; P is then the capacity of the buffers (the kernels clamp the point count to the count, the one-wavefront
+// kernel reads points through the grid alone)
+static int corridor_launch(const frp_nmpc_corridor *p, const frp_nmpc_corridor_cut *cut, void *stream, bool counted_grid = false)
 {
     if (!p || p->B <= 0 || p->N < 1 || p->N > 64 || p->F < 6 || p->F > FRP_CORRIDOR_MAX_F || p->P < 0 || p->P > FRP_CORRIDOR_MAX_POINTS ||
         (p->P > 0 && !p->cloud) || !p->ref_pos || !p->ref_yaw || !p->ellipsoid || !p->poly_A || !p->poly_b || !p->poly_nfaces || !p->poly_index)
@@ -1207,7 +1210,7 @@ static int corridor_launch(const frp_nmpc_corridor *p, const frp_nmpc_corridor_c
         return FRP_ERR_ARG;
     const size_t lds = (size_t)3 * ((p->P + 63) / 64) * sizeof(uint64_t) + frp::CR_LIST * sizeof(uint32_t);
     const bool has_box = p->bbox[0] != 0.0 || p->bbox[1] != 0.0 || p->bbox[2] != 0.0;
-    const bool grid = p->grid_start && has_box && !p->cloud_count;
+    const bool grid = p->grid_start && has_box && (counted_grid || !p->cloud_count);
     // production configuration (shared cloud with a grid, local box, N <= 64 = one lane per stage): one wavefront per planner;
     // planners it flags (more than a tile of points inside a seed ellipsoid, more than CS_PLANES cuts) go to the workgroup kernel
     // through the grid, and what THAT one flags (more in-box points than its LDS list) to the plain-cloud kernel.
@@ -1233,4 +1236,11 @@ extern "C" int frp_nmpc_corridor_batch(const frp_nmpc_corridor *p, void *stream)
 extern "C" int frp_nmpc_corridor_batch_cut(const frp_nmpc_corridor *p, const frp_nmpc_corridor_cut *cut, void *stream)
 {
     return corridor_launch(p, cut, stream);
+}
+
+// include/frp_nmpc_occmap_view.h: the same chain for the device-built shared view -- a device-side count AND the grid
+extern "C" int frp_nmpc_corridor_batch_view(const frp_nmpc_corridor *p, const frp_nmpc_corridor_cut *cut, void *stream)
+{
+    if (!p || !p->cloud_count || p->cloud_per_planner) return FRP_ERR_ARG;
+    return corridor_launch(p, cut, stream, true);
 }

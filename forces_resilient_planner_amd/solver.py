@@ -131,6 +131,13 @@ class OccMapRender(ctypes.Structure):  # frp_nmpc_occmap_render (include/frp_nmp
                 ("depth", ctypes.c_void_p), ("voxel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class OccMapSharedView(ctypes.Structure):  # frp_nmpc_occmap_shared_view (include/frp_nmpc_occmap_view.h)
+    _fields_ = [("cap", ctypes.c_int), ("cell", ctypes.c_double), ("dims", ctypes.c_int * 3),
+                ("cloud", ctypes.c_void_p), ("count", ctypes.c_void_p), ("total", ctypes.c_void_p),
+                ("grid_points", ctypes.c_void_p), ("grid_index", ctypes.c_void_p), ("grid_start", ctypes.c_void_p),
+                ("cursor", ctypes.c_void_p), ("group_sums", ctypes.c_void_p)]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -162,6 +169,12 @@ OCCMAP_FUSE_REFUSED = -256      # FRP_OCCMAP_FUSE_REFUSED: status[f][0] of a fra
 
 # section (8)'s fifth header (include/frp_nmpc_occmap_render.h): depth images rendered from the map, camera poses from planner states
 RENDER_EXPORTS = ["frp_nmpc_occmap_render_depth", "frp_nmpc_occmap_camera_poses"]
+
+# section (8)'s sixth header (include/frp_nmpc_occmap_view.h): the shared view rebuilt on the device, and the corridor entry that takes it
+VIEW_EXPORTS = ["frp_nmpc_occmap_shared_view_dims", "frp_nmpc_occmap_shared_view_update", "frp_nmpc_corridor_batch_view"]
+CORRIDOR_MAX_CELLS = 1 << 22       # FRP_CORRIDOR_MAX_CELLS
+OCCMAP_VIEW_MAX_GROUPS = 1024      # FRP_OCCMAP_VIEW_MAX_GROUPS
+OCCMAP_VIEW_LAUNCHES = 5           # FRP_OCCMAP_VIEW_LAUNCHES
 
 # section (8)'s third header (include/frp_nmpc_occmap_check.h): the safety timer's checks, checked at load time like EXPORTS
 CHECK_EXPORTS = ["frp_nmpc_occmap_check_surround", "frp_nmpc_occmap_check_paths", "frp_nmpc_occmap_check_goals"]
@@ -302,7 +315,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + VIEW_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -322,6 +335,9 @@ def lib():
         l.frp_nmpc_occmap_fuse_depth_batch.argtypes = [pm, ctypes.POINTER(OccMapFuseBatch), vp, sz, vp, sz, vp]
         l.frp_nmpc_occmap_render_depth.argtypes = [pm, ctypes.POINTER(OccMapRender), vp, sz, vp]
         l.frp_nmpc_occmap_camera_poses.argtypes = [ctypes.c_int, vp, c_double_p, vp, vp]
+        l.frp_nmpc_occmap_shared_view_dims.argtypes = [pm, ctypes.c_double, ctypes.POINTER(ctypes.c_int * 3)]
+        l.frp_nmpc_occmap_shared_view_update.argtypes = [pm, ctypes.POINTER(OccMapSharedView), vp, sz, vp]
+        l.frp_nmpc_corridor_batch_view.argtypes = [ctypes.POINTER(Corridor), ctypes.POINTER(CorridorCut), vp]
         pb, ci, cd = ctypes.POINTER(OccMapBody), ctypes.c_int, ctypes.c_double
         l.frp_nmpc_occmap_check_surround.argtypes = [pm, pb, cd, ci, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_paths.argtypes = [pm, pb, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -970,6 +986,11 @@ class OccupancyMap:
         dims = tuple(max(1, int(np.ceil(m / float(cell)))) for m in self.map_size)
         return cloud, CloudGrid(cloud, cell, origin=self.origin, dims=dims, stream=stream)
 
+    def shared_view_device(self, cap=CORRIDOR_MAX_POINTS, cell=0.5):
+        """A SharedView of this map: the cloud and grid of shared_view() in persistent buffers of `cap` points, rebuilt by
+        SharedView.update() with nothing on the host.  The per-tick form of the shared-cloud route when the map changes every tick."""
+        return SharedView(self, cap, cell)
+
     def query(self, pos, local_box=None, planner=None, stream=None):
         """getVoxelState (occ_map.cpp:95-106) of pos [Q,3]: int32 [Q] device tensor, -1 outside the map, 0 free or outside the local
         map, 1 occupied.  local_box [.,6] of a local view with planner [Q] = its row per query (None: row 0)."""
@@ -1152,13 +1173,70 @@ class CloudGrid:
         s.synchronize()  # scratch may be freed
 
 
+class SharedViewGrid:
+    """The grid of a SharedView: CloudGrid's attributes (origin, dims, cell, points, index, start) over the view's persistent buffers.
+    It describes view.cloud[:view.count] as of the last update()."""
+
+    def __init__(self, origin, dims, cell, points, index, start):
+        self.origin, self.dims, self.cell, self.points, self.index, self.start = origin, dims, cell, points, index, start
+
+
+class SharedView:
+    """The whole-map obstacle cloud of an OccupancyMap and its uniform grid, resident on the device (frp_nmpc_occmap_shared_view_update):
+    cloud [cap,3] f64 whose first count[0] rows are local_view(None, cap).cloud[0, :n] to the bit, count / total [1] int32 (count =
+    min(total, cap); total = the map's occupied voxels), grid = a SharedViewGrid laid over the map (origin = the map's, dims =
+    ceil(map_size / cell)).  update() enqueues the rebuild -- five launches, no read-back, no allocation, capturable -- and the
+    corridor takes the view with the grid ON:  corridor_batch_device(None, ..., view=view, cut=...) / DeviceFleet.corridor /
+    full_tick(view=...).  Storage beyond count is never written and never read through the grid."""
+
+    def __init__(self, occmap, cap=CORRIDOR_MAX_POINTS, cell=0.5):
+        t = occmap.torch
+        self.map, self.cap, self.cell = occmap, int(cap), float(cell)
+        if not 1 <= self.cap <= CORRIDOR_MAX_POINTS:
+            raise ValueError(f"cap = {cap}: a shared cloud holds 1 .. FRP_CORRIDOR_MAX_POINTS = {CORRIDOR_MAX_POINTS} points")
+        dims = (ctypes.c_int * 3)()
+        m = occmap._map()
+        if lib().frp_nmpc_occmap_shared_view_dims(ctypes.byref(m), self.cell, ctypes.byref(dims)) != 0:
+            raise ValueError(f"cell = {cell}: not a positive finite size, or more than FRP_CORRIDOR_MAX_CELLS = {CORRIDOR_MAX_CELLS} cells over this map")
+        self.dims = tuple(int(v) for v in dims)
+        cells = self.dims[0] * self.dims[1] * self.dims[2]
+        dev = occmap.device
+        self.cloud = t.zeros((self.cap, 3), dtype=t.float64, device=dev)
+        self.count = t.zeros((1,), dtype=t.int32, device=dev)
+        self.total = t.zeros((1,), dtype=t.int32, device=dev)
+        self.grid = SharedViewGrid(occmap.origin, self.dims, self.cell, t.zeros((self.cap, 3), dtype=t.float64, device=dev),
+                                   t.zeros((self.cap,), dtype=t.int32, device=dev), t.zeros((cells + 1,), dtype=t.int32, device=dev))
+        self._cursor = t.zeros((cells,), dtype=t.int32, device=dev)
+        self._sums = t.zeros((OCCMAP_VIEW_MAX_GROUPS,), dtype=t.int32, device=dev)
+
+    def _args(self):
+        g = self.grid
+        return OccMapSharedView(self.cap, self.cell, (ctypes.c_int * 3)(*self.dims), self.cloud.data_ptr(), self.count.data_ptr(),
+                                self.total.data_ptr(), g.points.data_ptr(), g.index.data_ptr(), g.start.data_ptr(),
+                                self._cursor.data_ptr(), self._sums.data_ptr())
+
+    def update(self, stream=None):
+        """Rebuild cloud, count, total and grid from the map as it is on `stream` (torch's current stream when None).  Asynchronous."""
+        v = self._args()
+        self.map._call("frp_nmpc_occmap_shared_view_update", ctypes.byref(v), stream=stream)
+
+    def overflowed(self):
+        """Device bool [1]: the map held more occupied voxels than cap at the last update (the first cap in x, y, z order were kept)."""
+        return self.total > self.count
+
+
 def corridor_batch_device(cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b, poly_nfaces, poly_index, poly_count=None,
-                          cloud_count=None, consts=None, stream=None, grid=None, cut=None):
+                          cloud_count=None, consts=None, stream=None, grid=None, cut=None, view=None):
     """frp_nmpc_corridor_batch on device tensors.  cloud [P,3] (shared) or [B,P,3]; ref_pos [B,N,3]; ref_yaw [B,N];
     ellipsoid [B,N,3,3]; outputs poly_A [B,N,F,3], poly_b [B,N,F], poly_nfaces / poly_index [B,N] int32.
     cut (OccupancyMap.cut, a CorridorCut): frp_nmpc_corridor_batch_cut -- every planner sees only the points of the SHARED cloud
-    inside its own local box."""
+    inside its own local box.
+    view (a SharedView, with cloud = None and neither grid nor cloud_count): frp_nmpc_corridor_batch_view -- the view's cloud with its
+    device-side count AND its grid; combines with cut."""
     import torch
+    if view is not None:
+        assert cloud is None and grid is None and cloud_count is None, "view= brings its own cloud, grid and count"
+        cloud, grid, cloud_count = view.cloud, view.grid, view.count
     c = dict(CORRIDOR_DEFAULTS)
     c.update(consts or {})
     B, N, F, _ = poly_A.shape
@@ -1180,6 +1258,11 @@ def corridor_batch_device(cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b, po
     if cut is not None:
         assert per == 0, "the cut belongs to a shared cloud"
         assert getattr(cut, "_box", None) is None or cut._box.shape[0] == B, "one local_box row per planner"
+    if view is not None:
+        _check(lib().frp_nmpc_corridor_batch_view(ctypes.byref(cr), ctypes.byref(cut) if cut is not None else None, ctypes.c_void_p(s.cuda_stream)),
+               "frp_nmpc_corridor_batch_view")
+        return
+    if cut is not None:
         _check(lib().frp_nmpc_corridor_batch_cut(ctypes.byref(cr), ctypes.byref(cut), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_corridor_batch_cut")
         return
     _check(lib().frp_nmpc_corridor_batch(ctypes.byref(cr), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_corridor_batch")
@@ -1300,16 +1383,17 @@ class DeviceFleet:
         s = stream if stream is not None else self.torch.cuda.current_stream(self.solver.device)
         tube_batch_device(self.mpc_output, self.ellipsoid, consts, s)
 
-    def corridor(self, cloud, ref_pos, ref_yaw, consts=None, stream=None, cloud_count=None, grid=None, cut=None):
+    def corridor(self, cloud, ref_pos, ref_yaw, consts=None, stream=None, cloud_count=None, grid=None, cut=None, view=None):
         """polytopes and poly_indices of all B planners from the obstacle cloud, the stage
         references and the current tube (getSikangConst, nmpc_solver.cpp:288-332) -> self.poly_*, on the device.
-        cut: OccupancyMap.cut(local_box) with the shared cloud and grid of OccupancyMap.shared_view()."""
+        cut: OccupancyMap.cut(local_box) with the shared cloud and grid of OccupancyMap.shared_view().
+        view: a SharedView in place of cloud / grid / cloud_count (cloud = None); combines with cut."""
         t = self.torch
         assert self.NPOLY == self.N
         if self.poly_index is None:
             self.poly_index = t.zeros((self.B, self.N), dtype=t.int32, device=self.solver.device)
         corridor_batch_device(cloud, ref_pos, ref_yaw, self.ellipsoid, self.poly_A, self.poly_b, self.poly_nfaces,
-                              self.poly_index, self.poly_count, cloud_count, consts, stream, grid, cut)
+                              self.poly_index, self.poly_count, cloud_count, consts, stream, grid, cut, view)
 
     def overflowed(self):
         """Planners whose last corridor() truncated a polytope to F rows (device tensor of bool; all False before the first
@@ -1386,19 +1470,22 @@ class DeviceFleet:
         return ok
 
     def full_tick(self, external_acc, kino_path, time_offset, cloud, ref_pos, ref_yaw, stream=None, replan=None,
-                  kino_size=None, tube_consts=None, corridor_consts=None, Ts=0.05, coldstart=True, state=None, grid=None, cloud_count=None, cut=None):
+                  kino_size=None, tube_consts=None, corridor_consts=None, Ts=0.05, coldstart=True, state=None, grid=None, cloud_count=None, cut=None,
+                  view=None):
         """The reference's whole per-tick computation downstream of the A* (NMPCSolver::solveNMPC,
         nmpc_solver.cpp:351-482) for B planners, asynchronous on `stream`, nothing touching the host:
         stage references (f-4) -> tube (f-2) -> corridor (f-3) -> parameter packing (f-1) -> NLP solve -> result
         bookkeeping.  ref_pos [B,N,3] / ref_yaw [B,N] are caller-owned scratch that receives the references.
         With coldstart (default) planners whose previous solve failed first restart from the constant plan (:363-364).
         cloud [B,P,3] with cloud_count [B]: per-planner clouds, as OccupancyMap.local_view exports them; or the shared cloud and grid
-        of OccupancyMap.shared_view() with cut = OccupancyMap.cut(local_box): the same polytopes without the per-planner copies."""
+        of OccupancyMap.shared_view() with cut = OccupancyMap.cut(local_box): the same polytopes without the per-planner copies; or
+        cloud = None and view = a SharedView (OccupancyMap.shared_view_device) updated on this stream, with the same cut: the same
+        again for a map that changes every tick."""
         if coldstart:
             self.coldstart(state, True, stream=stream)
         self.references(kino_path, time_offset, ref_pos, ref_yaw, replan, kino_size, Ts, stream)
         self.tube(tube_consts, stream)
-        self.corridor(cloud, ref_pos, ref_yaw, corridor_consts, stream, cloud_count=cloud_count, grid=grid, cut=cut)
+        self.corridor(cloud, ref_pos, ref_yaw, corridor_consts, stream, cloud_count=cloud_count, grid=grid, cut=cut, view=view)
         self.pack(external_acc, ref_pos, ref_yaw, stream)
         self.solver.solve(stream)
         self.update(stream)

@@ -568,6 +568,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * version. */
 #include "frp_nmpc_occmap_render.h"
 
+/* The shared view rebuilt on the device: the whole-map cloud and its uniform grid in fixed-capacity buffers, every count read from
+ * device memory, and the corridor entry point that takes them with the grid on.  A header of its own, part of this section and of
+ * this ABI version. */
+#include "frp_nmpc_occmap_view.h"
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 
