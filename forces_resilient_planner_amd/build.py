@@ -7,10 +7,11 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfrp_nmpc_amd.so")
-SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_view.hip"]
-HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
+SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_view.hip"]
+HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_batch.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_check.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_occmap_render.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_view.h")]
+           os.path.join(ROOT, "include", "frp_nmpc_occmap_render.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_view.h"),
+           os.path.join(ROOT, "include", "frp_nmpc_corridor_large.h")]
 
 
 def hipcc():
@@ -110,6 +111,8 @@ PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS + ["-DFRP_LDS_SPLIT_TU"],
                     "frp_ipm_lds_q30.hip": CODEGEN_FLAGS,
                     "frp_ipm_lds_s2.hip": CODEGEN_FLAGS + ["-DFRP_INLINE_FACTOR", "-DFRP_INLINE_SWEEPS"],
                     "frp_corridor.hip": NO_HOIST,
+                    # the same scans over a list in device memory: the flags of the kernels it shares its text with
+                    "frp_corridor_large.hip": NO_HOIST,
                     # the A* agrees with its oracle to the bit (node order depends on comparisons of nearly equal costs): no a * b + c contraction
                     "frp_astar.hip": ["-ffp-contract=off"],
                     # the map's indices and voxel centres are the reference's operations, one rounding each: origin + (id + 0.5) * resolution is no FMA

@@ -221,12 +221,15 @@ int frp_nmpc_occmap_shared_view_dims(const frp_nmpc_occmap *m, double cell, int 
     return FRP_OK;
 }
 
-int frp_nmpc_occmap_shared_view_update(const frp_nmpc_occmap *m, const frp_nmpc_occmap_shared_view *v, void *workspace, size_t workspace_bytes,
-                                       void *stream)
+// The five launches for a view of at most max_cap points.  Nothing in the kernels above depends on the capacity's size: every position
+// (at, base, count, the grid's start / cursor / index entries) is a 32-bit int below 2^22, and every byte offset is taken as
+// 3 * (size_t)at -- so the large entry (include/frp_nmpc_corridor_large.h) is this function with another bound.
+static int shared_view_update(const frp_nmpc_occmap *m, const frp_nmpc_occmap_shared_view *v, void *workspace, size_t workspace_bytes, void *stream,
+                              int max_cap)
 {
     using namespace frp::occmap;
     if (!args_ok(m, workspace, workspace_bytes) || !v) return FRP_ERR_ARG;
-    if (v->cap < 1 || v->cap > FRP_CORRIDOR_MAX_POINTS) return FRP_ERR_ARG;
+    if (v->cap < 1 || v->cap > max_cap) return FRP_ERR_ARG;
     int d[3];
     if (!view_dims(m, v->cell, d) || d[0] != v->dims[0] || d[1] != v->dims[1] || d[2] != v->dims[2]) return FRP_ERR_ARG;
     if (!v->cloud || !v->count || !v->total || !v->grid_points || !v->grid_index || !v->grid_start || !v->cursor || !v->group_sums) return FRP_ERR_ARG;
@@ -251,6 +254,18 @@ int frp_nmpc_occmap_shared_view_update(const frp_nmpc_occmap *m, const frp_nmpc_
     hipLaunchKernelGGL(view_grid_scan_kernel, dim3(1), dim3(1024), 0, st, s);
     hipLaunchKernelGGL(view_grid_scatter_kernel, dim3(256), dim3(SV_THREADS), 0, st, g, s);
     return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+}
+
+int frp_nmpc_occmap_shared_view_update(const frp_nmpc_occmap *m, const frp_nmpc_occmap_shared_view *v, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return shared_view_update(m, v, workspace, workspace_bytes, stream, FRP_CORRIDOR_MAX_POINTS);
+}
+
+int frp_nmpc_occmap_shared_view_update_large(const frp_nmpc_occmap *m, const frp_nmpc_occmap_shared_view *v, void *workspace,
+                                             size_t workspace_bytes, void *stream)
+{
+    return shared_view_update(m, v, workspace, workspace_bytes, stream, FRP_CORRIDOR_LARGE_MAX_POINTS);
 }
 
 } // extern "C"

@@ -138,6 +138,10 @@ class OccMapSharedView(ctypes.Structure):  # frp_nmpc_occmap_shared_view (includ
                 ("cursor", ctypes.c_void_p), ("group_sums", ctypes.c_void_p)]
 
 
+class CorridorLarge(ctypes.Structure):  # frp_nmpc_corridor_large (include/frp_nmpc_corridor_large.h)
+    _fields_ = [("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("overflow", ctypes.c_void_p)]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -175,6 +179,12 @@ VIEW_EXPORTS = ["frp_nmpc_occmap_shared_view_dims", "frp_nmpc_occmap_shared_view
 CORRIDOR_MAX_CELLS = 1 << 22       # FRP_CORRIDOR_MAX_CELLS
 OCCMAP_VIEW_MAX_GROUPS = 1024      # FRP_OCCMAP_VIEW_MAX_GROUPS
 OCCMAP_VIEW_LAUNCHES = 5           # FRP_OCCMAP_VIEW_LAUNCHES
+
+# section (8)'s seventh header (include/frp_nmpc_corridor_large.h): shared clouds beyond CORRIDOR_MAX_POINTS
+LARGE_EXPORTS = ["frp_nmpc_corridor_large_workspace_bytes", "frp_nmpc_corridor_batch_large", "frp_nmpc_occmap_shared_view_update_large"]
+CORRIDOR_LARGE_MAX_POINTS = 1 << 22  # FRP_CORRIDOR_LARGE_MAX_POINTS
+CORRIDOR_LARGE_LIST = 65536          # FRP_CORRIDOR_LARGE_LIST
+CORRIDOR_LARGE_GROUPS = 512          # FRP_CORRIDOR_LARGE_GROUPS
 
 # section (8)'s third header (include/frp_nmpc_occmap_check.h): the safety timer's checks, checked at load time like EXPORTS
 CHECK_EXPORTS = ["frp_nmpc_occmap_check_surround", "frp_nmpc_occmap_check_paths", "frp_nmpc_occmap_check_goals"]
@@ -315,7 +325,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + VIEW_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -338,6 +348,10 @@ def lib():
         l.frp_nmpc_occmap_shared_view_dims.argtypes = [pm, ctypes.c_double, ctypes.POINTER(ctypes.c_int * 3)]
         l.frp_nmpc_occmap_shared_view_update.argtypes = [pm, ctypes.POINTER(OccMapSharedView), vp, sz, vp]
         l.frp_nmpc_corridor_batch_view.argtypes = [ctypes.POINTER(Corridor), ctypes.POINTER(CorridorCut), vp]
+        l.frp_nmpc_corridor_large_workspace_bytes.restype = ctypes.c_size_t
+        l.frp_nmpc_corridor_large_workspace_bytes.argtypes = [ctypes.c_int]
+        l.frp_nmpc_corridor_batch_large.argtypes = [ctypes.POINTER(Corridor), ctypes.POINTER(CorridorCut), ctypes.POINTER(CorridorLarge), vp]
+        l.frp_nmpc_occmap_shared_view_update_large.argtypes = [pm, ctypes.POINTER(OccMapSharedView), vp, sz, vp]
         pb, ci, cd = ctypes.POINTER(OccMapBody), ctypes.c_int, ctypes.c_double
         l.frp_nmpc_occmap_check_surround.argtypes = [pm, pb, cd, ci, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_paths.argtypes = [pm, pb, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -986,10 +1000,12 @@ class OccupancyMap:
         dims = tuple(max(1, int(np.ceil(m / float(cell)))) for m in self.map_size)
         return cloud, CloudGrid(cloud, cell, origin=self.origin, dims=dims, stream=stream)
 
-    def shared_view_device(self, cap=CORRIDOR_MAX_POINTS, cell=0.5):
+    def shared_view_device(self, cap=CORRIDOR_MAX_POINTS, cell=0.5, planners=4096):
         """A SharedView of this map: the cloud and grid of shared_view() in persistent buffers of `cap` points, rebuilt by
-        SharedView.update() with nothing on the host.  The per-tick form of the shared-cloud route when the map changes every tick."""
-        return SharedView(self, cap, cell)
+        SharedView.update() with nothing on the host.  The per-tick form of the shared-cloud route when the map changes every tick.
+        cap may exceed CORRIDOR_MAX_POINTS, up to CORRIDOR_LARGE_MAX_POINTS: a LARGE view, for at most `planners` planners per
+        corridor call (see SharedView)."""
+        return SharedView(self, cap, cell, planners)
 
     def query(self, pos, local_box=None, planner=None, stream=None):
         """getVoxelState (occ_map.cpp:95-106) of pos [Q,3]: int32 [Q] device tensor, -1 outside the map, 0 free or outside the local
@@ -1187,13 +1203,23 @@ class SharedView:
     min(total, cap); total = the map's occupied voxels), grid = a SharedViewGrid laid over the map (origin = the map's, dims =
     ceil(map_size / cell)).  update() enqueues the rebuild -- five launches, no read-back, no allocation, capturable -- and the
     corridor takes the view with the grid ON:  corridor_batch_device(None, ..., view=view, cut=...) / DeviceFleet.corridor /
-    full_tick(view=...).  Storage beyond count is never written and never read through the grid."""
+    full_tick(view=...).  Storage beyond count is never written and never read through the grid.
+    cap > CORRIDOR_MAX_POINTS (up to CORRIDOR_LARGE_MAX_POINTS) makes a LARGE view (include/frp_nmpc_corridor_large.h): update() is
+    frp_nmpc_occmap_shared_view_update_large, and the corridor entries route to frp_nmpc_corridor_batch_large.  Such a view owns what
+    that call needs, allocated here once: the fallback's workspace for min(planners, CORRIDOR_LARGE_GROUPS) lists (256 KB each) and
+    overflow, int32 [planners] -- after a corridor call of B <= planners planners overflow[:B] is 1 where a local box held more than
+    CORRIDOR_LARGE_LIST points (that planner's result is the refusal marker: poly_count = INT_MIN, poly_nfaces = poly_index = 0) and 0
+    elsewhere.  At or below CORRIDOR_MAX_POINTS nothing changes: overflow is None and the existing calls are used."""
 
-    def __init__(self, occmap, cap=CORRIDOR_MAX_POINTS, cell=0.5):
+    def __init__(self, occmap, cap=CORRIDOR_MAX_POINTS, cell=0.5, planners=4096):
         t = occmap.torch
         self.map, self.cap, self.cell = occmap, int(cap), float(cell)
-        if not 1 <= self.cap <= CORRIDOR_MAX_POINTS:
-            raise ValueError(f"cap = {cap}: a shared cloud holds 1 .. FRP_CORRIDOR_MAX_POINTS = {CORRIDOR_MAX_POINTS} points")
+        if not 1 <= self.cap <= CORRIDOR_LARGE_MAX_POINTS:
+            raise ValueError(f"cap = {cap}: a shared cloud holds 1 .. FRP_CORRIDOR_LARGE_MAX_POINTS = {CORRIDOR_LARGE_MAX_POINTS} points")
+        self.large = self.cap > CORRIDOR_MAX_POINTS
+        self.planners = int(planners)
+        if self.large and self.planners < 1:
+            raise ValueError(f"planners = {planners}: a large view serves at least one planner")
         dims = (ctypes.c_int * 3)()
         m = occmap._map()
         if lib().frp_nmpc_occmap_shared_view_dims(ctypes.byref(m), self.cell, ctypes.byref(dims)) != 0:
@@ -1208,6 +1234,16 @@ class SharedView:
                                    t.zeros((self.cap,), dtype=t.int32, device=dev), t.zeros((cells + 1,), dtype=t.int32, device=dev))
         self._cursor = t.zeros((cells,), dtype=t.int32, device=dev)
         self._sums = t.zeros((OCCMAP_VIEW_MAX_GROUPS,), dtype=t.int32, device=dev)
+        self.overflow = self._workspace = None
+        if self.large:
+            self._workspace = t.zeros((int(lib().frp_nmpc_corridor_large_workspace_bytes(self.planners)),), dtype=t.uint8, device=dev)
+            self.overflow = t.zeros((self.planners,), dtype=t.int32, device=dev)
+
+    def _large_args(self, B):
+        """frp_nmpc_corridor_large for a corridor call of B planners through this (large) view."""
+        if B > self.planners:
+            raise ValueError(f"{B} planners through a large view made for planners = {self.planners}")
+        return CorridorLarge(self._workspace.data_ptr(), self._workspace.numel(), self.overflow.data_ptr())
 
     def _args(self):
         g = self.grid
@@ -1218,7 +1254,7 @@ class SharedView:
     def update(self, stream=None):
         """Rebuild cloud, count, total and grid from the map as it is on `stream` (torch's current stream when None).  Asynchronous."""
         v = self._args()
-        self.map._call("frp_nmpc_occmap_shared_view_update", ctypes.byref(v), stream=stream)
+        self.map._call("frp_nmpc_occmap_shared_view_update_large" if self.large else "frp_nmpc_occmap_shared_view_update", ctypes.byref(v), stream=stream)
 
     def overflowed(self):
         """Device bool [1]: the map held more occupied voxels than cap at the last update (the first cap in x, y, z order were kept)."""
@@ -1232,7 +1268,8 @@ def corridor_batch_device(cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b, po
     cut (OccupancyMap.cut, a CorridorCut): frp_nmpc_corridor_batch_cut -- every planner sees only the points of the SHARED cloud
     inside its own local box.
     view (a SharedView, with cloud = None and neither grid nor cloud_count): frp_nmpc_corridor_batch_view -- the view's cloud with its
-    device-side count AND its grid; combines with cut."""
+    device-side count AND its grid; combines with cut.  A large view (view.cap > CORRIDOR_MAX_POINTS) goes to
+    frp_nmpc_corridor_batch_large with the view's workspace; view.overflow[:B] then tells which planners it refused."""
     import torch
     if view is not None:
         assert cloud is None and grid is None and cloud_count is None, "view= brings its own cloud, grid and count"
@@ -1258,6 +1295,11 @@ def corridor_batch_device(cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b, po
     if cut is not None:
         assert per == 0, "the cut belongs to a shared cloud"
         assert getattr(cut, "_box", None) is None or cut._box.shape[0] == B, "one local_box row per planner"
+    if view is not None and view.cap > CORRIDOR_MAX_POINTS:
+        w = view._large_args(B)
+        _check(lib().frp_nmpc_corridor_batch_large(ctypes.byref(cr), ctypes.byref(cut) if cut is not None else None, ctypes.byref(w),
+                                                   ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_corridor_batch_large")
+        return
     if view is not None:
         _check(lib().frp_nmpc_corridor_batch_view(ctypes.byref(cr), ctypes.byref(cut) if cut is not None else None, ctypes.c_void_p(s.cuda_stream)),
                "frp_nmpc_corridor_batch_view")

@@ -374,7 +374,7 @@ int frp_nmpc_corridor_batch(const frp_nmpc_corridor *p, void *stream);
  *       (max_k |origin[k]| + max_k map_size[k]) * 2^-23 < resolution / 2
  * (0.1 m voxels: maps up to 400 km from the origin).  Any other double cloud is cut by position, as stated.
  * A shared cloud holds at most FRP_CORRIDOR_MAX_POINTS points (the LDS masks of the plain-cloud kernel); a map with more occupied
- * voxels keeps using per-planner clouds. */
+ * voxels keeps using per-planner clouds, or takes the entries of frp_nmpc_corridor_large.h. */
 typedef struct frp_nmpc_corridor_cut {
     const int *box;     /* [B][6] device: min_id(3), max_id(3) -- frp_nmpc_occmap_view.local_box */
     double origin[3];   /* frp_nmpc_occmap.origin */
@@ -572,6 +572,10 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * device memory, and the corridor entry point that takes them with the grid on.  A header of its own, part of this section and of
  * this ABI version. */
 #include "frp_nmpc_occmap_view.h"
+
+/* Shared clouds beyond FRP_CORRIDOR_MAX_POINTS: the corridor chain and the device-built view for up to FRP_CORRIDOR_LARGE_MAX_POINTS
+ * points, beside the entries above, which keep their limit.  A header of its own, part of this section and of this ABI version. */
+#include "frp_nmpc_corridor_large.h"
 
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
