@@ -661,6 +661,7 @@ bool frp::corridor_args_ok(const frp_nmpc_corridor *p, const frp_nmpc_corridor_c
         (p->P > 0 && !p->cloud) || !p->ref_pos || !p->ref_yaw || !p->ellipsoid || !p->poly_A || !p->poly_b || !p->poly_nfaces || !p->poly_index)
         return false;
     if (!(p->seed_len > 0.0) || !(p->inflation >= 0.0)) return false;
+    if (!(p->offset_x > -0.5 * p->seed_len)) return false; // at or below, the seed ellipsoid's matrix is singular or negative and find_ellipsoid's loops do not end
     if (p->grid_start && (!p->grid_points || !p->grid_index || !(p->grid_cell > 0.0) || p->grid_dims[0] < 1 || p->grid_dims[1] < 1 || p->grid_dims[2] < 1 ||
                           p->cloud_per_planner))
         return false;

@@ -329,7 +329,11 @@ typedef struct frp_nmpc_corridor {
     double bbox[3];         /* set_local_bbox(Vec3f(2, 2, 1)) (:323)                                                */
     double seed_len;        /* 0.1: second seed point ahead along the yaw (:318)                                    */
     double inflation;       /* 1.1: "with little inflation" (:302)                                                  */
-    double offset_x;        /* 0: dilate()'s offset on the long semi-axis (ellipsoid_decomp.h:67)                   */
+    double offset_x;        /* 0: dilate()'s offset on the long semi-axis (ellipsoid_decomp.h:67).  With f = seed_len / 2
+                               and r = f / (f + offset_x) the seed ellipsoid has semi-axes (f, f r, f r) along the
+                               heading: a sphere at 0, prolate above, an oblate disc below.  Domain: offset_x >
+                               -seed_len / 2 (at or below, the seed matrix is singular or negative and the reference's
+                               loops do not end): anything else is FRP_ERR_ARG                                         */
     /* outputs = the polytope inputs of frp_nmpc_pack (NPOLY = N)                                                   */
     double *poly_A;         /* [B][N][F][3]  LinearConstraint3D::A_ of polytope k (rows beyond F are not stored)    */
     double *poly_b;         /* [B][N][F]                                                                            */

@@ -22,10 +22,20 @@ numpy restatement of what NMPCSolver::getSikangConst does for every stage of the
     vec3_to_rotation                  decomp_geometry/geometric_utils.h:27-35
     epsilon_ = 1e-10                  decomp_basis/data_type.h:129
 
-PARITY UNPINNED: DecompROS is header-only C++ over Eigen, and Eigen is not in this image, so the reference code
-cannot be compiled or run here; it ships no test vectors for this path.  The restatement keeps the reference's order
-of operations (order-preserving point lists, first-minimum tie breaking, the same thresholds) and the GPU kernel is
+PARITY: DecompROS is header-only C++ over Eigen, and Eigen is not in this image, so the reference code cannot be
+compiled or run here; it ships no test vectors for this path.  The restatement keeps the reference's order of
+operations (order-preserving point lists, first-minimum tie breaking, the same thresholds) and the GPU kernel is
 tested against it: identical polytope indices and row counts, rows within 1e-9.
+
+PINNED TO THE MATHEMATICS where no in-box obstacle lies inside the seed ellipsoid (the production regime; find_ellipsoid
+then returns the seed as it is): tests/golden/corridor_mp.npz holds a 50-digit evaluation of the geometry
+(tests/tools/gen_corridor_mp.py, written from the definitions and not from this file) for spherical, prolate and oblate
+seeds (offset_x = 0, > 0, < 0) and worlds turned about z, and tests/test_corridor_mp_cpu.py holds corridor_one to it on
+every planner whose discrete decisions all have more than 1e-7 to spare: same indices, face counts and row order, rows
+within 1e-9.  STILL UNPINNED: the transcription of find_ellipsoid's two shrink loops (obstacles inside the seed).
+
+offset_x (dilate()'s offset on the long semi-axis): with f = |p2 - p1| / 2 and r = f / (f + offset_x) the seed ellipsoid
+has semi-axes (f, f r, f r) along p2 - p1.  Domain: offset_x > -f.
 """
 import numpy as np
 
@@ -107,14 +117,14 @@ def find_ellipsoid(p1, p2, obs_, offset_x=0.0):  # line_segment.h:136-211; retur
     return C, d
 
 
-def decompose(p1, p2, cloud, bbox):
-    """LineSegment(p1, p2): set_local_bbox, set_obs, dilate(0), then LinearConstraint((p1+p2)/2, planes).
+def decompose(p1, p2, cloud, bbox, offset_x=0.0):
+    """LineSegment(p1, p2): set_local_bbox, set_obs, dilate(offset_x), then LinearConstraint((p1+p2)/2, planes).
     Returns (A [m,3], b [m])."""
     box = local_bbox_planes(p1, p2, bbox)
     obs_ = cloud
     for (pp, n) in box:  # Polyhedron::inside: rejected if signed_dist > epsilon_ (polyhedron.h:51-58)
         obs_ = obs_[(obs_ - pp) @ n <= EPS]
-    C, d = find_ellipsoid(p1, p2, obs_)
+    C, d = find_ellipsoid(p1, p2, obs_, offset_x)
     planes = []
     remain = obs_
     Ci = np.linalg.inv(C)
@@ -135,7 +145,7 @@ def decompose(p1, p2, cloud, bbox):
     return A, b
 
 
-def corridor_one(ref_pos, ref_yaw, E, cloud, bbox=(2.0, 2.0, 1.0), seed_len=0.1, inflation=1.1):
+def corridor_one(ref_pos, ref_yaw, E, cloud, bbox=(2.0, 2.0, 1.0), seed_len=0.1, inflation=1.1, offset_x=0.0):
     """One planner, one tick: the getSikangConst calls of NMPCSolver::setFORCESParams (nmpc_solver.cpp:515).
     ref_pos [N,3], ref_yaw [N], E [N,3,3], cloud [P,3].  Returns (poly_index [N], list of (A, b))."""
     bbox = np.asarray(bbox, float)
@@ -153,6 +163,6 @@ def corridor_one(ref_pos, ref_yaw, E, cloud, bbox=(2.0, 2.0, 1.0), seed_len=0.1,
         if not reuse:
             p1 = np.array(ref_pos[i], float)
             p2 = p1 + np.array([seed_len * np.cos(ref_yaw[i]), seed_len * np.sin(ref_yaw[i]), 0.0])
-            polys.append(decompose(p1, p2, cloud, bbox))
+            polys.append(decompose(p1, p2, cloud, bbox, offset_x))
         index.append(len(polys) - 1)
     return np.array(index, dtype=np.int32), polys
