@@ -618,29 +618,32 @@ done:
     return status;
 }
 
-/* getKinoTraj (:648-695) on a result: the search part backwards from the last node, reversed, then the shot */
+/* getKinoTraj (:648-695) on a result: the search part backwards from the last node, reversed, then the shot.  At most `cap` samples
+ * are stored -- the FIRST cap of the forward path, the contract of include/frp_nmpc.h ("more than K samples: the first K are kept")
+ * -- and the count returned is the untruncated one.  The search part is counted first so that every backward sample lands at its
+ * forward position; the shot's duplicate test reads the previous sample only while that one is stored (n <= cap). */
 int orc_astar_kino_traj(const orc_astar_params *P, const double external_acc[3], const orc_astar_result *r, double delta_t, double *pts, int cap)
 {
     Search Sv;
     memset(&Sv, 0, sizeof Sv);
     Sv.P = P;
     memcpy(Sv.external_acc, external_acc, sizeof Sv.external_acc);
-    int n = 0;
-    double *tmp = (double *)malloc((size_t)cap * 3 * sizeof(double));
+    int total = 0;
+    for (int q = r->n_path - 1; q >= 1; q--)
+        for (double t = r->path_duration[q]; t >= -1e-5; t -= delta_t) total++;
+    int w = 0; /* index in the reference's backward order */
     for (int q = r->n_path - 1; q >= 1; q--) { /* node = path_nodes_[q], node->parent = path_nodes_[q - 1] */
         const double *ut = r->path_input[q], *x0 = r->path_state[q - 1];
         const double duration = r->path_duration[q];
         for (double t = duration; t >= -1e-5; t -= delta_t) {
             double xt[6];
             state_transit(&Sv, x0, xt, ut, t);
-            if (n < cap) { tmp[3 * n] = xt[0]; tmp[3 * n + 1] = xt[1]; tmp[3 * n + 2] = xt[2]; }
-            n++;
+            const int pos = total - 1 - w;
+            if (pos < cap) { pts[3 * pos] = xt[0]; pts[3 * pos + 1] = xt[1]; pts[3 * pos + 2] = xt[2]; }
+            w++;
         }
     }
-    const int ns = n < cap ? n : cap;
-    for (int i = 0; i < ns; i++) memcpy(pts + 3 * i, tmp + 3 * (ns - 1 - i), 3 * sizeof(double)); /* reverse */
-    free(tmp);
-    n = ns;
+    int n = total;
     if (r->is_shot_succ) {
         for (double t = delta_t; t <= r->t_shot; t += delta_t) {
             const double tt[4] = {1.0, t, t * t, t * t * t};
@@ -687,6 +690,23 @@ int orc_astar_replay(const orc_astar_params *P, const double external_acc[3], co
         memcpy(cur, nx, sizeof cur);
     }
     return -1;
+}
+
+/* Test helpers: the closed forms above, callable on their own (tests/test_oracle_astar_mp.py pins them to the mathematics). */
+int orc_astar_quartic(double a, double b, double c, double d, double e, double roots[4]) { return quartic(a, b, c, d, e, roots); }
+double orc_astar_heuristic(const orc_astar_params *P, const double x1[6], const double x2[6], double *t_opt)
+{
+    Search Sv;
+    memset(&Sv, 0, sizeof Sv);
+    Sv.P = P;
+    return estimate_heuristic(&Sv, x1, x2, t_opt);
+}
+void orc_astar_transit(const double ext[3], const double s0[6], const double um[3], double tau, double s1[6])
+{
+    Search Sv;
+    memset(&Sv, 0, sizeof Sv);
+    memcpy(Sv.external_acc, ext, sizeof Sv.external_acc);
+    state_transit(&Sv, s0, s1, um, tau);
 }
 
 /* NMPCSolver::getKinoPath's search part (nmpc_solver.cpp:154-207): search with the continuous initial state (init = true), on

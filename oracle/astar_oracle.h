@@ -53,6 +53,11 @@ int orc_astar_search(const orc_astar_params *P, const double start_pt[3], const 
                      const double end_pt[3], const double end_v[3], int init, const double external_acc[3], orc_astar_result *out);
 int orc_astar_kino_traj(const orc_astar_params *P, const double external_acc[3], const orc_astar_result *r, double delta_t, double *pts, int cap);
 int orc_astar_replay(const orc_astar_params *P, const double external_acc[3], const orc_astar_result *r);
+/* test helpers: quartic() (number of roots, in the reference's order), estimateHeuristic (only max_vel, w_time, tie_breaker of P are
+ * read) and stateTransit under the external acceleration ext */
+int orc_astar_quartic(double a, double b, double c, double d, double e, double roots[4]);
+double orc_astar_heuristic(const orc_astar_params *P, const double x1[6], const double x2[6], double *t_opt);
+void orc_astar_transit(const double ext[3], const double s0[6], const double um[3], double tau, double s1[6]);
 int orc_astar_plan(const orc_astar_params *P, const double start_pt[3], const double start_v[3], const double start_a[3],
                    const double end_pt[3], const double end_v[3], int init, const double external_acc[3], double Ts,
                    double *kino_path, int cap, int *kino_size, orc_astar_result *res, int *retried, const double *retry_pt, const double *retry_v);

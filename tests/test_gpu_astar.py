@@ -6,35 +6,13 @@ import pytest
 
 from forces_resilient_planner_amd import solver, workloads
 
+from . import astar_gpu_lib as AG
 from . import astar_lib as AL
 
 pytestmark = pytest.mark.gpu
 
 
-def _run_gpu(world, q, B, K=2048, active=None, planner=None, init=True):
-    import torch
-    pl = planner or solver.AstarPlanner(world, B, K=K, want_path_nodes=True)
-    pl.upload(q["start_pt"], q["start_v"], q["start_a"], q["end_pt"], q["end_v"], q["f_ext"])
-    pl.plan(init=init, active=active)
-    torch.cuda.synchronize()
-    return pl
-
-
-def _compare(pl, o, B):
-    st = pl.status.cpu().numpy(); sz = pl.kino_size.cpu().numpy(); stats = pl.stats.cpu().numpy()
-    kp = pl.kino_path.cpu().numpy(); pn = pl.path_nodes.cpu().numpy()
-    for b in range(B):
-        r = o["results"][b]
-        assert st[b] == o["status"][b], (b, st[b], o["status"][b])
-        assert stats[b, 0] == r.use_node_num and stats[b, 1] == r.iter_num and stats[b, 2] == o["retried"][b], (b, stats[b], r.use_node_num, r.iter_num)
-        if st[b] != solver.ASTAR_NO_PATH:
-            n = r.n_path
-            assert stats[b, 3] == n
-            assert [int(pn[b, i, 10]) for i in range(n)] == [r.path_node[i] for i in range(n)]  # identical node sequence
-            for i in range(n):
-                assert np.array_equal(pn[b, i, 0:6], np.array(r.path_state[i][:])) and np.array_equal(pn[b, i, 6:9], np.array(r.path_input[i][:]))
-            assert sz[b] == o["kino_size"][b]
-            assert np.array_equal(kp[b, :sz[b]], o["kino_path"][b, :sz[b]])  # (the required tolerance is 1e-12; the samples are identical)
+_run_gpu, _compare = AG.run_gpu, AG.compare
 
 
 @pytest.mark.parametrize("chunk", range(6))
