@@ -102,14 +102,11 @@ def check_device_code(obj):
         if m and m.group(1).upper().endswith("FF") and int(m.group(2), 16) == 0:
             raise RuntimeError(f"{obj}: miscompiled 64-bit scalar immediate (literal cut to 32 bits): {line.strip()}")
     return n
-PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS + ["-DFRP_LDS_SPLIT_TU"],
+PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS,  # (what else a solver unit is built with -- layout, inlined sweeps -- its own file states)
                     "frp_ipm_lds_mem.hip": MEM_FLAGS,
-                    # (the factorisation sweep inlined: as a function of its own it saves and restores 38 callee-saved registers per call
-                    # whether or not the caller holds anything in them -- 0.858 -> 0.853 ms per 4096-problem launch; inlining the
-                    # vector sweeps as well loses that again, profiles/r05_q4_flags.txt)
-                    "frp_ipm_lds_q4.hip": CODEGEN_FLAGS + ["-DFRP_INLINE_FACTOR"],
+                    "frp_ipm_lds_q4.hip": CODEGEN_FLAGS,
                     "frp_ipm_lds_q30.hip": CODEGEN_FLAGS,
-                    "frp_ipm_lds_s2.hip": CODEGEN_FLAGS + ["-DFRP_INLINE_FACTOR", "-DFRP_INLINE_SWEEPS"],
+                    "frp_ipm_lds_s2.hip": CODEGEN_FLAGS,
                     "frp_corridor.hip": NO_HOIST,
                     # the same scans over a list in device memory: the flags of the kernels it shares its text with
                     "frp_corridor_large.hip": NO_HOIST,
@@ -133,11 +130,10 @@ PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS + ["-DFRP_LDS_SPLIT_TU"],
 OBJDIR = os.path.join(PKG, "_build")
 
 
-def build_native(force=False, verbose=True, lib=None, extra_flags=(), solver_flags=None, objdir=None, check=True, mem_flags=None, q4_flags=None):
+def build_native(force=False, verbose=True, lib=None, extra_flags=(), objdir=None, check=True):
     """hipcc --offload-arch=gfx950 -> forces_resilient_planner_amd/libfrp_nmpc_amd.so (in-tree): one object per source
     (compiled in parallel, per-source flags), linked into the shared library.
-    Experiment builds (tools/build_variant.sh): `lib` = another output file, `extra_flags` for every source, `solver_flags`
-    in place of CODEGEN_FLAGS for the solver kernel's translation unit (e.g. [] = the compiler's defaults)."""
+    Profile builds (tools/build_variant.sh): `lib` = another output file, `extra_flags` for every source (-DFRP_PROFILE ...)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     deps = srcs + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
     variant = lib is not None
@@ -156,12 +152,6 @@ def build_native(force=False, verbose=True, lib=None, extra_flags=(), solver_fla
         flags = PER_SOURCE_FLAGS.get(name, [])
         if not trusted:
             flags = [f for i, f in enumerate(flags) if f != "-mllvm" and (i == 0 or flags[i - 1] != "-mllvm")]
-        if solver_flags is not None and name == "frp_ipm_lds.hip":
-            flags = list(solver_flags) + ["-DFRP_LDS_SPLIT_TU"]
-        if mem_flags is not None and name == "frp_ipm_lds_mem.hip":  # (experiments: the re-reading variants' translation unit)
-            flags = list(mem_flags)
-        if q4_flags is not None and name == "frp_ipm_lds_q4.hip":    # (experiments: the four-per-CU variants' translation unit)
-            flags = list(q4_flags)
         cmd = common + flags + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -179,10 +169,10 @@ def build_native(force=False, verbose=True, lib=None, extra_flags=(), solver_fla
     return lib
 
 
-def build_variant(name, extra_flags=(), solver_flags=None, verbose=False, check=True, mem_flags=None, q4_flags=None):
+def build_variant(name, extra_flags=(), verbose=False, check=True):
     """forces_resilient_planner_amd/lib_<name>.so: the product sources with extra flags (selected with FRP_LIB=...)."""
     return build_native(force=True, verbose=verbose, lib=os.path.join(PKG, f"lib_{name}.so"), extra_flags=extra_flags,
-                        solver_flags=solver_flags, objdir=os.path.join(OBJDIR, "variant_" + name), check=check, mem_flags=mem_flags, q4_flags=q4_flags)
+                        objdir=os.path.join(OBJDIR, "variant_" + name), check=check)
 
 
 DROPIN_DIR = os.path.join(PKG, "dropin", "lib")
@@ -233,7 +223,7 @@ def build_default_flags_lib(verbose=False):
     os.makedirs(d, exist_ok=True)
     obj = os.path.join(d, "frp_ipm_lds.hip.o")
     cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-           "-DFRP_LDS_SPLIT_TU", "-c", src, "-o", obj]
+           "-c", src, "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
@@ -271,24 +261,9 @@ def build_oracle(verbose=True):
 
 if __name__ == "__main__":
     import sys
-    if len(sys.argv) > 2 and sys.argv[1] == "variant":  # python -m forces_resilient_planner_amd.build variant <name> [--solver-flags=...] [flags...]
-        sf = None
-        mf = None
-        qf = None
-        rest = []
-        chk = True
-        for a_ in sys.argv[3:]:
-            if a_.startswith("--solver-flags="):
-                sf = a_.split("=", 1)[1].split()
-            elif a_.startswith("--mem-flags="):
-                mf = a_.split("=", 1)[1].split()
-            elif a_.startswith("--q4-flags="):
-                qf = a_.split("=", 1)[1].split()
-            elif a_ == "--no-check":
-                chk = False
-            else:
-                rest.append(a_)
-        print(build_variant(sys.argv[2], rest, sf, check=chk, mem_flags=mf, q4_flags=qf))
+    if len(sys.argv) > 2 and sys.argv[1] == "variant":  # python -m forces_resilient_planner_amd.build variant <name> [--no-check] [flags...]
+        rest = [a_ for a_ in sys.argv[3:] if a_ != "--no-check"]
+        print(build_variant(sys.argv[2], rest, check="--no-check" not in sys.argv[3:]))
     else:
         build_native(force=True)
         build_ubench()

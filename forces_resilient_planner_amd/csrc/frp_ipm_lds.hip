@@ -30,121 +30,76 @@
 #include "frp_kernels.h"
 #include "frp_device.hpp"
 
-// (the Q4 translation unit instantiates the same templates on another record layout: a namespace of its own)
+// Each translation unit picks exactly ONE record layout (and, the templates being instantiated on it, a namespace of its own):
+// plain (frp_ipm_lds.hip, _mem, _s2), Q4 (frp_ipm_lds_q4.hip) or Q30 (frp_ipm_lds_q30.hip).
 #if defined(FRP_LDS_Q4_TU)
 #define FRP_LR lrq
+#define FRP_LAYOUT Layout::Q4
 #elif defined(FRP_LDS_Q30_TU)
 #define FRP_LR lrs
+#define FRP_LAYOUT Layout::Q30
 #elif defined(FRP_LDS_S2_TU)
 #define FRP_LR lr2
+#define FRP_LAYOUT Layout::Plain
 #else
 #define FRP_LR lr
+#define FRP_LAYOUT Layout::Plain
 #endif
 
 namespace frp {
 namespace FRP_LR {
 
 // ------------------------------------------------------------------ per-stage LDS record (doubles)
-// Two layouts.  The "plain" one (RS = 309: three problems per CU) keeps the packed P_k of every stage in LDS.  The "Q4" one
-// (-DFRP_LDS_Q4_TU, frp_ipm_lds_q4.hip: RS = 241 -> 38.6 KB per problem, FOUR problems per CU on three-wave workgroups) moves P_k
+// Three layouts.  The "plain" one (RS = 309: three problems per CU) keeps the packed P_k of every stage in LDS.  The "Q4" one
+// (frp_ipm_lds_q4.hip: RS = 241 -> 38.6 KB per problem, FOUR problems per CU on three-wave workgroups) moves P_k
 // -- written once by the factorisation sweep, read once by the multiplier recovery y = P ds + p -- to an L2-resident workspace in
 // global memory (KernelArgs::pws, 92 doubles per stage and resident workgroup) and lets T' and p share the slots of the
 // barrier-augmented Hessian, which is dead once the factorisation step of its stage has gathered it.
-// (three independent parts, switchable one by one for bisection builds: FRP_QP = P in global memory, FRP_QL = the 241-double
-// record, FRP_QW = three-wave workgroups; the Q4 translation unit defines all three)
-#ifdef FRP_LDS_Q4_TU
-#define FRP_QP 1
-#define FRP_QL 1
-#define FRP_QW 1
-#endif
-// The "Q30" translation unit (frp_ipm_lds_q30.hip, round 6): N <= 30 at THREE problems per CU.  P in global memory and the overlay record as in Q4, on four-wave
-// workgroups with the lane == stage model phase, and a record of 215 doubles (FRP_QS): no trig hand-over slots, P d aliased onto the p slots, no hole between the
+// The "Q30" one (frp_ipm_lds_q30.hip, round 6): N <= 30 at THREE problems per CU.  P in global memory and the overlay record as in Q4, on four-wave
+// workgroups with the lane == stage model phase, and a record of 215 doubles: no trig hand-over slots, P d aliased onto the p slots, no hole between the
 // B and C twins, the external force read from the parameters instead of the workgroup scratch: 30 x 215 x 8 + 1.4 KB = 53 032 B per workgroup.
-#ifdef FRP_LDS_Q30_TU
-#define FRP_QP 1
-#define FRP_QL 1
-#define FRP_QS 1
-#define FRP_NO_YPARK 1
-#endif
-#ifdef FRP_QS
-constexpr bool QS = true;
-#else
-constexpr bool QS = false;
-#endif
-#ifdef FRP_QP
-constexpr bool QP = true;
-#else
-constexpr bool QP = false;
-#endif
-#ifdef FRP_QL
-constexpr bool QL = true;
-#else
-constexpr bool QL = false;
-#endif
-#ifdef FRP_QW
-constexpr bool QW = true;
-#else
-constexpr bool QW = false;
-#endif
-static_assert(!QL || QP, "the short record has no room for P");
+enum class Layout { Plain, Q4, Q30 };
+constexpr Layout LAYOUT = FRP_LAYOUT;
+constexpr bool QP = LAYOUT != Layout::Plain; // P_k in global memory
+constexpr bool QL = QP;                      // the overlay record (it has no room for P)
+constexpr bool QW = LAYOUT == Layout::Q4;    // three-wave workgroups
+constexpr bool QS = LAYOUT == Layout::Q30;   // the 215-double record
+constexpr bool Y_PARK = !QS;                 // the model wave parks y in the record between its phases (Q30: y stays in its registers)
 constexpr int R_LIN = 0;     // compact linearisation (51): Apv Ape Avv Ave BpT BvT Bvw
 constexpr int R_D = 51;      // d = prev(z_k) - s_{k+1}, s-order [w; x] (13)            } the "M row": 64 slots
-#ifndef FRP_QL
-constexpr int R_T = 64;      // T' = [R | Kbar_x | kbar | hc]: lane (g, c) <-> T'[g][c] (64)
-// overlay region (104): the barrier-augmented Hessian is dead once the factorisation step of the stage has gathered
+constexpr int R_T = 64;      // T' = [R | Kbar_x | kbar | hc]: lane (g, c) <-> T'[g][c] (64); QL: over HD / PHID / the head of PHIPOS
+// plain: overlay region (104): the barrier-augmented Hessian is dead once the factorisation step of the stage has gathered
 // it, and that step's output P_k takes its place
-constexpr int R_PHID = 128;  // diag of Phi = cost Hessian + bound barriers (17)
-constexpr int R_PHIPOS = 145; // corridor barrier block on pos (3 x 3)
-constexpr int R_PHI = 154;   // predictor rhs gradient phi_aff without its corridor part (17)
-constexpr int R_HD = 171;    // exact Hessian of y'c(z): 45 structurally non-zero entries (hd_pack)
-constexpr int R_P = 128;     // P_k, packed lower triangle (91)
-constexpr int R_PV = 219;    // p_k of the corrector solve (13)
-constexpr int R_PD = 232;    // P_{k+1} d_k (13): written by the factorisation sweep, read by the corrector's backward sweep
-constexpr int R_PHIB = 245;  // corrector rhs phi_cc = PHIB + (sigma mu) PHIC (17 + 17), bound rows and cost;
-constexpr int R_PHIW = R_HD + 40; // (QP bisection builds on this layout) Phi_w of the stage (4), left by the factorisation step in consumed Hessian slots
-#else
-// overlay region (88): [HD 45 | PHID 17 | PHIPOS 9 | PHI 17] until the factorisation step of the stage has gathered it, then
+// QL: overlay region (88): [HD 45 | PHID 17 | PHIPOS 9 | PHI 17] until the factorisation step of the stage has gathered it, then
 // [T' 64 | p 13] (T' from that step, p from the corrector's backward sweep).  Scratch in it (all inside HD, whose only writer in the
 // evaluation phase is the wave that uses the scratch): the Riccati wave's trig hand-over (12) and the Hessian's inputs the model
 // wave leaves in the step phase (RT_HZ 10, RT_HY 6 -- T' slots, dead after the last forward sweep).
-constexpr int R_HD = 64;     // exact Hessian of y'c(z): 45 structurally non-zero entries (hd_pack)
-constexpr int R_PHID = 109;  // diag of Phi = cost Hessian + bound barriers (17)
-constexpr int R_PHIPOS = 126; // corridor barrier block on pos (3 x 3)
-constexpr int R_PHI = 135;   // predictor rhs gradient phi_aff without its corridor part (17)
-constexpr int R_T = 64;      // T' (64), over HD / PHID / the head of PHIPOS
-constexpr int R_PV = 128;    // p_k of the corrector solve (13), over PHIPOS / PHI
-constexpr int R_P = 0;       // (P_k lives in global memory: packed index 0..90 of the stage's block, 91 = dump)
-#ifndef FRP_QS
-constexpr int R_PD = 152;    // P_{k+1} d_k (13): written by the factorisation sweep, read by the corrector's backward sweep;
-                             //   from there to the next factorisation: the model wave's parked y (RT_Y)
-constexpr int R_PHIB = 165;  // corrector rhs phi_cc = PHIB + (sigma mu) PHIC (17 + 17), bound rows and cost;
-#else
-// QS: P_{k+1} d_k lives in the p slots of stage k.  The factorisation step of stage k+1 stores it into stage k's record AFTER it has gathered stage k's
+constexpr int R_PHID = QL ? 109 : 128;   // diag of Phi = cost Hessian + bound barriers (17)
+constexpr int R_PHIPOS = QL ? 126 : 145; // corridor barrier block on pos (3 x 3)
+constexpr int R_PHI = QL ? 135 : 154;    // predictor rhs gradient phi_aff without its corridor part (17)
+constexpr int R_HD = QL ? 64 : 171;      // exact Hessian of y'c(z): 45 structurally non-zero entries (hd_pack)
+constexpr int R_P = QL ? 0 : 128;        // P_k, packed lower triangle (91) (QL: P_k lives in global memory: packed index 0..90 of the stage's block, 91 = dump)
+constexpr int R_PV = QL ? 128 : 219;     // p_k of the corrector solve (13); QL: over PHIPOS / PHI
+// P_{k+1} d_k (13): written by the factorisation sweep, read by the corrector's backward sweep; Q4: from there to the next factorisation: the model wave's parked y (RT_Y)
+// Q30: P_{k+1} d_k lives in the p slots of stage k.  The factorisation step of stage k+1 stores it into stage k's record AFTER it has gathered stage k's
 // tiles (the slots lie in the overlay over PHIPOS / PHI: the timing argument of T'), the vector backward sweep reads it one step before its own step at
 // stage k overwrites the slot with p_k, and nothing reads p before that sweep.
-constexpr int R_PD = R_PV;
-constexpr int R_PHIB = 152;
-#endif
-constexpr int R_PHIW = R_PV + 13; // Phi_w of the stage (4) behind p, left by the factorisation step (the y+ rows of w are formed from T' and this)
-static_assert(QS || R_PHIW + 4 <= R_PD, "Phi_w stash");
-#endif
+constexpr int R_PD = !QL ? 232 : (QS ? R_PV : 152);
+constexpr int R_PHIB = !QL ? 245 : (QS ? 152 : 165); // corrector rhs phi_cc = PHIB + (sigma mu) PHIC (17 + 17), bound rows and cost;
+constexpr int R_PHIW = QL ? R_PV + 13 : -1; // QL only: Phi_w of the stage (4) behind p, left by the factorisation step (the y+ rows of w are formed from T' and this)
+static_assert(!QL || QS || R_PHIW + 4 <= R_PD, "Phi_w stash");
 constexpr int R_CB = R_PHIB + 17; //   corridor part (pos entries) of PHIB; evaluation phase: A' lam (stationarity residual)
-#ifndef FRP_QS
-constexpr int R_BC = 21;     // distance from every "B" slot (PHIB, CB) to its "C" twin (PHIC, CC): one ds_read2 fetches both
-#else
-constexpr int R_BC = 20;     // (no hole between CB and PHIC: the spare is the twisted solve's)
-#endif
+// distance from every "B" slot (PHIB, CB) to its "C" twin (PHIC, CC): one ds_read2 fetches both (Q30: no hole between CB and PHIC: the spare is the twisted solve's)
+constexpr int R_BC = QS ? 20 : 21;
 constexpr int R_PHIC = R_PHIB + R_BC; // evaluation phase: PHIB = cost gradient + bound multipliers, PHIC = M'y part (stationarity residual)
 constexpr int R_CC = R_CB + R_BC;     // corridor part of PHIC; evaluation phase: corridor part of phi_aff
-#ifndef FRP_QS
-constexpr int R_HC = R_PHIB + 41;    // (u_i, w_i) cost coupling -2 w_rate of this stage
-constexpr int R_ZERO = R_HC + 1, R_ONE = R_HC + 2, R_DT = R_HC + 3; // constants the gathers pick up
-constexpr int R_DUMP = R_HC + 4;  // target of masked-out writes (never read)
-constexpr int R_DZ = R_HC + 5;    // Newton step [du(4); ds(13)]
-#else
-// [0 | Newton step 17 | hc | 1 | 0' | dt | dump]: the two zeros R_BC apart around the step
-constexpr int R_ZERO = R_CC + 3, R_DZ = R_ZERO + 1, R_HC = R_DZ + 17, R_ONE = R_HC + 1, R_DT = R_ONE + 2, R_DUMP = R_DT + 1;
-#endif
+// plain, Q4: [hc | 0 | 1 | dt | dump | Newton step 17];  Q30: [0 | Newton step 17 | hc | 1 | 0' | dt | dump]: the two zeros R_BC apart around the step
+constexpr int R_ZERO = QS ? R_CC + 3 : R_PHIB + 42; // R_ZERO, R_ONE, R_DT: constants the gathers pick up
+constexpr int R_DZ = QS ? R_ZERO + 1 : R_PHIB + 46; // Newton step [du(4); ds(13)]
+constexpr int R_HC = QS ? R_DZ + 17 : R_PHIB + 41;  // (u_i, w_i) cost coupling -2 w_rate of this stage
+constexpr int R_ONE = QS ? R_HC + 1 : R_HC + 2;
+constexpr int R_DT = QS ? R_ONE + 2 : R_HC + 3;
+constexpr int R_DUMP = QS ? R_DT + 1 : R_HC + 4;    // target of masked-out writes (never read)
 constexpr int R_ZERO2 = R_ZERO + R_BC; // second zero, R_BC behind the first: masked (B, C) pair reads
 // Twisted solve: a stage of the FIRST half keeps the inverted transition [u; x]_k = T~ [w+; x+] + t~ where a stage of
 // the second half keeps the linearisation: A~ = A^-1 has A's block pattern (A~pv, A~pe, A~vv, A~ve in the slots of Apv, Ape, Avv, Ave),
@@ -152,32 +107,21 @@ constexpr int R_ZERO2 = R_ZERO + R_BC; // second zero, R_BC behind the first: ma
 // B~).  The nine entries of B~ that do not fit the 51 linearisation slots live where a first-half record has room: the columns 14, 15
 // of T' (eight slots that only ever meet the zero rows 14, 15 of a sweep vector; the first-half sweeps do not store there), the second
 // zero (only the second half's vector sweep reads it) -- and one spare: the hole between CB and PHIC.
-#ifndef FRP_QL
-constexpr int RS = 309;      // odd stride: lane == stage accesses are conflict-free
-static_assert(R_HD + REC_HD_SIZE <= R_PV && R_PV + 13 <= R_PD, "overlay region");
-static_assert(R_PHIB == 245 && R_HC == 286 && R_DZ == 291 && R_ZERO2 == 308, "the plain record");
-#elif !defined(FRP_QS)
-constexpr int RQ_MTRIG = R_ZERO2 + 1; // 12 slots of the model + corridor wave's own: four parking slots per lane of the stage (FRP_Q4_PARK; without it: that wave's trig hand-over)
-constexpr int RS = RQ_MTRIG + 12;     // 241, odd
-static_assert(RS == 241 && (RS & 1), "the Q4 record");
-static_assert(R_HD + REC_HD_SIZE == R_PHID && R_PHID + 17 == R_PHIPOS && R_PHIPOS + 9 == R_PHI && R_PHI + 17 == R_PD, "overlay region");
-static_assert(R_T + 64 <= R_PV && R_PV + 13 <= R_PD && R_PD + 13 == R_PHIB, "overlay region after the factorisation");
-#else
-constexpr int RQ_MTRIG = R_DUMP;      // (the lane == stage model phase has no trig hand-over)
-constexpr int RS = R_DUMP + 1;        // 215, odd
-static_assert(RS == 215 && (RS & 1) && R_ZERO2 == R_ONE + 1 && R_ZERO2 == R_DT - 1, "the Q30 record");
-static_assert(R_HD + REC_HD_SIZE == R_PHID && R_PHID + 17 == R_PHIPOS && R_PHIPOS + 9 == R_PHI && R_PHI + 17 == R_PHIB, "overlay region");
-static_assert(R_T + 64 <= R_PV && R_PHIW + 4 <= R_PHIB, "overlay region after the factorisation");
-#endif
-#ifndef FRP_QS
-static_assert(R_PHIC + 17 <= R_CC && R_CC + 3 <= R_HC && R_DZ + 17 <= R_ZERO2 && R_ZERO2 < RS, "record tail");
-#else
-static_assert(R_PHIC + 17 == R_CC && R_CC + 3 == R_ZERO && R_DZ + 17 == R_HC && R_DUMP < RS, "record tail");
-#endif
-#ifndef FRP_TW_RHO
-#define FRP_TW_RHO 1e12
-#endif
-constexpr double TW_RHO = FRP_TW_RHO; // penalty that pins x_0 in the arrival-cost recursion (tools/study/twisted_riccati.py)
+// RQ_MTRIG, Q4: 12 slots of the model + corridor wave's own: four parking slots per lane of the stage (the model wave's trig hand-over uses the d slots);
+// Q30: the lane == stage model phase has no trig hand-over
+constexpr int RQ_MTRIG = QS ? R_DUMP : R_ZERO2 + 1;
+constexpr int RS = !QL ? 309 : (QS ? R_DUMP + 1 : RQ_MTRIG + 12); // 309 / 241 / 215: odd stride: lane == stage accesses are conflict-free
+static_assert(QL || (R_HD + REC_HD_SIZE <= R_PV && R_PV + 13 <= R_PD), "overlay region");
+static_assert(QL || (R_PHIB == 245 && R_HC == 286 && R_DZ == 291 && R_ZERO2 == 308), "the plain record");
+static_assert(!QW || (RS == 241 && (RS & 1)), "the Q4 record");
+static_assert(!QW || (R_HD + REC_HD_SIZE == R_PHID && R_PHID + 17 == R_PHIPOS && R_PHIPOS + 9 == R_PHI && R_PHI + 17 == R_PD), "overlay region");
+static_assert(!QW || (R_T + 64 <= R_PV && R_PV + 13 <= R_PD && R_PD + 13 == R_PHIB), "overlay region after the factorisation");
+static_assert(!QS || (RS == 215 && (RS & 1) && R_ZERO2 == R_ONE + 1 && R_ZERO2 == R_DT - 1), "the Q30 record");
+static_assert(!QS || (R_HD + REC_HD_SIZE == R_PHID && R_PHID + 17 == R_PHIPOS && R_PHIPOS + 9 == R_PHI && R_PHI + 17 == R_PHIB), "overlay region");
+static_assert(!QS || (R_T + 64 <= R_PV && R_PHIW + 4 <= R_PHIB), "overlay region after the factorisation");
+static_assert(QS || (R_PHIC + 17 <= R_CC && R_CC + 3 <= R_HC && R_DZ + 17 <= R_ZERO2 && R_ZERO2 < RS), "record tail");
+static_assert(!QS || (R_PHIC + 17 == R_CC && R_CC + 3 == R_ZERO && R_DZ + 17 == R_HC && R_DUMP < RS), "record tail");
+constexpr double TW_RHO = 1e12; // penalty that pins x_0 in the arrival-cost recursion (tools/study/twisted_riccati.py)
 // QP: what the multiplier recovery y+ = P ds + p needs of P_k that is NOT in the record goes to global memory.  The w rows of P are
 // [Phi_w - hc^2 R | -hc Kbar_x] and the (x, w) block is their transpose: both follow from T' (in the record) and the four Phi_w (stashed in
 // the record by the factorisation step).  Only S_xx (9 x 9, symmetric) leaves: per resident workgroup NP blocks of PG = 48 doubles, three
@@ -322,13 +266,6 @@ static __device__ const LaneTables g_tab = make_tables();
 __device__ __forceinline__ int tab(int row, int lane) { return (int)g_tab.v[row][lane]; }
 #define BAR() __syncthreads()
 #define FRP_SB() __builtin_amdgcn_sched_barrier(0)
-// between the rounds / rows of the element-wise loops (unrolled): keeps the scheduler from interleaving them, i.e. from multiplying
-// their temporaries in waves whose persistent state leaves ~30 registers (-DFRP_ROUND_SB)
-#ifdef FRP_ROUND_SB
-#define FRP_RSB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define FRP_RSB()
-#endif
 
 // LDS pointers carry their address space: through a generic double* every access of a non-inlined function would pay
 // 64-bit address arithmetic and the null check of the address-space cast
@@ -457,8 +394,9 @@ __device__ __forceinline__ double stationarity_norm(cldouble *recs, int N)
 
 struct Ctl { // workgroup-shared control words
     int next, fail, bad, mtot, fail1, fail2; // twisted solve: fail1 = the first half's factorisation, fail2 = the system where the halves meet
-    // FRP_EARLY_FACTOR: the termination decision of an iteration, taken by the helper waves while the Riccati wave is already factoring
-    // (dec_tag = (problem << 8 | iteration) once dec_stop / dec_flag are valid; reset at kernel start: LDS keeps a previous launch's words)
+    // (three words nothing reads: they carried an experiment's hand-over -- the termination decision taken by the helper waves while the Riccati wave was
+    // already factoring, DESIGN_HISTORY.  They and their reset at kernel start stay because the offsets of the words behind them and those two stores
+    // are part of the generated code, which the removal of the experiment left byte for byte as it was)
     unsigned dec_tag;
     int dec_stop, dec_flag;
     int head_first; // (Q4) >= 0: this workgroup was first on its CU and took a head-start problem (KernelArgs::head_start): its first solve holds the CU's mark
@@ -473,9 +411,8 @@ typedef __attribute__((address_space(3))) Ctl lctl_t;
 // ================================================================== wave 0: Riccati sweeps
 // ---- stage-0 solve (both passes): dx_0 = xinit - x_0, dw_0 = -Pww^-1 (Pwx dx_0 + p_w); leaves ds_0 in X_DS0.
 // pw_here: p_w[g] in the lanes (g, 13).
-#ifndef FRP_S0_OPQ // 1: the lane opaque at the call in the factorisation sweep -- inlined into the kernel, the stage-0 solve's lane-dependent LDS addresses are loop
-#define FRP_S0_OPQ 1 // invariants of the interior-point loop: hoisted, spilled, and fetched from scratch one round trip at a time at the tail of the factorisation
-#endif
+// (the factorisation sweep passes the lane opaque: inlined into the kernel, the stage-0 solve's lane-dependent LDS addresses are otherwise loop
+// invariants of the interior-point loop: hoisted, spilled, and fetched from scratch one round trip at a time at the tail of the factorisation)
 __device__ __forceinline__ void stage0_solve(ldouble *xs, int lane, double pw_here)
 {
     const int g = lane >> 4, c = lane & 15;
@@ -553,7 +490,6 @@ template <int OFF>
 __device__ __forceinline__ void gst(const double *base, unsigned boff, double v)
 {
     static_assert(OFF >= 0 && OFF < 4096, "immediate offset of a global store");
-#ifndef FRP_GST_CXX
     // Inline asm: written in C++ the compiler keeps a 64-bit address per store in vector registers (8 VGPRs in a wave at the cap).
     // CAUTION: the hazard recognizer does not look inside inline asm -- a memory instruction that reads the result of an MFMA needs
     // 18 wait states behind it, which the compiler inserts for its own stores (s_nop 15; s_nop 0) and NOT here: the caller makes sure
@@ -561,11 +497,8 @@ __device__ __forceinline__ void gst(const double *base, unsigned boff, double v)
     // still converged, two iterations late, on wrong multipliers).  Not on the compiler's vmcnt scoreboard either: nothing in the
     // sweeps reads global memory, and the predictor phase ends with an explicit s_waitcnt vmcnt(0).
     asm volatile("global_store_dwordx2 %0, %1, %2 offset:%3" : : "v"(boff), "v"(v), "s"(base), "n"(OFF) : "memory");
-#else
-    *(__attribute__((address_space(1))) double *)((__attribute__((address_space(1))) char *)base + boff + OFF) = v;
-#endif
 }
-#ifdef FRP_QP
+#if defined(FRP_LDS_Q4_TU) || defined(FRP_LDS_Q30_TU) // (QP: the sweeps take the workgroup's block of packed P in global memory)
 #define FRP_GP_PARAM , double *gp
 #define FRP_GP_ARG(x) , x
 #else
@@ -584,26 +517,12 @@ __device__ __forceinline__ void gst(const double *base, unsigned boff, double v)
 #endif
 // twist (second half of a twisted solve: `recs` is the record of the meeting stage, N the stages from there to the end): the stage-0
 // tail is replaced by publishing p of the meeting stage (column 13 of the tile) in its R_PV slots.
-// POLL (FRP_EARLY_FACTOR): the sweep starts before the iteration's termination test is known; between its passes it looks for the helper
-// waves' decision (Ctl::dec_tag == want) and leaves at once when that says "stop".  Return value: bit 0 = a pivot block failed, bit 1 =
-// stopped by the decision, bit 2 = the decision has been seen (and said "go on").
-template <bool twist, bool POLL = false>
-__device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N, double theta FRP_GP_PARAM, lctl_t *ctl = nullptr, unsigned want = 0)
+// Returns 1 when a pivot block failed.
+template <bool twist>
+__device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N, double theta FRP_GP_PARAM)
 {
     N = uni(N); theta = uni(theta);
-    want = (unsigned)uni((int)want); // (the problem index comes out of an LDS load: uniform, but not to the compiler -- a loop exit on it would make every value of the loop "divergent")
-    bool decided = false;
-    auto poll = [&]() -> bool { // true: stop
-        if constexpr (POLL) {
-            // (an LDS-address-space pointer: through a generic one the load is a FLAT instruction, whose wait drains the S_xx stores too -- measured +6 %)
-            if (!decided && uni((int)*(volatile __attribute__((address_space(3))) unsigned *)&ctl->dec_tag) == (int)want) {
-                decided = true;
-                return uni(*(volatile __attribute__((address_space(3))) int *)&ctl->dec_stop) != 0;
-            }
-        }
-        return false;
-    };
-#ifdef FRP_QP
+#if defined(FRP_LDS_Q4_TU) || defined(FRP_LDS_Q30_TU)
     const double *gpk = uni(gp) + (size_t)(N - 1) * PG; // block of the stage the pointers sit on
 #endif
     const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15, c3_ = c & 3;
@@ -634,7 +553,8 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
     ldouble *base = recs + (N - 1) * RS;
     ldouble *p_c1[4], *p_c3[4], *p_mo[4], *p_pp[4], *p_pd[4];
     ldouble *p_c2 = base + c2[1], *p_pq = base + pqo, *p_t = base + lane;
-    ldouble *p_pw = base + ((c < 4 && g == c) ? R_PHIW + g : R_DUMP); // QP: Phi_w[g] stays in the record (the diagonal lanes of the w block hold it)
+    ldouble *p_pw = nullptr; // QP: Phi_w[g] stays in the record (the diagonal lanes of the w block hold it)
+    if constexpr (QP) p_pw = base + ((c < 4 && g == c) ? R_PHIW + g : R_DUMP);
     unsigned gb[4]; // Q4: byte offsets of this lane's four tile entries inside a stage's block of packed P
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -657,7 +577,7 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
             opaque(p_c1[r]); opaque(p_c3[r]); opaque(p_mo[r]); opaque(p_pd[r]);
             if constexpr (!QP) { p_pp[r] -= by; opaque(p_pp[r]); }
         }
-#ifdef FRP_QP
+#if defined(FRP_LDS_Q4_TU) || defined(FRP_LDS_Q30_TU)
         gpk -= stages * PG;
 #endif
     };
@@ -665,7 +585,7 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
     // gathered one step ago (plain) / to the workgroup's block in global memory (Q4)
     auto store_p = [&](auto orc, const d4 &Pt) {
         constexpr int OR = decltype(orc)::value;
-#ifdef FRP_QP
+#if defined(FRP_LDS_Q4_TU) || defined(FRP_LDS_Q30_TU)
 #pragma unroll
         for (int r = 0; r < 4; r++) gst<(OR / RS) * PG * 8>(gpk, gb[r], Pt[r]);
 #else
@@ -753,7 +673,6 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
     using std::integral_constant;
     int kk = N - 1;
     for (; kk >= 4; kk -= 4) {
-        if (poll()) return 2;
         move(4); // pointers on stage kk - 4
         stage(integral_constant<int, 4 * RS>{}, std::false_type{});
         stage(integral_constant<int, 3 * RS>{}, std::false_type{});
@@ -771,7 +690,6 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
             stage(integral_constant<int, RS>{}, std::false_type{});
         }
     }
-    if (poll()) return 2;
     stage(integral_constant<int, 0>{}, std::true_type{}); // stage 0
     SEG_FLUSH();
     int fail = ok ? 0 : 1;
@@ -792,11 +710,11 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
 #pragma unroll
             for (int i = 0; i < 16; i++) xs[X_RW + i] = Rw[i];
             if (c >= 4 && c <= 12) xs[X_PWX + g * 9 + c - 4] = P[0];
-            stage0_solve(xs, FRP_S0_OPQ ? opq(lane) : lane, P[0]); // (p_w sits in column 13 of the w rows)
+            stage0_solve(xs, opq(lane), P[0]); // (p_w sits in column 13 of the w rows)
         }
     }
     WSYNC();
-    return fail | (decided ? 4 : 0);
+    return fail;
 }
 
 // ---- the two vector sweeps.  One wavefront issues in order and its MFMAs do not overlap its own VALU / LDS instructions
@@ -1476,51 +1394,31 @@ struct ModelState {
 // through the T' slots of the stage record, which are dead between the last forward sweep and the next factorisation:
 // J1 (21) while J2 is formed, y (13) during the whole linearisation.
 // The Hessian lanes' inputs: RT_HU (rates, T: 4), RT_HVE (v, e: 6), RT_HY (y_p, y_v: 6) before the step, RT_HYP (y+ rows 4..9: 6).
-#if !defined(FRP_QL) && !defined(FRP_QP)
-constexpr int RT_J1 = R_T, RT_Y = R_T + 24;
-// after the last forward sweep of an iteration wave 1 leaves here what wave 0 needs to rebuild its Hessian inputs for the
+// plain: after the last forward sweep of an iteration wave 1 leaves in the T' slots what wave 0 needs to rebuild its Hessian inputs for the
 // next one (so that nothing of it occupies registers across the sweeps): (rates, T, v, e) before the step, (y_p, y_v) too
 // (placed clear of RT_Y -- written at the start of the model phase while the Hessian lanes read these -- and of the columns 14, 15
-// of T', which hold part of B~ in a first-half record)
-constexpr int RT_HU = R_T + 48, RT_HVE = R_T + 52, RT_HY = R_T + 37, RT_HYP = R_DUMP /* (in registers) */, RT_YV = R_DUMP;
-static_assert(RT_HY >= RT_Y + 13 && RT_HY + 6 <= R_T + 46 && RT_HVE + 6 <= R_T + 62, "scratch in the T' slots");
-constexpr int RX_MTRIG = R_PV, RX_HTRIG = R_PD; // trig hand-over of the model wave / of the Riccati wave's Hessian lanes (12 each)
-#else
+// of T', which hold part of B~ in a first-half record); y+ rows 4..9 stay in registers.
 // QP: the y+ lanes (bounds wave) read Kbar_x and kbar of T' in the step phase, while the model wave leaves the Hessian's inputs: those go
 // to the T' slots the y+ lanes do not read -- R (columns 0..3) and the zero columns 14, 15 of the rows 0..2.  The y+ lanes' own scratch
 // (block hand-over RT_YV, 9; y+ rows 4..9 for the Hessian lanes RT_HYP, 6) takes Kbar_x slots AFTER their last read of T' (same wave).
-constexpr int RT_HU = R_T + 0, RT_HVE = R_T + 14, RT_HY = R_T + 30, RT_YV = R_T + 4, RT_HYP = R_T + 20;
-#ifndef FRP_QS
-constexpr int RT_J1 = R_T; // (the lane == stage model phase: not built with QP)
-#endif
-#ifndef FRP_QL
-constexpr int RT_Y = R_T + 36; // (bisection builds: T' is a region of its own, dead in the evaluation phase)
-constexpr int RX_MTRIG = R_PV, RX_HTRIG = R_PD;
-#else
+constexpr int RT_HU = QP ? R_T + 0 : R_T + 48, RT_HVE = QP ? R_T + 14 : R_T + 52, RT_HY = QP ? R_T + 30 : R_T + 37;
+constexpr int RT_YV = QP ? R_T + 4 : R_DUMP, RT_HYP = QP ? R_T + 20 : R_DUMP;
+constexpr int RT_J1 = R_T; // (Q30: unused, see RT_J1V below)
 // QL: T' shares the Hessian's slots, which the element-wise waves fill during the evaluation phase -- the model wave's scratch of that
 // phase has slots outside the overlay (y in the P d slots, dead from the corrector's backward sweep to the next factorisation; the trig
 // hand-over at the record's end); what the Riccati wave reads at the start of the evaluation (RT_H*) and its trig hand-over sit inside HD,
 // which only that wave writes in the phase (the hand-over overlaps RT_HYP / RT_HY: written after they were read, by the same wave)
-constexpr int RT_Y = R_PD; // (QS: unused -- y stays in the model wave's registers, FRP_NO_YPARK)
-#ifndef FRP_Q4_PARK // 1: the 12 slots at the record's end are the corridor lanes' parking (see PARK in solve_one); the model wave's trig hand-over uses the d slots instead --
-#define FRP_Q4_PARK 1 // dead from that wave's commit (they carried y+) to its own store of d, a few hundred instructions behind the hand-over
-#endif
-#if !defined(FRP_QS) && FRP_Q4_PARK
-constexpr int RX_HTRIG = R_T + 20, RX_MTRIG = R_D;
-#else
-constexpr int RX_HTRIG = R_T + 20, RX_MTRIG = RQ_MTRIG;
-#endif
-static_assert(RX_HTRIG + 12 <= R_HD + REC_HD_SIZE && RT_HY + 6 <= R_HD + REC_HD_SIZE, "the Riccati wave's scratch inside HD");
-#endif
-#endif
+constexpr int RT_Y = QL ? R_PD : R_T + 24; // (Q30: unused -- y stays in the model wave's registers, Y_PARK)
+static_assert(QP || (RT_HY >= RT_Y + 13 && RT_HY + 6 <= R_T + 46 && RT_HVE + 6 <= R_T + 62), "scratch in the T' slots");
+// trig hand-over of the model wave / of the Riccati wave's Hessian lanes (12 each).  Q4: the 12 slots at the record's end are the corridor lanes' parking
+// (see PARK in solve_one); the model wave's trig hand-over uses the d slots instead -- dead from that wave's commit (they carried y+) to its own store of
+// d, a few hundred instructions behind the hand-over
+constexpr int RX_HTRIG = QL ? R_T + 20 : R_PD, RX_MTRIG = !QL ? R_PV : (QS ? RQ_MTRIG : R_D);
+static_assert(!QL || (RX_HTRIG + 12 <= R_HD + REC_HD_SIZE && RT_HY + 6 <= R_HD + REC_HD_SIZE), "the Riccati wave's scratch inside HD");
 // where the lane == stage model phase parks J1 = [F_vv (9) | F_ve (9) | g_T (3)] of the first RK2 point while J2 is formed.  QS: T' shares the Hessian's slots, which
 // the other waves fill during this phase -- the scratch is what THIS wave writes last: the M'y slots (PHIC, written at the end of the phase) and the d slots (written
 // behind the J2 J1 products; they carried y+ until this wave's commit)
-#ifndef FRP_QS
-constexpr int RT_J1V = RT_J1, RT_J1E = RT_J1 + 9, RT_J1T = RT_J1 + 18;
-#else
-constexpr int RT_J1V = R_PHIC, RT_J1E = R_D, RT_J1T = R_D + 9;
-#endif
+constexpr int RT_J1V = QS ? R_PHIC : RT_J1, RT_J1E = QS ? R_D : RT_J1 + 9, RT_J1T = QS ? R_D + 9 : RT_J1 + 18;
 template <int NP>
 __device__ __forceinline__ void model_phase(ldouble *recs, ldouble *xs, ModelState &st, int N, double &l_eq)
 {
@@ -1532,12 +1430,12 @@ __device__ __forceinline__ void model_phase(ldouble *recs, ldouble *xs, ModelSta
     const bool dyn = k < N - 1;
     SEG_DECL();
     // ---- part 1: the step and its linearisation (no multipliers involved)
-#ifndef FRP_NO_YPARK
-    if (k < N) {
+    if constexpr (Y_PARK) {
+        if (k < N) {
 #pragma unroll
-        for (int i = 0; i < NS; i++) rec[RT_Y + i] = st.y[i];
+            for (int i = 0; i < NS; i++) rec[RT_Y + i] = st.y[i];
+        }
     }
-#endif
     if (k == 0) {
 #pragma unroll
         for (int i = 0; i < 9; i++) {
@@ -1640,12 +1538,12 @@ __device__ __forceinline__ void model_phase(ldouble *recs, ldouble *xs, ModelSta
     SEG(4);
     // ---- part 2: gm = M' y_{k+1} - [0; y_k], the linearisation read back from the record this lane has just written
     {
-#ifndef FRP_NO_YPARK
-        if (k < N) {
+        if constexpr (Y_PARK) {
+            if (k < N) {
 #pragma unroll
-            for (int i = 0; i < NS; i++) st.y[i] = rec[RT_Y + i];
+                for (int i = 0; i < NS; i++) st.y[i] = rec[RT_Y + i];
+            }
         }
-#endif
         double yn[NS];
 #pragma unroll
         for (int i = 0; i < NS; i++) yn[i] = dpp_move<0x130>(st.y[i]);
@@ -2186,16 +2084,11 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     // of the sweeps, and that wave runs at low priority), against 7.1 / 3.2 / 2.2 k of the four-wave split.
     // The element-wise partial results are published per wave in X_RED and combined by everybody in the fixed order (WB, WF);
     // WEQ = the row the model wave publishes the equality norm in.
-#ifndef FRP_Q4_FWAVE // Q4: the wave that owns the corridor rows (0 = the Riccati wave, 1 = the model wave, 2 = the wave of the bound rounds)
-#define FRP_Q4_FWAVE 1
-#endif
-#ifndef FRP_Q4_RM // Q4: bound rounds on the model wave (the LAST ones: rows 15, 16 carry no rate coupling and need two cost parameters)
-#define FRP_Q4_RM 0
-#endif
+    // Q4: the model wave owns the corridor rows, wave 2 every bound round (the timings above)
     constexpr int WEQ = QW ? 3 : 1;
-    constexpr bool IS_M = wave == 1, IS_F = wave == (QW ? FRP_Q4_FWAVE : 3);   // model; corridor rows
+    constexpr bool IS_M = wave == 1, IS_F = wave == (QW ? 1 : 3);   // model; corridor rows
     // CONTRIB(w): wave w owns bound rounds and / or corridor rows and publishes element-wise partial results
-    auto contrib = [](int w) constexpr { return QW ? (w == 2 || w == FRP_Q4_FWAVE || (w == 1 && FRP_Q4_RM > 0)) : (w == 2 || w == 3); };
+    auto contrib = [](int w) constexpr { return QW ? (w == 2 || w == 1) : (w == 2 || w == 3); };
     constexpr bool IS_B = contrib(wave);
     constexpr bool IS_BO = IS_B && !IS_F;                                      // ... bound rounds only
     static_assert(!QP || ((NP == 20 || QS) && !TW), "P in global memory: the y+ rows are dealt over the three lanes of a stage (Q4) or formed by the lane of the stage (Q30)");
@@ -2256,10 +2149,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     // wave 0: what its Hessian lanes carry from the step phase to the next evaluation -- the Newton step of (rates, T), (v, e) and
     // y+ (p, v rows) of the next stage; the values before the step come from the model wave through the record (RT_HZ, RT_HY),
     // so that nothing of the Hessian's inputs is live across the sweeps
-#ifndef FRP_QP_YWAVE // QP: the wave that forms y+ (0 = the Riccati wave, fetching S_xx in the step phase; 2 = the bounds wave, prefetching behind barrier D)
-#define FRP_QP_YWAVE 0
-#endif
-    constexpr int WY = FRP_QP_YWAVE;
     double sx[16];       // QP: this lane's block of S_xx
 #pragma unroll
     for (int i = 0; i < 16; i++) sx[i] = 0.0;
@@ -2291,13 +2180,8 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     // scratch_load, s_waitcnt vmcnt(0), use, next scratch_load), on the wave that is the long pole of every one of them.  Those values live in LDS instead:
     // four slots per lane at the record's end (lane (k, half): slots 4 half .. 4 half + 3 of stage k -- b of its two rows, then their second-order terms),
     // written and read by their own lane only.
-#if defined(FRP_QL) && !defined(FRP_QS) && FRP_Q4_PARK
     constexpr bool PARK = QW && FREG && IS_F && FL <= 2;
-    constexpr int R_PRK = RQ_MTRIG;
-#else
-    constexpr bool PARK = false;
-    constexpr int R_PRK = 0;
-#endif
+    constexpr int R_PRK = QW ? RQ_MTRIG : 0;
     ldouble *const prk = recs + (k < NP ? k : 0) * RS + R_PRK + 4 * (half < 3 ? half : 0);
 
     // face t of this lane is row j = t * H + half of its stage; its constants come from registers or from the parameters
@@ -2309,11 +2193,7 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     const int halfc = half < H ? half : H - 1;
     // (pointers into GLOBAL memory by type: behind the opaque asm of face_bases() a generic pointer's loads are FLAT instructions, which count on the LDS counter as well --
     // every wait for a row constant then drains the wave's LDS reads, and the other way round)
-#ifdef FRP_ROWS_FLAT // (experiment knob: the generic pointers of rounds 2-5)
-    typedef const double gcdouble;
-#else
     typedef const __attribute__((address_space(1))) double gcdouble;
-#endif
     gcdouble *pkA = (gcdouble *)(pk + NPRE + 3 * halfc), *pkB = (gcdouble *)(pk + NPRE + 3 * M + halfc);
     auto face_bases = [&]() {
         if constexpr (!FREG) {
@@ -2330,16 +2210,12 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     // 8.9 k cycles in the evaluation / affine / step phases at 30 rows per stage against 6.1 / 3.3 / 2.6 k at 6); the constants of
     // FCH rows are now fetched together, unconditionally (every row index of the lane is inside the stage's block when M covers
     // FL * H rows -- else the row-by-row form), and only their use is predicated.
-#ifndef FRP_FCH // experiment knob: rows per fetch
-#define FRP_FCH 5
-#endif
-    constexpr int FCH = (!FREG && FL % FRP_FCH == 0) ? FRP_FCH : 1;
+    constexpr int FCH = (!FREG && FL % 5 == 0) ? 5 : 1; // rows per fetch
     const bool rows_in_block = M >= FL * H;
     auto for_faces = [&](auto body) __attribute__((always_inline)) {
         if constexpr (FREG || FCH == 1) {
 #pragma unroll
             for (int t = 0; t < FL; t++) {
-                FRP_RSB();
                 if (t * H + half < nfk) {
                     double a0, a1, a2, bb;
                     face_consts(t, a0, a1, a2, bb);
@@ -2376,17 +2252,9 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     // The 17 bound pairs of a stage are shared by waves 2 and 3: rounds [RB0, RB1) of the row mapping each (wave 3 also
     // owns the corridor rows), so that neither is the long pole of the element-wise phases.
     // (measured: a corridor row costs about as much as 1.5 bound pairs because of its cross-lane sums)
-#ifndef FRP_RSPLIT_ADJ // experiment knob: bound rounds moved from the faces wave to the bounds wave
-#define FRP_RSPLIT_ADJ 0
-#endif
-    constexpr int RSPLIT0 = R - (FL <= 2 ? R / 3 : (FL <= 5 ? R / 6 : 0));
-#ifndef FRP_RSPLIT_ADJ32 // (same, for the N <= 32 variants only)
-#define FRP_RSPLIT_ADJ32 0
-#endif
-    constexpr int RSPLIT_ADJ_ = FRP_RSPLIT_ADJ + ((NP == 32 || NP == 30) ? FRP_RSPLIT_ADJ32 : 0);
-    constexpr int RSPLIT = RSPLIT0 + RSPLIT_ADJ_ <= R ? RSPLIT0 + RSPLIT_ADJ_ : R;
-    constexpr int RQ = R - FRP_Q4_RM;
-    constexpr int RB0 = QW ? (wave == 1 ? RQ : 0) : (IS_F ? RSPLIT : 0), RB1 = QW ? (wave == 1 ? R : RQ) : (IS_F ? R : RSPLIT);
+    constexpr int RSPLIT = R - (FL <= 2 ? R / 3 : (FL <= 5 ? R / 6 : 0));
+    // (Q4: every bound round on wave 2)
+    constexpr int RB0 = QW ? (wave == 1 ? R : 0) : (IS_F ? RSPLIT : 0), RB1 = QW ? R : (IS_F ? R : RSPLIT);
     // evaluation: residuals, barrier Hessian / predictor rhs of this wave's bound rows -> record; norms
     auto bounds_eval = [&](double &l_in, double &l_rc, double &l_gap) {
         if (!kact) return;
@@ -2395,7 +2263,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         const int halfp = opq(half);
 #pragma unroll
         for (int r = RB0; r < RB1; r++) {
-            FRP_RSB();
             const int ib = r * H, i = ib + half;
             if (i >= NZ) continue;
             const double hd = ROW_PICK(cq.hd(i));
@@ -2425,7 +2292,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         const int halfp = opq(half);
 #pragma unroll
         for (int r = RB0; r < RB1; r++) {
-            FRP_RSB();
             const int ib = r * H, i = ib + half;
             if (i >= NZ) continue;
             const double hd = ROW_PICK(cq.hd(i));
@@ -2468,7 +2334,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         const int halfp = opq(half);
 #pragma unroll
         for (int r = RB0; r < RB1; r++) {
-            FRP_RSB();
             const int ib = r * H, i = ib + half;
             if (i >= NZ) continue;
             const double lb = ROW_PICK(lower_bound(i));
@@ -2560,7 +2425,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         if constexpr (IS_B) {
 #pragma unroll
             for (int r = RB0; r < RB1; r++) {
-            FRP_RSB();
                 bsl[r] += shift; bsu[r] += shift;
                 bll[r] = a.mu0 / bsl[r]; blu[r] = a.mu0 / bsu[r];
             }
@@ -2591,35 +2455,22 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     bool gn_retry = false;              // this iteration is being redone with the Gauss-Newton Hessian
     Norms nm = {0, 0, 0, 0, 0, 0};
     double mu = 0.0, step_cc = 0.0;
-#ifndef FRP_R_PRIO
-#define FRP_R_PRIO 0
-#endif
-#ifndef FRP_H_PRIO
-#define FRP_H_PRIO 2
-#endif
     // Issue priority: the element-wise waves above the Riccati waves.  A SIMD hosts one wave of each of the three resident
     // workgroups; the short VALU-dense phases of one problem (model, bounds, faces) otherwise queue behind the long sweep
     // of another and take twice their stand-alone time, while a sweep (MFMA / latency bound) barely notices the extra
     // VALU traffic: measured 1.712 vs 1.743 ms per 4096-problem launch (the opposite assignment: no difference to none).
-    if constexpr (wave == 0) __builtin_amdgcn_s_setprio(FRP_R_PRIO);
-    else __builtin_amdgcn_s_setprio(FRP_H_PRIO);
+    constexpr int R_PRIO = 0, H_PRIO = 2;
+    if constexpr (wave == 0) __builtin_amdgcn_s_setprio(R_PRIO);
+    else __builtin_amdgcn_s_setprio(H_PRIO);
 
-    // Which wave runs the forward sweeps (experiment knobs; 0 = the Riccati wave itself).  With three workgroups per CU the
-    // roles are placed by SIMD and SIMD 3 hosts no Riccati wave: a sweep handed to the wave that sits there (role 3) takes
-    // its issue cycles off the SIMD the Riccati wave shares with two helpers of the other resident problems.
-#ifndef FRP_FWD_WAVE_P
-#define FRP_FWD_WAVE_P 0
-#endif
-#ifndef FRP_FWD_WAVE_C
-#define FRP_FWD_WAVE_C 0
-#endif
-    constexpr int FWD_P = NP == 20 ? FRP_FWD_WAVE_P : 0, FWD_C = NP == 20 ? FRP_FWD_WAVE_C : 0;
+    // (the forward sweeps run on the Riccati wave itself.  With three workgroups per CU the roles are placed by SIMD and SIMD 3 hosts no
+    // Riccati wave; handing a sweep to the wave that sits there (role 3) was measured and dropped: DESIGN_HISTORY)
     PROF_DECL();
     // (Q4 with the corridor rows on the Riccati wave: that wave runs its element-wise phases at the helpers' priority, the sweeps at its own)
     constexpr bool W0H = QW && wave == 0 && IS_F;
     for (it = 0;;) {
         // ============================================================ evaluation phase
-        if constexpr (W0H) __builtin_amdgcn_s_setprio(FRP_H_PRIO);
+        if constexpr (W0H) __builtin_amdgcn_s_setprio(H_PRIO);
         if constexpr (wave == 0) {
             if (hact) {
                 HessState hs; // the model wave's values before the last step + the step
@@ -2657,19 +2508,15 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         // (Q4, corridor rows on the model wave: their state does not fit beside the model phase's temporaries -- ~25 scratch accesses, 14.9 k
         // cycles for the phase instead of ~10 k.  Measured and dropped: evaluating the rows first, parking their 15 doubles in the global
         // workspace across the model phase and fetching them back in one batch behind it -- the barrier waits for the loads: 18.7 k.)
-        // Q4, corridor rows on the model wave: which of the two runs first (FRP_Q4_FACES_FIRST: the rows' residuals only need z; with the
-        // rows ahead of the model their accumulators are dead before the model's temporaries come alive -- VERDICT r05 item 1a / DESIGN 9.5-5b)
-#ifndef FRP_Q4_FACES_FIRST
-#define FRP_Q4_FACES_FIRST 0
-#endif
-        constexpr bool FACES_FIRST = QW && IS_M && IS_F && FRP_Q4_FACES_FIRST;
+        // Q4, corridor rows on the model wave: the model runs first (the rows ahead of the model -- their residuals only need z, and their accumulators
+        // would be dead before the model's temporaries come alive -- measured and dropped: VERDICT r05 item 1a / DESIGN 9.5-5b)
 #ifdef FRP_PROFILE_W1 // (profile build) where the model + corridor wave spends its evaluation phase: slots 16.. of the segment counters
         long long w1t_ = clock64();
 #define W1_SEG(i) do { if constexpr (IS_M) { const long long tn_ = clock64(); if (lane == 0) atomicAdd((unsigned long long *)&g_prof_seg[16 + (i)], (unsigned long long)(tn_ - w1t_)); w1t_ = tn_; } } while (0)
 #else
 #define W1_SEG(i)
 #endif
-        if constexpr (IS_M && !FACES_FIRST) { model_block(); W1_SEG(0); }
+        if constexpr (IS_M) { model_block(); W1_SEG(0); }
         if constexpr (IS_BO) {
             double l_in = 0.0, l_rc = 0.0, l_gap = 0.0;
             bounds_eval(l_in, l_rc, l_gap);
@@ -2712,7 +2559,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
             publish(xs, wave, lane, 0, wave_max(l_in)); publish(xs, wave, lane, 1, wave_max(l_rc)); publish(xs, wave, lane, 2, wave_sum_mx(l_gap));
             W1_SEG(1);
         }
-        if constexpr (FACES_FIRST) { FRP_SB(); model_block(); W1_SEG(0); }
         if constexpr (wave == 2) { // the budget's decision of this iteration (Ctl::tmo), behind no hand-counted LDS waits
             if (a.deadline) {
                 const unsigned long long now = wall_now();
@@ -2720,20 +2566,8 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
             }
         }
         BAR_P(0); // ------------------------------------------------------------- A
-        // FRP_EARLY_FACTOR: the Riccati wave does not take part in the termination test -- ~2 k cycles of LDS reads and reductions in front of
-        // its 46 k-cycle predictor, on the chain of every iteration -- but starts the factorisation at once; the helper waves, idle until
-        // barrier C anyway, take the decision and leave it in Ctl::dec_*; the factorisation sweep looks for it between its passes and the
-        // wave leaves the iteration like the others when it says "stop" (once per solve: a few stages of a sweep nobody needs).  What the
-        // wave needs of the norms later (mu, for the centring parameter) it reads from the partial results after its sweeps; the values
-        // it reports at exit it computes there.
-#ifndef FRP_EARLY_FACTOR
-#define FRP_EARLY_FACTOR 0
-#endif
-        constexpr bool EARLY = FRP_EARLY_FACTOR && !TW && FWD_P == 0;
-        constexpr bool EARLY_R = EARLY && wave == 0;
-        const unsigned dec_want = ((unsigned)b << 8) | (unsigned)(it & 255);
         bool tw_next = false;
-        if constexpr (!EARLY_R) {
+        {
             // (workgroup-uniform scalars that live across phases go to scalar registers: the element-wise roles are at the
             // 168-VGPR cap of three workgroups per CU, and every spilled value is an L2 round trip on an in-order wavefront)
             nm.eq = uni(red(xs, WEQ, 0));
@@ -2751,9 +2585,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
                 else if (uni(sh.ctl->tmo)) { stop_flag = FRP_EXIT_TIMEOUT; stop = 1; } // (Ctl::tmo: 0 without a budget)
                 else if (mu > a.diverge_mu * fmax(1.0, a.mu0) || nm.rs > DIVERGE_RS) { stop_flag = FRP_EXIT_NOPROGRESS; stop = 1; }
             }
-            if constexpr (EARLY && wave == 2) {
-                if (lane == 0) { sh.ctl->dec_flag = stop_flag; sh.ctl->dec_stop = stop; __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); *(volatile unsigned *)&sh.ctl->dec_tag = dec_want; }
-            }
             if (stop) { flag = stop_flag; break; }
         }
         if constexpr (QW && wave == 0) { // a long solve: it takes the CU for itself (see claim_next)
@@ -2769,7 +2600,7 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         }
 
         // ============================================================ predictor: factorisation + forward sweep
-        if constexpr (W0H) __builtin_amdgcn_s_setprio(FRP_R_PRIO);
+        if constexpr (W0H) __builtin_amdgcn_s_setprio(R_PRIO);
         if (TW && !tw_it) { // (twisted variants, end game: the plain recursion -- behind ONE call, so that the twisted path keeps its registers)
             if constexpr (wave == 0) {
                 const int fr = endgame_predictor(recs, xs, N, gn_retry ? 0.0 : theta_h FRP_GP_ARG(pws));
@@ -2810,33 +2641,12 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
             }
         } else if constexpr (wave == 0) {
             SWEEP_T0();
-            lctl_t *lctl = (lctl_t *)sh.ctl;
-            int fr = sweep_factor<false, EARLY>(recs, xs, N, gn_retry ? 0.0 : theta_h FRP_GP_ARG(pws), lctl, dec_want);
-            if constexpr (EARLY) {
-                bool stopped = (fr & 2) != 0;
-                if (!stopped && !(fr & 4)) { // the sweep is through and the helpers' decision is not in yet (never observed to take that long)
-                    while (uni((int)*(volatile __attribute__((address_space(3))) unsigned *)&lctl->dec_tag) != (int)dec_want) __builtin_amdgcn_s_sleep(1);
-                    stopped = uni(*(volatile __attribute__((address_space(3))) int *)&lctl->dec_stop) != 0;
-                }
-                if (stopped) {
-                    flag = uni(*(volatile __attribute__((address_space(3))) int *)&lctl->dec_flag);
-                    if constexpr (QP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    break;
-                }
-                fr &= 1;
-            }
+            const int fr = sweep_factor<false>(recs, xs, N, gn_retry ? 0.0 : theta_h FRP_GP_ARG(pws));
             SWEEP_T1(0);
-            if (FWD_P == 0 && !fr) sweep_forward(recs, xs, N);
+            if (!fr) sweep_forward(recs, xs, N);
             SWEEP_T1(1);
             if (lane == 0) sh.ctl->fail = fr;
             if constexpr (QP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the P stores of the factorisation sweep (long retired by now)
-            if constexpr (EARLY) { nm.gap = uni(rsum(2)); mu = uni(nm.gap * (KAPPA_LAM * inv_kmtot)); } // (for the centring parameter behind barrier D)
-        }
-        if constexpr (FWD_P != 0 && !TW) { // the forward sweep works from the records alone: it runs on the wave whose SIMD has room
-            BAR();
-            if constexpr (wave == FWD_P) {
-                if (!sh.ctl->fail) sweep_forward(recs, xs, N);
-            }
         }
         BAR_P(1); // ------------------------------------------------------------- C
         {
@@ -2868,7 +2678,7 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         }
 
         // ============================================================ affine step: lengths, second-order term, corrector rhs
-        if constexpr (W0H) __builtin_amdgcn_s_setprio(FRP_H_PRIO);
+        if constexpr (W0H) __builtin_amdgcn_s_setprio(H_PRIO);
         if constexpr (IS_BO) {
             double m_p = 0.0, m_d = 0.0, s_sdl = 0.0, s_lds = 0.0, s_dsdl = 0.0;
             bounds_affine(m_p, m_d, s_sdl, s_lds, s_dsdl);
@@ -2935,20 +2745,10 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
             }
         }
 
-        // QP: the bounds wave -- idle until barrier E -- fetches its block of S_xx (16 doubles per lane, one 128-byte line: the lane's
-        // diagonal block and the block to its right, stored by the factorisation sweep of this iteration) for the y+ rows of the step phase
-        // (FRP_QP_YWAVE = 2; the default is the Riccati wave, which fetches at the start of the step phase: the bounds wave has no
-        // room for 32 more registers between the barriers D and F -- 310 spilled VGPRs instead of 126)
-        if constexpr (wave == WY && WY != 0 && QP) fetch_sx();
-#ifndef FRP_QP_TOUCH // experiment knob: the bounds wave -- idle from here to barrier E -- reads one word of every 128-byte line of this workgroup's S_xx blocks, so
-#define FRP_QP_TOUCH 0 // that the Riccati wave's fetch at the head of the step phase finds them in the CU's vector cache (one register, waited for before barrier E)
-#endif
-        unsigned touch_ = 0;
-        if constexpr (FRP_QP_TOUCH != 0 && QP && !QS && WY == 0 && IS_BO) {
-            const char *tp_ = (const char *)pws + (unsigned)(lane < 3 * N ? lane : 0) * 128u;
-            asm volatile("global_load_dword %0, %1, off" : "=v"(touch_) : "v"(tp_) : "memory");
-        }
-        if constexpr (W0H) __builtin_amdgcn_s_setprio(FRP_R_PRIO);
+        // (QP: the Riccati wave forms y+ and fetches its block of S_xx at the start of the step phase.  Measured and dropped: the fetch on the bounds wave,
+        // idle from here to barrier E -- no room for 32 more registers between the barriers D and F, 310 spilled VGPRs instead of 126 -- and that wave
+        // touching the lines so that the Riccati wave's fetch finds them in the CU's vector cache)
+        if constexpr (W0H) __builtin_amdgcn_s_setprio(R_PRIO);
 
         // ============================================================ corrector: vector backward sweep + forward sweep with y+
         if (TW && !tw_it) {
@@ -2980,18 +2780,13 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
             SWEEP_T0();
             sweep_backvec<false>(recs, xs, N, smu);
             SWEEP_T1(2);
-            if (FWD_C == 0) sweep_forward(recs, xs, N);
+            sweep_forward(recs, xs, N);
             SWEEP_T1(3);
         }
-        if constexpr (FWD_C != 0 && !TW) {
-            BAR();
-            if constexpr (wave == FWD_C) sweep_forward(recs, xs, N);
-        }
-        if constexpr (FRP_QP_TOUCH != 0 && QP && !QS && WY == 0 && IS_BO) asm volatile("s_waitcnt vmcnt(0)" : "+v"(touch_) : : "memory");
         BAR_P(3); // ------------------------------------------------------------- E
 
         // ============================================================ step: pass A (ratios), pass B (commit)
-        if constexpr (W0H) __builtin_amdgcn_s_setprio(FRP_H_PRIO);
+        if constexpr (W0H) __builtin_amdgcn_s_setprio(H_PRIO);
         double m_p = 0.0, m_d = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0; // q: sums of ds l, s dl, ds dl
         double dzf[3];                            // wave 3: dz of pos (the commit reads every dz from the record again: nothing is carried across barrier F)
         // one constraint of the corrector step
@@ -3019,11 +2814,10 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         //     y_w = Phi_w dw + hc (du + kbar) + p_w        (the w rows of P are [Phi_w - hc^2 R | -hc Kbar_x] and du = -(hc R dw + Kbar_x dx + kbar))
         //     y_x = S_xx dx - hc Kbar_x' dw + p_x          (lane a of a stage: rows 3a .. 3a+2; S_aa and S_{a,a+1} are its own, the
         //                                                   contribution S_{a,a+1}' dx_a goes to the lane that owns the rows a+1)
-        if constexpr (wave == WY && QP && QS) {
+        if constexpr (wave == 0 && QP && QS) {
             // Q30: the lane of a stage forms all thirteen rows itself -- its three blocks of S_xx (block b: S_bb lower triangle, then S_{b,b+1} row-major, b + 1 cyclic:
             // every unique entry of the symmetric 9 x 9 once) in one trip to the L2, T', p, Phi_w, hc from its record; no hand-over between lanes
-            static_assert(WY == 0, "Q30: y+ on the Riccati wave");
-            __builtin_amdgcn_s_setprio(FRP_H_PRIO);
+            __builtin_amdgcn_s_setprio(H_PRIO);
             if (hact) {
                 typedef double gd2 __attribute__((ext_vector_type(2)));
                 ldouble *rec = recs + k * RS;
@@ -3065,9 +2859,9 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
 #pragma unroll
                 for (int g = 0; g < 4; g++) rec[R_D + g] = yw[g];
             }
-            __builtin_amdgcn_s_setprio(FRP_R_PRIO);
-        } else if constexpr (wave == WY && QP) {
-            if constexpr (WY == 0) { __builtin_amdgcn_s_setprio(FRP_H_PRIO); fetch_sx(); } // (one trip to the L2 on the path: 8 x 16 bytes per lane)
+            __builtin_amdgcn_s_setprio(R_PRIO);
+        } else if constexpr (wave == 0 && QP) {
+            __builtin_amdgcn_s_setprio(H_PRIO); fetch_sx(); // (one trip to the L2 on the path: 8 x 16 bytes per lane)
             ldouble *rec = recs + k * RS;
             const int aq = opq(half) < 3 ? opq(half) : 2, ia = 3 * aq, ib = aq == 2 ? 0 : ia + 3;
             double ux[3], yw[4];
@@ -3115,7 +2909,7 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
                     for (int g = 0; g < 4; g++) rec[R_D + g] = yw[g];
                 }
             }
-            if constexpr (WY == 0 && !W0H) __builtin_amdgcn_s_setprio(FRP_R_PRIO);
+            if constexpr (!W0H) __builtin_amdgcn_s_setprio(R_PRIO);
         }
         if constexpr (wave == 1 && QP) {
             if (own0) { // the values before the step, for the Hessian lanes (T' slots the y+ lanes do not read)
@@ -3171,7 +2965,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         const int halfp = opq(half);
 #pragma unroll
         for (int r = RB0; r < RB1; r++) {
-            FRP_RSB();
                     const int ib = r * H, i = ib + half;
                     if (i >= NZ) continue;
                     const double lb = ROW_PICK(lower_bound(i));
@@ -3222,7 +3015,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
         const int halfp = opq(half);
 #pragma unroll
         for (int r = RB0; r < RB1; r++) {
-            FRP_RSB();
                     const int ib = r * H, i = ib + half;
                     if (i >= NZ) continue;
                     const double lb = ROW_PICK(lower_bound(i));
@@ -3262,13 +3054,6 @@ __device__ __forceinline__ void solve_one(const KernelArgs &a, const int b, cons
     }
 
     // ---------------------------------------------------------------- outputs
-#if FRP_EARLY_FACTOR
-    if constexpr (wave == 0 && !TW) { // (the Riccati wave skipped the termination tests: what it reports it computes here, from the same partial results)
-        nm.eq = uni(red(xs, WEQ, 0)); nm.in = uni(rmax(0)); nm.rc = uni(rmax(1)); nm.gap = uni(rsum(2));
-        nm.rs = uni(stationarity_norm<NP>(recs, N));
-        mu = uni(nm.gap * (KAPPA_LAM * inv_kmtot));
-    }
-#endif
     PROF_FLUSH(wave, it);
     __builtin_amdgcn_s_setprio(0);
     // the next problem is claimed only now (its latency hides behind the write-out): a slot that claimed it while it still
@@ -3317,11 +3102,8 @@ template <int NP, int FL, bool FREG, int ROLE, bool TW>
 __device__ __forceinline__ void role_loop(const KernelArgs &a, const Shared &sh)
 {
     // (solve_one claims the next problem when it leaves its iteration)
-#ifndef FRP_STAGGER // experiment knob: the k-th workgroup of a CU starts its first solve k * FRP_STAGGER * 8 k cycles late (the four workgroups of a
-#define FRP_STAGGER 0 // CU otherwise run the first round of a launch in lockstep -- 46 us per iteration against 41 later: profiles/r05_timeline.txt)
-#endif
-    if (QW && FRP_STAGGER > 0 && ROLE == 0 && sh.rsimd > 0)
-        for (int q = 0; q < sh.rsimd * FRP_STAGGER; q++) __builtin_amdgcn_s_sleep(127);
+    // (the four workgroups of a CU run the first round of a launch in lockstep -- 46 us per iteration against 41 later; starting them staggered
+    // was measured and dropped: profiles/r05_timeline.txt)
     if (ROLE == 0 && (threadIdx.x & 63) == 0) {
         const int hf = QW ? sh.ctl->head_first : -1;
         if (hf >= 0) sh.ctl->next = a.order ? a.order[hf] : hf; // a head-start problem: this workgroup was first on its CU and has marked it
@@ -3341,28 +3123,16 @@ __device__ __forceinline__ void role_loop(const KernelArgs &a, const Shared &sh)
     }
 }
 
-#ifdef FRP_NUM_VGPR // experiment knob: a hard register cap for every kernel of the translation unit (the waves-per-EU attribute is relaxed by the compiler when the LDS size limits the occupancy anyway)
-#define FRP_VGPR_ATTR __attribute__((amdgpu_num_vgpr(FRP_NUM_VGPR)))
-#else
-#define FRP_VGPR_ATTR
-#endif
 template <int NP, int FL, bool FREG, int WPE, bool TW>
-__global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) FRP_VGPR_ATTR void nmpc_ipm_lds_kernel(KernelArgs a)
+__global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void nmpc_ipm_lds_kernel(KernelArgs a)
 {
     static_assert(!(QW && QL) || (size_t)(NP * RS + X_TOTAL + 3 * NP + 1) * 8 + sizeof(Ctl) + 5 * sizeof(int) <= 40960, "Q4: four workgroups per CU in 160 KB of LDS");
     static_assert(!QS || (size_t)(NP * RS + X_TOTAL + 1) * 8 + sizeof(Ctl) + 5 * sizeof(int) <= 53248, "Q30: three workgroups per CU in 160 KB of LDS");
-#ifdef FRP_DYN_LDS // experiment knob (round 6): LDS sized at launch -- the compiler then cannot tell that the LDS limits the occupancy below WPE and keeps the register cap of WPE waves per SIMD
-    extern __shared__ double s_dyn_[];
-    double *s_recs = s_dyn_, *s_xs = s_recs + NP * RS, *s_tw = s_xs + X_TOTAL + (QS ? 0 : 3 * NP);
-    Ctl &s_ctl = *reinterpret_cast<Ctl *>(s_tw + (TW ? TW_TOTAL : 1));
-    int *s_place = reinterpret_cast<int *>(&s_ctl + 1);
-#else
     __shared__ double s_recs[NP * RS];
     __shared__ double s_xs[X_TOTAL + (QS ? 0 : 3 * NP)];
     __shared__ double s_tw[TW ? TW_TOTAL : 1];
     __shared__ Ctl s_ctl;
     __shared__ int s_place[5];
-#endif
     static_assert(!TW || NP == 20, "the twisted solve is built on the three-lanes-per-stage model phase");
     Shared sh;
     sh.recs = (ldouble *)s_recs; sh.xs = (ldouble *)s_xs; sh.tw = (ldouble *)s_tw; sh.ctl = &s_ctl; sh.cukey = -1; sh.late = 0; sh.rsimd = -1;
@@ -3386,16 +3156,13 @@ __global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(
     // against the dispatcher's own rotation, so it is applied to the three-per-CU variants only.)
     const int widx = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int role = widx;
-#ifndef FRP_NO_PLACE
-#define FRP_NO_PLACE 0
-#endif
     if constexpr (QW) {
         // Q4: four workgroups of three wavefronts per CU -- twelve waves, three per SIMD.  Every workgroup claims a SIMD for its Riccati
         // wave that no other workgroup's Riccati wave has taken (a bit mask per CU in the workspace, zeroed by the launcher), trying the
         // SIMDs its own waves sit on; its other two waves take the roles 1 and 2 in the cyclic order of their SIMDs behind the claimed
         // one, so that with the dispatcher's rotation {s, s+1, s+2} every SIMD ends up with one Riccati wave, one model + bounds wave
         // and one faces + bounds wave.  Anything unexpected (two waves on one SIMD, no free SIMD) falls back to role = wave index.
-        if (a.cu_slots && !FRP_NO_PLACE) {
+        if (a.cu_slots) {
             const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
             const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
             const int simd = (int)((hw >> 4) & 3u);
@@ -3443,7 +3210,7 @@ __global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(
             if (threadIdx.x == 0) atomicAdd((unsigned long long *)&g_prof_seg[24 + (rs >= 0 ? rs : 4)], 1ull);
 #endif
         }
-    } else if (WPE >= 3 && a.cu_slots && !FRP_NO_PLACE) {
+    } else if (WPE >= 3 && a.cu_slots) {
         const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);   // HW_REG_HW_ID: SIMD_ID [5:4], CU_ID [11:8], SH_ID [12], SE_ID [15:13]
         const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);  // HW_REG_XCC_ID [3:0]
         const int simd = (int)((hw >> 4) & 3u);
@@ -3457,23 +3224,13 @@ __global__ __launch_bounds__(QW ? 192 : 256) __attribute__((amdgpu_waves_per_eu(
         const bool distinct = ((1 << s0) | (1 << s1) | (1 << s2) | (1 << s3)) == 15;
         if (distinct && arrival < 3) {
             const int rs = arrival; // SIMD of this workgroup's Riccati wave
-            // the two SIMDs that are neither rs nor 3, in increasing order, take the roles 2 and 3
-            int lo = -1;
-            for (int q = 0; q < 3; q++)
-                if (q != rs && lo < 0) lo = q;
-#ifndef FRP_PLACE_CYCLIC
-#define FRP_PLACE_CYCLIC 1
-#endif
             // SIMD 3 hosts no Riccati wave: it takes the heaviest helper (the faces wave); model and bounds go to the other two
             // SIMDs, cyclically, so that every Riccati wave shares its SIMD with one of each
-            const int s_model = FRP_PLACE_CYCLIC ? (rs + 1) % 3 : lo;
+            const int s_model = (rs + 1) % 3;
             role = simd == rs ? 0 : (simd == 3 ? 3 : (simd == s_model ? 1 : 2));
-#ifndef FRP_TW_PLACE // (0: the placement of the plain solve)
-#define FRP_TW_PLACE 1
-#endif
             // twisted variants: the model wave runs the first half's sweeps, so IT is the heaviest helper and takes SIMD 3 (measured against
             // the plain placement, m = 9: 768 problems 468 -> 447 us, 1024: 631 -> 619; 4096 problems, m = 6: 1.021 -> 0.974 ms)
-            if (TW && FRP_TW_PLACE) role = simd == rs ? 0 : (simd == 3 ? 1 : (simd == s_model ? 3 : 2));
+            if (TW) role = simd == rs ? 0 : (simd == 3 ? 1 : (simd == s_model ? 3 : 2));
         }
     }
     // one copy of the solver loop per role: the four waves run different code between the same barriers
@@ -3506,14 +3263,7 @@ static hipError_t launch_variant(const KernelArgs &k, int slots, hipStream_t str
         lds_selected_name = name;
         return hipSuccess;
     }
-#ifdef FRP_DYN_LDS
-    const size_t lds = (size_t)(NP * RS + X_TOTAL + (QS ? 0 : 3 * NP) + (TW ? TW_TOTAL : 1)) * 8 + sizeof(Ctl) + 5 * sizeof(int) + 16;
-    static bool once = [&] { return hipFuncSetAttribute(reinterpret_cast<const void *>(&nmpc_ipm_lds_kernel<NP, FL, FREG, WPE, TW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess; }();
-    (void)once;
-    hipLaunchKernelGGL((nmpc_ipm_lds_kernel<NP, FL, FREG, WPE, TW>), dim3(slots), dim3(QW ? 192 : 256), lds, stream, k);
-#else
     hipLaunchKernelGGL((nmpc_ipm_lds_kernel<NP, FL, FREG, WPE, TW>), dim3(slots), dim3(QW ? 192 : 256), 0, stream, k);
-#endif
     return hipGetLastError();
 }
 // the twisted variants: frp_nmpc_options.twist = m (stages eliminated forward), -1 = 9 N / 20 (3 N / 10 beyond 1024 problems); anything the twisted solve does not cover
@@ -3526,30 +3276,35 @@ static inline int twist_stages(const KernelArgs &k)
     return (k.N >= 4 && k.N <= 20 && m >= 2 && m <= k.N - 2) ? m : 0;
 }
 
-} // namespace lr / lrq
+#ifdef FRP_PROFILE
+// read and reset this translation unit's copy of the profile counters (exported under the unit's own name at the end of the file)
+static void read_prof_lds(long long *out)
+{
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof_lds), sizeof(long long) * 64);
+    (void)hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(g_prof_seg), sizeof(long long) * 32);
+    long long z[64] = {0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof_lds), z, sizeof z);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_prof_seg), z, sizeof(long long) * 32);
+}
+#endif
 
-// Two translation units (build.py): the variants that keep the corridor rows in registers (FREG) are compiled with
+} // namespace lr / lrq / lrs / lr2
+
+// Five translation units (build.py), each with its launcher.  The variants that keep the corridor rows in registers (FREG) are compiled with
 // -amdgpu-use-amdgpu-trackers=1 (-4 % on the (20, 2) variant of the headline workload), the variants that re-read them from
-// the parameters without it (the same flag costs them 2-10 %).  frp_ipm_lds_mem.hip includes this file with FRP_LDS_MEM_TU
-// and contributes launch_ipm_lds_mem only; a build that defines neither macro (probes, experiments) gets everything here.
+// the parameters without it (the same flag costs them 2-10 %): frp_ipm_lds_mem.hip includes this file with FRP_LDS_MEM_TU
+// and contributes launch_ipm_lds_mem only.  This file compiled as itself is the main unit: its own variants and the selection among all of them.
 #if defined(FRP_LDS_Q4_TU)
 // frp_ipm_lds_q4.hip: the four-problems-per-CU variants (three-wave workgroups, P in global memory); contributes launch_ipm_lds_q4 only
 hipError_t launch_ipm_lds_q4(const KernelArgs &k, int slots, hipStream_t stream)
 {
-#ifdef FRP_Q4_MORE_ROWS // experiment (round 6): the four-per-CU form for up to 15 rows in registers / up to 30 rows re-read (the tick's 30-row stages)
-    if (k.MF > 15) return FRP_LR::launch_variant<20, 10, false, 3>(k, slots, stream);
-    if (k.MF > 6) return FRP_LR::launch_variant<20, 5, true, 3>(k, slots, stream);
-#endif
     return FRP_LR::launch_variant<20, 2, true, 3>(k, slots, stream);
 }
 #elif defined(FRP_LDS_Q30_TU)
 // frp_ipm_lds_q30.hip: N <= 30, <= 16 corridor rows, three problems per CU (215-double records, P in global memory); contributes launch_ipm_lds_q30 only
-#ifndef FRP_Q30_FREG
-#define FRP_Q30_FREG 1
-#endif
 hipError_t launch_ipm_lds_q30(const KernelArgs &k, int slots, hipStream_t stream)
 {
-    return FRP_LR::launch_variant<30, 8, (FRP_Q30_FREG != 0), 3>(k, slots, stream);
+    return FRP_LR::launch_variant<30, 8, true, 3>(k, slots, stream);
 }
 #elif defined(FRP_LDS_S2_TU)
 // frp_ipm_lds_s2.hip: the small-launch variants (N <= 20, rows in registers, at most two problems per CU): the kernels of the main translation unit compiled for
@@ -3570,21 +3325,9 @@ hipError_t launch_ipm_lds_mem(const KernelArgs &k, int slots, hipStream_t stream
     if (k.N <= 32) return FRP_LR::launch_variant<32, 15, false, 2>(k, slots, stream);
     return FRP_LR::launch_variant<64, 30, false, 1>(k, slots, stream);
 }
-#else
-#ifdef FRP_PROFILE
-void debug_read_prof_lds(long long *out)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(FRP_LR::g_prof_lds), sizeof(long long) * 64);
-    (void)hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(FRP_LR::g_prof_seg), sizeof(long long) * 32);
-    long long z[64] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(FRP_LR::g_prof_lds), z, sizeof z);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(FRP_LR::g_prof_seg), z, sizeof(long long) * 32);
-}
-#endif
-
+#elif !defined(FRP_LDS_TEMPLATES_ONLY) // (a probe that wants the device templates of namespace frp::lr and no launcher: tools/ubench/sweep_timing.hip)
 // The Q4 variants (frp_ipm_lds_q4.hip) take the launches they cover: plain solve, N <= 20, at most six corridor rows per stage.
 // FRP_Q4=0 in the environment keeps the three-per-CU variants (A/B runs).
-#ifdef FRP_LDS_SPLIT_TU
 hipError_t launch_ipm_lds_q4(const KernelArgs &k, int slots, hipStream_t stream); // frp_ipm_lds_q4.hip
 hipError_t launch_ipm_lds_q30(const KernelArgs &k, int slots, hipStream_t stream); // frp_ipm_lds_q30.hip
 hipError_t launch_ipm_lds_s2(const KernelArgs &k, int slots, hipStream_t stream);  // frp_ipm_lds_s2.hip
@@ -3598,16 +3341,6 @@ static bool q30_enabled() // FRP_Q30=0 keeps the two-per-CU variants (A/B runs)
     static const bool on = [] { const char *e = getenv("FRP_Q30"); return !(e && e[0] == '0'); }();
     return on;
 }
-#else
-static hipError_t launch_ipm_lds_q4(const KernelArgs &, int, hipStream_t) { return hipErrorInvalidValue; }
-static hipError_t launch_ipm_lds_q30(const KernelArgs &, int, hipStream_t) { return hipErrorInvalidValue; }
-static bool q4_enabled() { return false; } // (a single-translation-unit build has one record layout)
-static bool q30_enabled() { return false; }
-#endif
-#if (defined(FRP_QP) || defined(FRP_QW)) && !defined(FRP_LDS_Q4_TU)
-static bool q4_covers(const KernelArgs &) { return false; } // (bisection builds: the launch stays on this translation unit)
-int lds_q4_max_rows() { return 6; }
-#else
 // ... and only launches with more problems than the three-per-CU variants hold at once: a problem that has a CU (nearly) to itself
 // iterates faster on four wavefronts (69 k cycles per iteration against 80 k: profiles/r05_wave_phases.txt)
 static int device_cus()
@@ -3623,20 +3356,15 @@ static int device_cus()
     return cus[dev];
 }
 static std::atomic<int> g_q4_min_b{[] { const char *e = getenv("FRP_Q4_MIN_B"); return e ? atoi(e) : -1; }()}; // (frp_nmpc_set_q4_min_batch, a process-wide tuning hook; -1: three workgroups per CU)
-int lds_q4_max_rows() { static const int m = [] { const char *e = getenv("FRP_Q4_MAXF"); return e ? atoi(e) : 6; }(); return m; } // (experiment knob: needs a -DFRP_Q4_MORE_ROWS build of the Q4 unit)
 static bool q4_covers(const KernelArgs &k)
 {
     const int B = k.variant_B > 0 ? k.variant_B : k.B; // (the chunks of a host batch: the whole batch's variant)
-    return q4_enabled() && k.pws && k.N <= 20 && k.MF <= lds_q4_max_rows() && FRP_LR::twist_stages(k) == 0 && B > (g_q4_min_b.load(std::memory_order_relaxed) >= 0 ? g_q4_min_b.load(std::memory_order_relaxed) : 3 * device_cus());
+    return q4_enabled() && k.pws && k.N <= 20 && k.MF <= LDS_Q4_MAX_ROWS && FRP_LR::twist_stages(k) == 0 && B > (g_q4_min_b.load(std::memory_order_relaxed) >= 0 ? g_q4_min_b.load(std::memory_order_relaxed) : 3 * device_cus());
 }
-#endif
 
 // The Q30 variant (frp_ipm_lds_q30.hip): 20 < N <= 30, at most 16 corridor rows per stage, plain solve, and a launch of at least ~2.3 rounds of its resident
 // workgroups (7 x CUs problems): the 168-register build is 6 % slower per iteration than the 243-register one, and measured on configs[3] the third slot per CU
 // pays from B = 2048 on (B = 512 / 1024 / 2048 / 4096 / 16384: 1.72 / 2.18 / 2.56 / 3.48 / 11.09 ms against 1.63 / 2.06 / 2.58 / 4.05 / 13.90 at two per CU)
-#if (defined(FRP_QP) || defined(FRP_QW)) && !defined(FRP_LDS_Q4_TU)
-static bool q30_covers(const KernelArgs &) { return false; }
-#else
 static bool q30_covers(const KernelArgs &k)
 {
     const int B = k.variant_B > 0 ? k.variant_B : k.B;
@@ -3645,19 +3373,14 @@ static bool q30_covers(const KernelArgs &k)
     const int min_b = set_b >= 0 ? set_b : env_b;
     return q30_enabled() && k.pws && k.N > 20 && k.N <= 30 && k.MF <= 16 && FRP_LR::twist_stages(k) == 0 && B > (min_b >= 0 ? min_b : 7 * device_cus());
 }
-#endif
 // Small launches (N <= 20, rows in registers, at most two problems per CU -- the drop-in call is the case of ONE): the same kernels compiled for two wavefronts per
 // SIMD, i.e. 256 registers instead of 168 -- no spills, nothing to fetch back on the chain: 0.1260 -> 0.1226 ms per drop-in call, 0.1142 -> 0.1095 with the twisted
 // solve (FRP_SMALL2=0 switches it off).  The choice goes by the size of the whole batch (variant_B), like that of the high-residency variants.
 static bool small2_covers(const KernelArgs &k)
 {
-#ifndef FRP_LDS_SPLIT_TU
-    return false; // (a build without the other translation units has no such variants)
-#endif
     static const int env = [] { const char *e = getenv("FRP_SMALL2"); return e ? atoi(e) : 1; }();
     const int B = k.variant_B > 0 ? k.variant_B : k.B;
-    static const int max_b = [] { const char *e = getenv("FRP_SMALL2_MAXB"); return e ? atoi(e) : 0; }(); // (experiments: the two-per-CU builds for larger batches too)
-    return env != 0 && k.N <= 20 && k.MF <= 30 && B <= (max_b > 0 ? max_b : 2 * device_cus()) && !q4_covers(k);
+    return env != 0 && k.N <= 20 && k.MF <= 30 && B <= 2 * device_cus() && !q4_covers(k);
 }
 // workgroups resident per CU: LDS-bound (4 x 40 KB on the Q4 variants; 3 x 51 KB, 3 x 52 KB on the Q30 variant, 2 x 79 KB, 1 x 157 KB), two by registers on the small-launch variants
 int lds_workgroups_per_cu(const KernelArgs &k) { return k.N <= 20 ? (q4_covers(k) ? 4 : (small2_covers(k) ? 2 : 3)) : (k.N <= 32 ? (q30_covers(k) ? 3 : 2) : 1); }
@@ -3666,29 +3389,12 @@ size_t lds_q30_pws_doubles_per_slot() { return (size_t)30 * FRP_LR::PG; }
 // doubles of packed-P workspace a resident workgroup of the Q4 variants needs (KernelArgs::pws)
 size_t lds_q4_pws_doubles_per_slot() { return (size_t)20 * FRP_LR::PG; }
 bool lds_q4_enabled() { return q4_enabled(); }
-#if (defined(FRP_QP) || defined(FRP_QW)) && !defined(FRP_LDS_Q4_TU)
-int lds_q4_set_min_batch(int) { return -1; }
-#else
 int lds_q4_set_min_batch(int min_b) { return g_q4_min_b.exchange(min_b < 0 ? -1 : min_b); }
-#endif
 
 bool lds_kernel_supports(int N, int MF) { return N >= 1 && N <= 64 && MF >= 0 && MF <= FRP_MAX_FACES; }
 
-#ifdef FRP_LDS_SPLIT_TU
 hipError_t launch_ipm_lds_mem(const KernelArgs &k, int slots, hipStream_t stream); // frp_ipm_lds_mem.hip
-#else
-static hipError_t launch_ipm_lds_mem(const KernelArgs &k, int slots, hipStream_t stream)
-{
-    if (k.N <= 20 && k.twist) return FRP_LR::launch_variant<20, 10, false, 3, true>(k, slots, stream);
-    if (k.N <= 20) return FRP_LR::launch_variant<20, 10, false, 3>(k, slots, stream);
-    if (k.N <= 32) return FRP_LR::launch_variant<32, 15, false, 2>(k, slots, stream);
-    return FRP_LR::launch_variant<64, 30, false, 1>(k, slots, stream);
-}
-#endif
 
-#ifndef FRP_WPE20 // experiment knob: register budget of the N <= 20 variants (3 waves per SIMD = 168 VGPRs; 4 = 128)
-#define FRP_WPE20 3
-#endif
 thread_local bool lds_select_only = false; // (frp_kernels.h: ipm_variant_name)
 thread_local const char *lds_selected_name = nullptr;
 
@@ -3702,67 +3408,31 @@ hipError_t launch_ipm_lds(const KernelArgs &k0, int slots, hipStream_t stream)
     const int MF = k.MF;
     if (q4_covers(k0)) return launch_ipm_lds_q4(k, slots, stream);
     if (q30_covers(k0)) return launch_ipm_lds_q30(k, slots, stream);
-#if (defined(FRP_QP) || defined(FRP_QW)) && !defined(FRP_LDS_Q4_TU) // bisection builds (parts of Q4 on the main translation unit): one variant
-    return (k.N <= 20 && MF <= 6 && !k.twist && k.pws) ? FRP_LR::launch_variant<20, 2, true, FRP_WPE20>(k, slots, stream) : hipErrorInvalidValue;
-#else
-#ifdef FRP_LDS_SPLIT_TU
     if (small2_covers(k0)) return launch_ipm_lds_s2(k, slots, stream);
-#endif
     if (k.N <= 20 && k.twist) {
-        if (MF <= 6) return FRP_LR::launch_variant<20, 2, true, FRP_WPE20, true>(k, slots, stream);
-        if (MF <= 15) return FRP_LR::launch_variant<20, 5, true, FRP_WPE20, true>(k, slots, stream);
+        if (MF <= 6) return FRP_LR::launch_variant<20, 2, true, 3, true>(k, slots, stream);
+        if (MF <= 15) return FRP_LR::launch_variant<20, 5, true, 3, true>(k, slots, stream);
     } else if (k.N <= 20) {
-        if (MF <= 6) return FRP_LR::launch_variant<20, 2, true, FRP_WPE20>(k, slots, stream);
-        if (MF <= 15) return FRP_LR::launch_variant<20, 5, true, FRP_WPE20>(k, slots, stream);
+        if (MF <= 6) return FRP_LR::launch_variant<20, 2, true, 3>(k, slots, stream);
+        if (MF <= 15) return FRP_LR::launch_variant<20, 5, true, 3>(k, slots, stream);
     } else if (k.N <= 32) {
         if (MF <= 6) return FRP_LR::launch_variant<32, 3, true, 2>(k, slots, stream);
-#ifndef FRP_N32_WPE // experiment knobs (round 6): register budget / rows in registers of the N <= 32, <= 16-row variant -- the proxy for three problems per CU
-#define FRP_N32_WPE 2
-#endif
-#ifndef FRP_N32_FREG
-#define FRP_N32_FREG 1
-#endif
-        if (MF <= 16) return FRP_LR::launch_variant<32, 8, (FRP_N32_FREG != 0), FRP_N32_WPE>(k, slots, stream);
+        if (MF <= 16) return FRP_LR::launch_variant<32, 8, true, 2>(k, slots, stream);
     } else if (MF <= 8) return FRP_LR::launch_variant<64, 8, true, 1>(k, slots, stream);
     return launch_ipm_lds_mem(k, slots, stream);
-#endif
 }
-#endif // FRP_LDS_MEM_TU
+#endif // the main unit
 
 } // namespace frp
 
-#if defined(FRP_PROFILE) && !defined(FRP_LDS_MEM_TU) && !defined(FRP_LDS_Q4_TU) && !defined(FRP_LDS_Q30_TU) && !defined(FRP_LDS_S2_TU)
-extern "C" void frp_debug_read_prof_lds(long long *out) { frp::debug_read_prof_lds(out); }
+#ifdef FRP_PROFILE // tools/prof_lds.py: every unit exports the read-back of its own counters (the small-launch unit has none)
+#if defined(FRP_LDS_Q4_TU) // (slots 24..28 of the segment counters: workgroups whose Riccati wave claimed SIMD 0..3 / fell back to role = wave index)
+extern "C" void frp_debug_read_prof_lds_q4(long long *out) { frp::FRP_LR::read_prof_lds(out); }
+#elif defined(FRP_LDS_Q30_TU)
+extern "C" void frp_debug_read_prof_lds_q30(long long *out) { frp::FRP_LR::read_prof_lds(out); }
+#elif defined(FRP_LDS_MEM_TU)
+extern "C" void frp_debug_read_prof_lds_mem(long long *out) { frp::FRP_LR::read_prof_lds(out); }
+#elif !defined(FRP_LDS_S2_TU) && !defined(FRP_LDS_TEMPLATES_ONLY)
+extern "C" void frp_debug_read_prof_lds(long long *out) { frp::FRP_LR::read_prof_lds(out); }
 #endif
-#if defined(FRP_PROFILE) && defined(FRP_LDS_Q4_TU)
-// (the Q4 variants too; slots 24..28 of the segment counters: workgroups whose Riccati wave claimed SIMD 0..3 / fell back to role = wave index)
-extern "C" void frp_debug_read_prof_lds_q4(long long *out)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(frp::FRP_LR::g_prof_lds), sizeof(long long) * 64);
-    (void)hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(frp::FRP_LR::g_prof_seg), sizeof(long long) * 32);
-    long long z[64] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(frp::FRP_LR::g_prof_lds), z, sizeof z);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(frp::FRP_LR::g_prof_seg), z, sizeof(long long) * 32);
-}
-#endif
-#if defined(FRP_PROFILE) && defined(FRP_LDS_Q30_TU)
-extern "C" void frp_debug_read_prof_lds_q30(long long *out)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(frp::FRP_LR::g_prof_lds), sizeof(long long) * 64);
-    (void)hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(frp::FRP_LR::g_prof_seg), sizeof(long long) * 32);
-    long long z[64] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(frp::FRP_LR::g_prof_lds), z, sizeof z);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(frp::FRP_LR::g_prof_seg), z, sizeof(long long) * 32);
-}
-#endif
-#if defined(FRP_PROFILE) && defined(FRP_LDS_MEM_TU) && !defined(FRP_LDS_Q4_TU)
-// (the re-reading variants are a translation unit of their own, with their own copy of the profile counters)
-extern "C" void frp_debug_read_prof_lds_mem(long long *out)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(frp::FRP_LR::g_prof_lds), sizeof(long long) * 64);
-    (void)hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(frp::FRP_LR::g_prof_seg), sizeof(long long) * 32);
-    long long z[64] = {0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(frp::FRP_LR::g_prof_lds), z, sizeof z);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(frp::FRP_LR::g_prof_seg), z, sizeof(long long) * 32);
-}
 #endif

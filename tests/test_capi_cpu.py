@@ -518,3 +518,32 @@ def test_slot_reuse_cases_cover_every_kernel_instantiation_that_ships(tmp_path):
     names, _ = _kernel_instantiations(solver.LIB_PATH, tmp_path)
     covered = {l[1] for l in LAUNCHES}
     assert set(names) == covered, (sorted(set(names) - covered), sorted(covered - set(names)))
+
+
+def test_solver_sources_carry_no_experiment_knobs():
+    """The solver kernel's experiments are frozen at the values that ship (profiles/solver_knob_freeze_identity.txt): the only FRP_*
+    names its sources may test in the preprocessor are the unit selectors, the per-unit inline settings, the profile macros and the
+    objective dump, and nothing is a default-define pair (#ifndef X / #define X) that a -D could override."""
+    import glob
+    from forces_resilient_planner_amd import build
+    allowed = {"FRP_LDS_MEM_TU", "FRP_LDS_Q4_TU", "FRP_LDS_Q30_TU", "FRP_LDS_S2_TU",  # the unit selectors (none of them: the main unit)
+               "FRP_LDS_TEMPLATES_ONLY",                                            # ... and the probe that wants no launcher
+               "FRP_INLINE_FACTOR", "FRP_INLINE_SWEEPS",                            # set by the units' own files
+               "FRP_PROFILE", "FRP_PROFILE_SEG", "FRP_PROFILE_W1", "FRP_DEBUG_OBJ"}  # tooling
+    files = sorted(glob.glob(os.path.join(build.CSRC, "frp_ipm_lds*.hip")) + glob.glob(os.path.join(build.CSRC, "frp_ipm_lds*.inc")))
+    assert len(files) >= 5, files
+    tested, pairs = set(), []
+    for f in files:
+        lines = open(f).read().split("\n")
+        for i, line in enumerate(lines):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            cond = m.group(2).split("//")[0]
+            tested |= set(re.findall(r"\bFRP_[A-Za-z0-9_]+", cond))
+            d = re.match(r"\s*(\w+)", cond)
+            nxt = next((l for l in lines[i + 1:] if l.strip()), "")
+            if m.group(1) == "ifndef" and d and re.match(r"\s*#\s*define\s+" + re.escape(d.group(1)) + r"\b", nxt):
+                pairs.append(f"{os.path.basename(f)}:{i + 1}: {d.group(1)}")
+    assert tested == allowed, f"unexpected: {sorted(tested - allowed)}, missing: {sorted(allowed - tested)}"
+    assert not pairs, pairs

@@ -1,6 +1,8 @@
 // Cycle counts of the three Riccati sweeps of the LDS-resident solver, one wavefront alone on its SIMD, on a synthetic
 // (diagonally dominant) record set: the stand-alone cost per stage of the serial chain, without barriers, other waves
 // or the rest of the solve.  Built against the product source itself.
+// (the solver sources for their device templates of namespace frp::lr: no launcher, no kernel instantiated)
+#define FRP_LDS_TEMPLATES_ONLY
 #include "../../forces_resilient_planner_amd/csrc/frp_ipm_lds.hip"
 #include <cstdio>
 #include <cstdlib>
