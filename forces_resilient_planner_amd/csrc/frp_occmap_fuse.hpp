@@ -1,7 +1,8 @@
-// What the two translation units of depth fusion share (frp_occmap_fuse.hip: one frame per call; frp_occmap_fuse_batch.hip: F frames
-// per call): the frame description and workspace layout, the reference's index arithmetic and ray caster, the bodies of the
-// per-pixel / per-ray stages, and the host checks of a description.  Both files are compiled with -ffp-contract=off; everything
-// here that computes a double does it in the order tests/occmap_fusion_oracle.py writes down, on the host and on the device alike.
+// What the translation units of ray-cast fusion share (frp_occmap_fuse.hip: one depth frame per call; frp_occmap_fuse_batch.hip: F depth
+// frames per call; frp_occmap_fuse_points.hip: S point scans per call): the frame description and workspace layout, the reference's
+// index arithmetic and ray caster, the bodies of the per-pixel / per-ray stages, the batch's descriptors and ordered update, and the
+// host checks of a description.  All of them are compiled with -ffp-contract=off; everything here that computes a double does it in
+// the order tests/occmap_fusion_oracle.py writes down, on the host and on the device alike.
 #pragma once
 #include <cfloat>
 #include <climits>
@@ -136,6 +137,28 @@ __device__ inline void init_lane(const Frame &f, const Ws &w, int i)
     if (i < f.nbox) { w.all[i] = 0; w.hit[i] = 0; w.owner[i] = INT_MAX; w.mark[i] = NO_MARK; }
 }
 
+// The head of raycastProcess's loop (:456-467) for point n = p of a frame whose sensor stands at f.t: the length test, the clip,
+// setCacheOccupancy on the end voxel and the owner of cache_rayend_'s dedup.  The caller has set endv[n] = NO_RAY.
+__device__ inline void end_lane(const Geo &g, const Frame &f, const Ws &w, int n, double *p)
+{
+    const double d[3] = {p[0] - f.t[0], p[1] - f.t[1], p[2] - f.t[2]};
+    const double length = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]); // :457
+    if (length < f.min_len) return;                                         // :459
+    int occ = 1;
+    if (length > f.max_len) {                                               // :461-464
+        for (int i = 0; i < 3; i++) p[i] = d[i] / length * f.max_len + f.t[i];
+        occ = 0;
+    }
+    const int e = box_voxel(g, f, p[0], p[1], p[2]);
+    if (e >= 0) { // setCacheOccupancy (:552-560) and the dedup's owner
+        atomicAdd(&w.all[e], 1);
+        if (occ) atomicAdd(&w.hit[e], 1);
+        atomicMin(&w.owner[e], n);
+    }
+    for (int i = 0; i < 3; i++) w.pts[3 * (size_t)n + i] = p[i];
+    w.endv[n] = e;
+}
+
 // projectDepthImage (:314-439) and the head of raycastProcess's loop (:456-467) for scanned pixel n
 __device__ inline void project_lane(const Geo &g, const Frame &f, const Ws &w, int n)
 {
@@ -157,22 +180,7 @@ __device__ inline void project_lane(const Geo &g, const Frame &f, const Ws &w, i
             if (!(drift < f.tol)) return;                                            // :389
         }
     }
-    const double d[3] = {p[0] - f.t[0], p[1] - f.t[1], p[2] - f.t[2]};
-    const double length = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]); // :457
-    if (length < f.min_len) return;                                         // :459
-    int occ = 1;
-    if (length > f.max_len) {                                               // :461-464
-        for (int i = 0; i < 3; i++) p[i] = d[i] / length * f.max_len + f.t[i];
-        occ = 0;
-    }
-    const int e = box_voxel(g, f, p[0], p[1], p[2]);
-    if (e >= 0) { // setCacheOccupancy (:552-560) and the dedup's owner
-        atomicAdd(&w.all[e], 1);
-        if (occ) atomicAdd(&w.hit[e], 1);
-        atomicMin(&w.owner[e], n);
-    }
-    for (int i = 0; i < 3; i++) w.pts[3 * (size_t)n + i] = p[i];
-    w.endv[n] = e;
+    end_lane(g, f, w, n, p);
 }
 
 __device__ inline void setup_lane(const Geo &g, const Frame &f, const Ws &w, int n)
@@ -328,28 +336,21 @@ struct Plan {
     size_t nbmax, off[9], bytes;
 };
 
-// Everything about a description that does not involve a pose or a pointer: fills the frame description except R, t, Ri, lt and the
-// ray box, and the workspace layout.  nbmax, the pose-independent bound on the ray box's size, sizes the per-voxel arrays.
-inline bool plan_shape(const frp_nmpc_occmap *m, int rows, int cols, const double *K, double depth_scale, double mindist, double tol, int margin,
-                       int skip, double hit_log, double miss_log, double min_len, double max_len, int max_rounds, Plan *out)
+// What every route's description shares -- N points per frame, the increments, the ray lengths, the round cap: fills those fields of
+// the frame description (not the image's, not R, t, Ri, lt, the ray box) and the workspace layout.  nbmax, the bound on the ray
+// box's size whatever the sensor position, sizes the per-voxel arrays.
+inline bool plan_rays(const frp_nmpc_occmap *m, long long N, double hit_log, double miss_log, double min_len, double max_len, int max_rounds, Plan *out)
 {
     if (!valid(m)) return false;
-    if (rows < 1 || cols < 1 || skip < 1 || margin < 0) return false;
-    if (!finite_all(K, 9)) return false;
-    const double par[8] = {depth_scale, mindist, tol, hit_log, miss_log, min_len, max_len, 0.0};
-    if (!finite_all(par, 8) || !(depth_scale > 0.0) || max_len < min_len) return false;
+    const double par[4] = {hit_log, miss_log, min_len, max_len};
+    if (!finite_all(par, 4) || max_len < min_len) return false;
     if (max_rounds < 0 || max_rounds > MAX_ROUNDS) return false;
     const double cells = std::ceil(max_len / m->resolution), nb = 3.0 * (cells + 2.0);
     if (!(nb <= (double)MAX_STEPS)) return false;
+    if (N < 0 || N > MAX_PIXELS) return false;
     Frame &f = out->f;
-    f.rows = rows; f.cols = cols; f.margin = margin; f.skip = skip;
-    const long long span_v = (long long)rows - 2LL * f.margin, span_u = (long long)cols - 2LL * f.margin; // v = margin; v < rows - margin; v += skip
-    const long long nv = span_v > 0 ? (span_v + f.skip - 1) / f.skip : 0, nu = span_u > 0 ? (span_u + f.skip - 1) / f.skip : 0;
-    if (nv * nu > MAX_PIXELS) return false;
-    f.nu = nu > 0 ? (int)nu : 1; f.N = (int)(nv * nu);
+    f.N = (int)N;
     f.depth = nullptr; f.last = nullptr; f.status = nullptr;
-    f.fx = K[0]; f.cx = K[2]; f.fy = K[4]; f.cy = K[5];
-    f.depth_scale = depth_scale; f.mindist = mindist; f.tol = tol;
     f.hit_log = hit_log; f.miss_log = miss_log; f.min_len = min_len; f.max_len = max_len;
     f.cmin = m->clamp_min_log; f.cmax = m->clamp_max_log;
     f.nb = nb > 0.0 ? (int)nb : 0;
@@ -361,14 +362,115 @@ inline bool plan_shape(const frp_nmpc_occmap *m, int rows, int cols, const doubl
     }
     if (nbmax >= ((size_t)1 << 30)) return false;
     out->nbmax = nbmax;
-    const size_t N = (size_t)f.N;
-    const size_t sizes[9] = {HDR_INTS * sizeof(int), 3 * N * sizeof(double), N * sizeof(int), N * sizeof(int), N * sizeof(int),
+    const size_t n = (size_t)f.N;
+    const size_t sizes[9] = {HDR_INTS * sizeof(int), 3 * n * sizeof(double), n * sizeof(int), n * sizeof(int), n * sizeof(int),
                              nbmax * sizeof(int), nbmax * sizeof(int), nbmax * sizeof(int), nbmax * sizeof(unsigned)};
     size_t at = 0;
     for (int i = 0; i < 9; i++) { out->off[i] = at; at += up256(sizes[i]); }
     out->bytes = at;
     return true;
 }
+
+// Everything about a depth frame's description that does not involve a pose or a pointer: the image's scan and camera on top of
+// plan_rays.
+inline bool plan_shape(const frp_nmpc_occmap *m, int rows, int cols, const double *K, double depth_scale, double mindist, double tol, int margin,
+                       int skip, double hit_log, double miss_log, double min_len, double max_len, int max_rounds, Plan *out)
+{
+    if (rows < 1 || cols < 1 || skip < 1 || margin < 0) return false;
+    if (!finite_all(K, 9)) return false;
+    const double par[3] = {depth_scale, mindist, tol};
+    if (!finite_all(par, 3) || !(depth_scale > 0.0)) return false;
+    const long long span_v = (long long)rows - 2LL * margin, span_u = (long long)cols - 2LL * margin; // v = margin; v < rows - margin; v += skip
+    const long long nv = span_v > 0 ? (span_v + skip - 1) / skip : 0, nu = span_u > 0 ? (span_u + skip - 1) / skip : 0;
+    if (!plan_rays(m, nv * nu, hit_log, miss_log, min_len, max_len, max_rounds, out)) return false;
+    Frame &f = out->f;
+    f.rows = rows; f.cols = cols; f.margin = margin; f.skip = skip;
+    f.nu = nu > 0 ? (int)nu : 1;
+    f.fx = K[0]; f.cx = K[2]; f.fy = K[4]; f.cy = K[5];
+    f.depth_scale = depth_scale; f.mindist = mindist; f.tol = tol;
+    return true;
+}
+
+// ---- a batch of frames in one call: what frp_occmap_fuse_batch.hip and frp_occmap_fuse_points.hip share ----
+namespace batch {
+
+struct Desc {
+    Frame f;
+    int live;  // active and not refused: the frame runs the stages
+    int fused; // live and converged: the frame takes part in the update (written by the status stage)
+};
+
+struct Batch {
+    Desc *desc;   // [frames], at the start of the workspace
+    char *slices; // frame k's arrays: ws_at(slices + k * slice, off)
+    size_t slice, off[9];
+    int frames;
+};
+
+__device__ inline Ws ws_of(const Batch &b, int k) { return ws_at(b.slices + (size_t)k * b.slice, b.off); }
+
+// voxel (x, y, z) of the map in frame f's ray box: its index there, or OUTSIDE
+__device__ inline int in_box(const Frame &f, int x, int y, int z)
+{
+    if (x < f.box[0] || x >= f.box[3] || y < f.box[1] || y >= f.box[4] || z < f.box[2] || z >= f.box[5]) return OUTSIDE;
+    return ((x - f.box[0]) * f.bd[1] + (y - f.box[1])) * f.bd[2] + (z - f.box[2]);
+}
+
+// The ordered update, lane (j, i) = (blockIdx.y, the lane's index along x): voxel i of frame j's ray box.  A voxel is owned by the first fused frame whose box holds it; the owner applies
+// the update of :512-531 for frames j, j + 1, ... in order on a value carried in a register and writes it once.  The descriptors are
+// read through addresses that are the same for every lane of a workgroup (scalar loads); the per-voxel reads (all, hit, log_odds)
+// run along z, the fastest index of the boxes and of the map alike.
+__device__ inline void update_lane(const Batch &b, const Geo &g, double *log_odds, unsigned char *occ, uint32_t *plane)
+{
+    const int j = blockIdx.y;
+    const Desc *desc = b.desc;
+    if (!desc[j].fused) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const Frame &fj = desc[j].f;
+    if (i >= fj.nbox) return;
+    const int z = fj.box[2] + i % fj.bd[2], y = fj.box[1] + (i / fj.bd[2]) % fj.bd[1], x = fj.box[0] + i / (fj.bd[2] * fj.bd[1]);
+    for (int k = 0; k < j; k++)
+        if (desc[k].fused && in_box(desc[k].f, x, y, z) >= 0) return; // frame k's lane owns this voxel
+    double v = 0.0;
+    bool loaded = false, wrote = false;
+    for (int k = j; k < b.frames; k++) {
+        if (!desc[k].fused) continue;
+        const Frame &fk = desc[k].f;
+        const int ik = k == j ? i : in_box(fk, x, y, z);
+        if (ik < 0) continue;
+        const Ws w = ws_of(b, k);
+        const int all = w.all[ik];
+        if (all == 0) continue; // not in frame k's cache_voxel_
+        if (!loaded) { v = log_odds[((size_t)x * g.grid[1] + y) * g.grid[2] + z]; loaded = true; }
+        if (update_value(fk, all, w.hit[ik], v)) wrote = true;
+    }
+    if (wrote) write_voxel(g, x, y, z, v, log_odds, occ, plane);
+}
+
+struct BatchPlan {
+    Plan p;
+    size_t desc_bytes, bytes;
+};
+
+// the workspace of `frames` frames of the planned shape: the descriptors, then one slice per frame
+inline void plan_slices(BatchPlan *bp, int frames)
+{
+    bp->desc_bytes = up256((size_t)frames * sizeof(Desc));
+    bp->bytes = bp->desc_bytes + (size_t)frames * bp->p.bytes;
+}
+
+inline Batch batch_at(void *fuse_workspace, const BatchPlan &bp, int frames)
+{
+    Batch b;
+    b.desc = static_cast<Desc *>(fuse_workspace);
+    b.slices = static_cast<char *>(fuse_workspace) + bp.desc_bytes;
+    b.slice = bp.p.bytes;
+    for (int i = 0; i < 9; i++) b.off[i] = bp.p.off[i];
+    b.frames = frames;
+    return b;
+}
+
+} // namespace batch
 
 } // namespace fuse
 } // namespace occmap

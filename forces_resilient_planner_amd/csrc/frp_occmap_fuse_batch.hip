@@ -23,21 +23,6 @@ namespace occmap {
 namespace fuse {
 namespace batch {
 
-struct Desc {
-    Frame f;
-    int live;  // active and not refused: the frame runs the stages
-    int fused; // live and converged: the frame takes part in the update (written by the status stage)
-};
-
-struct Batch {
-    Desc *desc;   // [frames], at the start of the workspace
-    char *slices; // frame k's arrays: ws_at(slices + k * slice, off)
-    size_t slice, off[9];
-    int frames;
-};
-
-__device__ inline Ws ws_of(const Batch &b, int k) { return ws_at(b.slices + (size_t)k * b.slice, b.off); }
-
 __global__ void describe_kernel(Batch b, Geo g, Frame shape, const unsigned short *depth, const unsigned short *last, const double *T_wc,
                                 const double *last_T_wc, const int *active, int *status, size_t nbmax)
 {
@@ -132,46 +117,11 @@ __global__ __launch_bounds__(256) void count_kernel(Batch b, Geo g)
     count_lane(g, f, ws_of(b, blockIdx.y), blockIdx.x * blockDim.x + threadIdx.x);
 }
 
-// voxel (x, y, z) of the map in frame f's ray box: its index there, or OUTSIDE
-__device__ inline int in_box(const Frame &f, int x, int y, int z)
-{
-    if (x < f.box[0] || x >= f.box[3] || y < f.box[1] || y >= f.box[4] || z < f.box[2] || z >= f.box[5]) return OUTSIDE;
-    return ((x - f.box[0]) * f.bd[1] + (y - f.box[1])) * f.bd[2] + (z - f.box[2]);
-}
-
-// The ordered update.  The descriptors are read through addresses that are the same for every lane of a workgroup (scalar loads);
-// the per-voxel reads (all, hit, log_odds) run along z, the fastest index of the boxes and of the map alike.
+// The ordered update: lane (j, i) is voxel i of frame j's ray box (update_lane, frp_occmap_fuse.hpp)
 __global__ __launch_bounds__(256) void update_kernel(Batch b, Geo g, double *log_odds, unsigned char *occ, uint32_t *plane)
 {
-    const int j = blockIdx.y;
-    const Desc *desc = b.desc;
-    if (!desc[j].fused) return;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const Frame &fj = desc[j].f;
-    if (i >= fj.nbox) return;
-    const int z = fj.box[2] + i % fj.bd[2], y = fj.box[1] + (i / fj.bd[2]) % fj.bd[1], x = fj.box[0] + i / (fj.bd[2] * fj.bd[1]);
-    for (int k = 0; k < j; k++)
-        if (desc[k].fused && in_box(desc[k].f, x, y, z) >= 0) return; // frame k's lane owns this voxel
-    double v = 0.0;
-    bool loaded = false, wrote = false;
-    for (int k = j; k < b.frames; k++) {
-        if (!desc[k].fused) continue;
-        const Frame &fk = desc[k].f;
-        const int ik = k == j ? i : in_box(fk, x, y, z);
-        if (ik < 0) continue;
-        const Ws w = ws_of(b, k);
-        const int all = w.all[ik];
-        if (all == 0) continue; // not in frame k's cache_voxel_
-        if (!loaded) { v = log_odds[((size_t)x * g.grid[1] + y) * g.grid[2] + z]; loaded = true; }
-        if (update_value(fk, all, w.hit[ik], v)) wrote = true;
-    }
-    if (wrote) write_voxel(g, x, y, z, v, log_odds, occ, plane);
+    update_lane(b, g, log_odds, occ, plane);
 }
-
-struct BatchPlan {
-    Plan p;
-    size_t desc_bytes, bytes;
-};
 
 // Everything that can be refused on the host: the shape of the frames and the parameters (no pose, no pointer)
 static bool plan(const frp_nmpc_occmap *m, const frp_nmpc_occmap_fuse_batch *q, BatchPlan *out)
@@ -181,8 +131,7 @@ static bool plan(const frp_nmpc_occmap *m, const frp_nmpc_occmap_fuse_batch *q, 
     if (!plan_shape(m, q->rows, q->cols, q->K, q->depth_scale, q->depth_filter_mindist, q->depth_filter_tolerance, q->depth_filter_margin, q->skip_pixel,
                     q->prob_hit_log, q->prob_miss_log, q->min_ray_length, q->max_ray_length, q->max_rounds, &out->p))
         return false;
-    out->desc_bytes = up256((size_t)q->frames * sizeof(Desc));
-    out->bytes = out->desc_bytes + (size_t)q->frames * out->p.bytes;
+    plan_slices(out, q->frames);
     return true;
 }
 
@@ -212,12 +161,7 @@ int frp_nmpc_occmap_fuse_depth_batch(const frp_nmpc_occmap *map, const frp_nmpc_
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Plan &p = bp.p;
-    Batch b;
-    b.desc = static_cast<Desc *>(fuse_workspace);
-    b.slices = static_cast<char *>(fuse_workspace) + bp.desc_bytes;
-    b.slice = p.bytes;
-    for (int i = 0; i < 9; i++) b.off[i] = p.off[i];
-    b.frames = q->frames;
+    const Batch b = batch_at(fuse_workspace, bp, q->frames);
     const Geo g = geo(map);
     const unsigned F = (unsigned)q->frames;
     const auto blocks = [F](size_t n) { return dim3((unsigned)((n > 0 ? n : 1) + 255) / 256, F); };

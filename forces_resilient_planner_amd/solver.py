@@ -125,6 +125,14 @@ class OccMapFuseBatch(ctypes.Structure):  # frp_nmpc_occmap_fuse_batch (include/
                 ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
 
 
+class OccMapFusePoints(ctypes.Structure):  # frp_nmpc_occmap_fuse_points (include/frp_nmpc_occmap_fuse_points.h)
+    _fields_ = [("scans", ctypes.c_int), ("P", ctypes.c_int), ("points", ctypes.c_void_p), ("points_f32", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("origin", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("prob_hit_log", ctypes.c_double), ("prob_miss_log", ctypes.c_double),
+                ("min_ray_length", ctypes.c_double), ("max_ray_length", ctypes.c_double),
+                ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
+
+
 class OccMapRender(ctypes.Structure):  # frp_nmpc_occmap_render (include/frp_nmpc_occmap_render.h)
     _fields_ = [("frames", ctypes.c_int), ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("T_wc", ctypes.c_void_p), ("active", ctypes.c_void_p),
                 ("K", ctypes.c_double * 9), ("depth_scale", ctypes.c_double), ("max_range", ctypes.c_double),
@@ -170,6 +178,10 @@ FUSE_EXPORTS = ["frp_nmpc_occmap_fuse_workspace_bytes", "frp_nmpc_occmap_fuse_de
 FUSE_BATCH_EXPORTS = ["frp_nmpc_occmap_fuse_batch_workspace_bytes", "frp_nmpc_occmap_fuse_depth_batch"]
 OCCMAP_FUSE_MAX_FRAMES = 64     # FRP_OCCMAP_FUSE_MAX_FRAMES
 OCCMAP_FUSE_REFUSED = -256      # FRP_OCCMAP_FUSE_REFUSED: status[f][0] of a frame whose pose the device refuses
+# ... and the same ray casting for point scans (include/frp_nmpc_occmap_fuse_points.h): S clouds with their sensor positions per call
+FUSE_POINTS_EXPORTS = ["frp_nmpc_occmap_fuse_points_workspace_bytes", "frp_nmpc_occmap_fuse_points_batch"]
+OCCMAP_FUSE_POINTS_MAX_SCANS = 64    # FRP_OCCMAP_FUSE_POINTS_MAX_SCANS
+OCCMAP_FUSE_POINTS_PARAMS = ("prob_hit_log", "prob_miss_log", "min_ray_length", "max_ray_length", "max_rounds")  # the keys of OCCMAP_FUSE_DEFAULTS a point scan has
 
 # section (8)'s fifth header (include/frp_nmpc_occmap_render.h): depth images rendered from the map, camera poses from planner states
 RENDER_EXPORTS = ["frp_nmpc_occmap_render_depth", "frp_nmpc_occmap_camera_poses"]
@@ -325,7 +337,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -343,6 +355,9 @@ def lib():
         l.frp_nmpc_occmap_fuse_batch_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_occmap_fuse_batch_workspace_bytes.argtypes = [pm, ctypes.POINTER(OccMapFuseBatch)]
         l.frp_nmpc_occmap_fuse_depth_batch.argtypes = [pm, ctypes.POINTER(OccMapFuseBatch), vp, sz, vp, sz, vp]
+        l.frp_nmpc_occmap_fuse_points_workspace_bytes.restype = ctypes.c_size_t
+        l.frp_nmpc_occmap_fuse_points_workspace_bytes.argtypes = [pm, ctypes.POINTER(OccMapFusePoints)]
+        l.frp_nmpc_occmap_fuse_points_batch.argtypes = [pm, ctypes.POINTER(OccMapFusePoints), vp, sz, vp, sz, vp]
         l.frp_nmpc_occmap_render_depth.argtypes = [pm, ctypes.POINTER(OccMapRender), vp, sz, vp]
         l.frp_nmpc_occmap_camera_poses.argtypes = [ctypes.c_int, vp, c_double_p, vp, vp]
         l.frp_nmpc_occmap_shared_view_dims.argtypes = [pm, ctypes.c_double, ctypes.POINTER(ctypes.c_int * 3)]
@@ -634,7 +649,8 @@ class OccupancyMap:
     world: the dict of workloads.astar_world -- its geometry, and its occ as the initial content (occupied voxels at
     clamp_max_log, the others at clamp_min_log); or explicit origin / map_size / resolution for an empty map.  fuse_depth() fuses a
     camera frame by ray casting (projectDepthImage / raycastProcess, include/frp_nmpc_occmap_fuse.h) with the reference's serial
-    result to the bit; a caller with another fusion of its own writes .log_odds and calls refresh().  render_depth() is the other
+    result to the bit, fuse_points() does the same ray casting for point scans (a LiDAR's cloud and the position it was taken from); a
+    caller with another fusion of its own writes .log_odds and calls refresh().  render_depth() is the other
     direction: the depth images cameras at given poses see of this map (a ground-truth world feeding a belief map's fuse_depth_batch)."""
 
     def __init__(self, world=None, origin=None, map_size=None, resolution=None, local_radius=None, clamp_min_log=None,
@@ -667,6 +683,7 @@ class OccupancyMap:
         self.ws = torch.empty((self.ws_bytes // 4 + 1,), dtype=torch.int32, device=self.device)
         self.fuse_ws = None          # the fusion workspace: allocated by fuse_depth, grown when a larger frame needs it
         self.fuse_batch_ws = None    # the batched fusion's workspace: allocated by fuse_depth_batch, grown when a larger batch needs it
+        self.fuse_points_ws = None   # the point scans' fusion workspace: allocated by fuse_points, grown when (S, P, max_ray_length) need more
         self._last_frame = None      # (depth, T_wc) of the previous filtered frame (last_depth_image, last_T_wc: occ_map.cpp:423-424)
         self._fusing_against = None  # the frame the latest filtered call reads on its stream: kept alive until the next call
         self._goal_table = None      # (table, n_groups, group_size) of goal_search_table() on the device: made by the first safety_check
@@ -872,6 +889,79 @@ class OccupancyMap:
                                                       ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_occmap_fuse_depth_batch")
         if stream is not None:
             for a in (depth, T, last, lastT, active):
+                if a is not None:
+                    a.record_stream(stream)
+        return status
+
+    def fuse_points(self, points, origin, *, count=None, active=None, status=None, stream=None, **params):
+        """S point scans into the map in one call (include/frp_nmpc_occmap_fuse_points.h): raycastProcess (occ_map.cpp:441-533) for
+        a sensor that delivers a cloud in the world frame and the position it was taken from -- a LiDAR, a stereo rig.  The map
+        afterwards is, to the bit, what fusing scans 0 ... S - 1 one after the other leaves; scans that are inactive, refused or not
+        converged are skipped.  log_odds, occ and the bit plane follow together -- no refresh().
+        points: a contiguous DEVICE tensor [S, P, 3], or [P, 3] for one scan, float64 or float32 (a float is widened exactly), used IN
+        PLACE; a point with a NaN or infinite coordinate ("no return") is dropped and keeps its index.  origin [S, 3] or [3]
+        float64, count [S] int32 or None (every scan holds P points; storage beyond count[s] is not read) and active [S] int32 or
+        None may be numpy arrays, which are uploaded, or device tensors, which are used in place: the kernels read them, so a
+        captured call replays with whatever the caller has written into its tensors since.  params: prob_hit_log, prob_miss_log,
+        min_ray_length, max_ray_length, max_rounds of OCCMAP_FUSE_DEFAULTS, shared by the scans.
+        Returns the status tensor (int32 [S, 2], device; nothing is synchronised) as fuse_depth_batch does: [rounds used, rays cast],
+        [-max_rounds, rays] for a scan that did not converge, [0, 0] inactive, [OCCMAP_FUSE_REFUSED, 0] for a non-finite origin.
+        status: a tensor to write into.  ValueError: arguments of another kind than described, or a description the library refuses."""
+        t = self.torch
+        unknown = set(params) - set(OCCMAP_FUSE_POINTS_PARAMS)
+        if unknown:
+            raise TypeError(f"fuse_points: unknown parameters {sorted(unknown)}")
+        d = dict(OCCMAP_FUSE_DEFAULTS); d.update(params)
+        if not t.is_tensor(points) or points.device != self.log_odds.device:
+            raise ValueError("fuse_points: points must be a tensor on the map's device")
+        if points.dtype not in (t.float64, t.float32):
+            raise ValueError(f"fuse_points: points must be float64 or float32, not {points.dtype}")
+        if points.dim() not in (2, 3) or points.shape[-1] != 3:
+            raise ValueError(f"fuse_points: points must be [S, P, 3] or [P, 3], not {tuple(points.shape)}")
+        if not points.is_contiguous():
+            raise ValueError("fuse_points: points must be contiguous")
+        S, P = (1, int(points.shape[0])) if points.dim() == 2 else (int(points.shape[0]), int(points.shape[1]))
+
+        def per_scan(a, dtype, shape, what):
+            if not t.is_tensor(a):
+                a = t.from_numpy(np.ascontiguousarray(a, dtype={t.float64: np.float64, t.int32: np.int32}[dtype])).to(self.device)
+            if S == 1 and a.dim() == len(shape) - 1 and a.is_contiguous():
+                a = a.reshape(shape)  # one scan given without its leading dimension: a view, still the caller's storage
+            if a.dtype != dtype or tuple(a.shape) != shape or a.device != self.log_odds.device or not a.is_contiguous():
+                raise ValueError(f"fuse_points: {what} must be a contiguous {list(shape)} {dtype} tensor on the map's device (or an array of that shape)")
+            return a
+
+        origin = per_scan(origin, t.float64, (S, 3), "origin")
+        if count is not None:
+            count = per_scan(count, t.int32, (S,), "count")
+        if active is not None:
+            active = per_scan(active, t.int32, (S,), "active")
+        if status is None:
+            status = t.zeros((S, 2), dtype=t.int32, device=self.device)
+        if not t.is_tensor(status) or status.dtype != t.int32 or tuple(status.shape) != (S, 2) or status.device != self.log_odds.device or not status.is_contiguous():
+            raise ValueError("fuse_points: status must be a contiguous [S, 2] int32 tensor on the map's device")
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        f = OccMapFusePoints()
+        f.scans, f.P = S, P
+        f.points = points.data_ptr() if P > 0 and points.dtype == t.float64 else None
+        f.points_f32 = points.data_ptr() if P > 0 and points.dtype == t.float32 else None
+        f.count = count.data_ptr() if count is not None else None
+        f.active = active.data_ptr() if active is not None else None
+        f.origin, f.status = origin.data_ptr(), status.data_ptr()
+        for k in ("prob_hit_log", "prob_miss_log", "min_ray_length", "max_ray_length"):
+            setattr(f, k, float(d[k]))
+        f.max_rounds = int(d["max_rounds"])
+        m = self._map()
+        need = int(lib().frp_nmpc_occmap_fuse_points_workspace_bytes(ctypes.byref(m), ctypes.byref(f)))
+        if need == 0:
+            raise ValueError(f"frp_nmpc_occmap_fuse_points_batch refuses this description: {S} scans of {P} points (see include/frp_nmpc_occmap_fuse_points.h)")
+        if self.fuse_points_ws is None or self.fuse_points_ws.numel() < need:
+            self.fuse_points_ws = t.empty((need,), dtype=t.uint8, device=self.device)
+        _check(lib().frp_nmpc_occmap_fuse_points_batch(ctypes.byref(m), ctypes.byref(f), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
+                                                       ctypes.c_void_p(self.fuse_points_ws.data_ptr()), int(self.fuse_points_ws.numel()),
+                                                       ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_occmap_fuse_points_batch")
+        if stream is not None:
+            for a in (points, origin, count, active):
                 if a is not None:
                     a.record_stream(stream)
         return status

@@ -563,6 +563,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * of its own, part of this section and of this ABI version. */
 #include "frp_nmpc_occmap_fuse_batch.h"
 
+/* The same ray casting for sensors that deliver a cloud in the world frame and the position it was taken from (a LiDAR, a stereo
+ * rig): raycastProcess for a batch of point scans, everything read on the device.  A header of its own, part of this section and of
+ * this ABI version. */
+#include "frp_nmpc_occmap_fuse_points.h"
+
 /* The safety timer's collision checks (checkPosSurround, :625-643, and the goal and path loops of checkReplanCallback,
  * plan_manage/src/nmpc_manage.cpp:285-341) on the bit plane.  A header of its own, part of this section and of this ABI version. */
 #include "frp_nmpc_occmap_check.h"
