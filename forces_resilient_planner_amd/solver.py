@@ -139,6 +139,13 @@ class OccMapRender(ctypes.Structure):  # frp_nmpc_occmap_render (include/frp_nmp
                 ("depth", ctypes.c_void_p), ("voxel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class OccMapRenderScan(ctypes.Structure):  # frp_nmpc_occmap_render_scan (include/frp_nmpc_occmap_render_scan.h)
+    _fields_ = [("scans", ctypes.c_int), ("P", ctypes.c_int), ("beams", ctypes.c_void_p), ("T_ws", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("min_range", ctypes.c_double), ("max_range", ctypes.c_double), ("far_range", ctypes.c_double),
+                ("points", ctypes.c_void_p), ("points_f32", ctypes.c_void_p), ("origin", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("range", ctypes.c_void_p), ("voxel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
 class OccMapSharedView(ctypes.Structure):  # frp_nmpc_occmap_shared_view (include/frp_nmpc_occmap_view.h)
     _fields_ = [("cap", ctypes.c_int), ("cell", ctypes.c_double), ("dims", ctypes.c_int * 3),
                 ("cloud", ctypes.c_void_p), ("count", ctypes.c_void_p), ("total", ctypes.c_void_p),
@@ -185,6 +192,8 @@ OCCMAP_FUSE_POINTS_PARAMS = ("prob_hit_log", "prob_miss_log", "min_ray_length", 
 
 # section (8)'s fifth header (include/frp_nmpc_occmap_render.h): depth images rendered from the map, camera poses from planner states
 RENDER_EXPORTS = ["frp_nmpc_occmap_render_depth", "frp_nmpc_occmap_camera_poses"]
+# ... and the same sensor for a table of beam directions (include/frp_nmpc_occmap_render_scan.h): the point scans fuse_points takes
+RENDER_SCAN_EXPORTS = ["frp_nmpc_occmap_render_scan_batch"]
 
 # section (8)'s sixth header (include/frp_nmpc_occmap_view.h): the shared view rebuilt on the device, and the corridor entry that takes it
 VIEW_EXPORTS = ["frp_nmpc_occmap_shared_view_dims", "frp_nmpc_occmap_shared_view_update", "frp_nmpc_corridor_batch_view"]
@@ -229,6 +238,25 @@ def goal_search_table():
         r += dr
     assert len(set(sizes)) == 1, sizes
     return np.array(rows, dtype=np.float64).reshape(-1, 3), len(sizes), sizes[0]
+
+
+def lidar_beams(rings, columns, elevation_min, elevation_max, azimuth_span=2 * np.pi):
+    """The beam table of a spinning LiDAR for OccupancyMap.render_scan: [rings * columns, 3] float64 unit vectors in the SENSOR frame
+    (x forward, z up) in firing order, column-major -- all rings of azimuth 0, then the next azimuth --, so that the 64 consecutive
+    beams of a wavefront point in nearby directions.  az_j = azimuth_span * j / columns, el_i = elevation_min + (elevation_max -
+    elevation_min) * i / (rings - 1) (elevation_min when rings == 1), beam = (cos(el) cos(az), cos(el) sin(az), sin(el)).  A
+    convenience: frp_nmpc_occmap_render_scan_batch takes any table."""
+    rings, columns = int(rings), int(columns)
+    if rings < 1 or columns < 1:
+        raise ValueError("lidar_beams: at least one ring and one column")
+    i, j = np.arange(rings, dtype=np.float64), np.arange(columns, dtype=np.float64)
+    el = np.full(rings, float(elevation_min)) if rings == 1 else float(elevation_min) + (float(elevation_max) - float(elevation_min)) * i / (rings - 1)
+    az = float(azimuth_span) * j / columns
+    out = np.empty((columns, rings, 3), dtype=np.float64)
+    out[:, :, 0] = np.cos(el)[None, :] * np.cos(az)[:, None]
+    out[:, :, 1] = np.cos(el)[None, :] * np.sin(az)[:, None]
+    out[:, :, 2] = np.sin(el)[None, :]
+    return out.reshape(rings * columns, 3)
 
 
 class SafetyCheck:
@@ -337,7 +365,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -651,7 +679,8 @@ class OccupancyMap:
     camera frame by ray casting (projectDepthImage / raycastProcess, include/frp_nmpc_occmap_fuse.h) with the reference's serial
     result to the bit, fuse_points() does the same ray casting for point scans (a LiDAR's cloud and the position it was taken from); a
     caller with another fusion of its own writes .log_odds and calls refresh().  render_depth() is the other
-    direction: the depth images cameras at given poses see of this map (a ground-truth world feeding a belief map's fuse_depth_batch)."""
+    direction: the depth images cameras at given poses see of this map (a ground-truth world feeding a belief map's fuse_depth_batch),
+    and render_scan() the point scans a LiDAR's beam table measures in it (feeding fuse_points)."""
 
     def __init__(self, world=None, origin=None, map_size=None, resolution=None, local_radius=None, clamp_min_log=None,
                  clamp_max_log=None, min_occupancy_log=None, device="cuda:0"):
@@ -1016,6 +1045,88 @@ class OccupancyMap:
                 if a is not None:
                     a.record_stream(stream)
         return out
+
+    def render_scan(self, T_ws, beams, *, max_range, min_range=0.0, far_range=0.0, dtype=None, active=None, points=None, points_f32=None,
+                    origin=None, count=None, range=None, voxel=None, status=None, stream=None):
+        """What S range sensors at the poses T_ws measure of THIS map along a table of P beam directions
+        (include/frp_nmpc_occmap_render_scan.h): the point scans [S, P, 3] in the world frame that fuse_points takes, in beam order,
+        with their origins [S, 3] and counts [S] written on the device -- camera_poses -> render_scan -> fuse_points needs no host.
+        T_ws [S, 4, 4] float64 sensor-to-world, beams [P, 3] float64 in the sensor frame (any length; lidar_beams() makes a spinning
+        LiDAR's) and active [S] int32 (or None) may be numpy arrays, which are uploaded, or device tensors, which are used IN PLACE: the
+        kernels read them, so a captured call replays with whatever the caller has written since.  max_range, min_range: metres along
+        the beam.  A beam without a return gives a NaN point (fuse_points drops it), or with far_range >= max_range the point at
+        far_range along the beam (fused with max_ray_length < far_range: a miss that carves free space).
+        dtype: torch.float64 (the default) or torch.float32, the type of the points returned.  The output tensors are used if given,
+        so that a captured call replays into them: points [S, P, 3] (its dtype then decides), points_f32 [S, P, 3] float32 written
+        as well as float64 points (each float is the double rounded once), origin [S, 3] float64, count [S] int32, range [S, P]
+        float64 (metres along the beam of the return, 0: none), voxel [S, P] int32 (linear voxel index of the return, -1: none),
+        status [S, 2] int32 ({1, returns} / {0, 0} inactive, nothing of the scan written but count 0 / {OCCMAP_FUSE_REFUSED, 0} a
+        non-finite pose, its points NaN).  Returns (points, origin, count, status); nothing is synchronised.  ValueError: a
+        description the library refuses."""
+        t = self.torch
+        dev = self.log_odds.device
+
+        def given(a, dt, shape, what, upload=False):
+            if upload and not t.is_tensor(a):
+                a = t.from_numpy(np.ascontiguousarray(a, dtype={t.float64: np.float64, t.int32: np.int32}[dt])).to(self.device)
+            if not t.is_tensor(a) or a.dtype != dt or (shape is not None and tuple(a.shape) != shape) or a.device != dev or not a.is_contiguous():
+                raise TypeError(f"render_scan: {what} must be a contiguous {list(shape) if shape else ''} {dt} tensor on the map's device")
+            return a
+
+        if not t.is_tensor(T_ws):
+            T_ws = t.from_numpy(np.ascontiguousarray(T_ws, dtype=np.float64)).to(self.device)
+        if T_ws.dim() != 3 or tuple(T_ws.shape[1:]) != (4, 4):
+            raise TypeError("render_scan: T_ws must be [S, 4, 4]")
+        T_ws = given(T_ws, t.float64, None, "T_ws")
+        if not t.is_tensor(beams):
+            beams = t.from_numpy(np.array(beams, dtype=np.float64, order="C")).to(self.device)  # (a copy: a table kept read-only uploads too)
+        if beams.dim() != 2 or beams.shape[1] != 3:
+            raise TypeError("render_scan: beams must be [P, 3]")
+        beams = given(beams, t.float64, None, "beams")
+        S, P = int(T_ws.shape[0]), int(beams.shape[0])
+        if S < 1 or P < 1:
+            raise ValueError("render_scan: at least one scan and one beam")
+        if active is not None:
+            active = given(active, t.int32, (S,), "active", upload=True)
+        if points is None:
+            dtype = t.float64 if dtype is None else dtype
+            if dtype not in (t.float64, t.float32):
+                raise TypeError(f"render_scan: dtype must be float64 or float32, not {dtype}")
+            points = t.full((S, P, 3), float("nan"), dtype=dtype, device=self.device)
+        elif not t.is_tensor(points) or points.dtype not in (t.float64, t.float32) or (dtype is not None and points.dtype != dtype):
+            raise TypeError("render_scan: points must be a float64 or float32 tensor of the dtype asked for")
+        points = given(points, points.dtype, (S, P, 3), "points")
+        if points_f32 is not None:
+            if points.dtype != t.float64:
+                raise TypeError("render_scan: points_f32 goes with float64 points")
+            points_f32 = given(points_f32, t.float32, (S, P, 3), "points_f32")
+        origin = t.zeros((S, 3), dtype=t.float64, device=self.device) if origin is None else given(origin, t.float64, (S, 3), "origin")
+        count = t.zeros((S,), dtype=t.int32, device=self.device) if count is None else given(count, t.int32, (S,), "count")
+        status = t.zeros((S, 2), dtype=t.int32, device=self.device) if status is None else given(status, t.int32, (S, 2), "status")
+        if range is not None:
+            range = given(range, t.float64, (S, P), "range")
+        if voxel is not None:
+            voxel = given(voxel, t.int32, (S, P), "voxel")
+        r = OccMapRenderScan()
+        r.scans, r.P = S, P
+        r.beams, r.T_ws, r.active = beams.data_ptr(), T_ws.data_ptr(), active.data_ptr() if active is not None else None
+        r.min_range, r.max_range, r.far_range = float(min_range), float(max_range), float(far_range)
+        r.points = points.data_ptr() if points.dtype == t.float64 else None
+        r.points_f32 = points.data_ptr() if points.dtype == t.float32 else points_f32.data_ptr() if points_f32 is not None else None
+        r.origin, r.count, r.status = origin.data_ptr(), count.data_ptr(), status.data_ptr()
+        r.range, r.voxel = range.data_ptr() if range is not None else None, voxel.data_ptr() if voxel is not None else None
+        s = stream if stream is not None else t.cuda.current_stream(self.device)
+        m = self._map()
+        rc = lib().frp_nmpc_occmap_render_scan_batch(ctypes.byref(m), ctypes.byref(r), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
+                                                     ctypes.c_void_p(s.cuda_stream))
+        if rc == -1003:  # FRP_ERR_ARG
+            raise ValueError("frp_nmpc_occmap_render_scan_batch refuses this description (see include/frp_nmpc_occmap_render_scan.h)")
+        _check(rc, "frp_nmpc_occmap_render_scan_batch")
+        if stream is not None:
+            for a in (T_ws, beams, active, points, points_f32, origin, count, range, voxel, status):
+                if a is not None:
+                    a.record_stream(stream)
+        return points, origin, count, status
 
     def camera_poses(self, state, T_bc, out=None, stream=None):
         """T_wc [B, 4, 4] = T_wb(state) T_bc for planner states [B, 9] (position, velocity, Euler angles; device tensor, used in

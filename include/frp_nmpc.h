@@ -577,6 +577,10 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * version. */
 #include "frp_nmpc_occmap_render.h"
 
+/* The same sensor for a table of beam directions (a spinning LiDAR, a ToF array): point scans rendered from the bit plane in the
+ * format the point-scan fusion reads.  A header of its own, part of this section and of this ABI version. */
+#include "frp_nmpc_occmap_render_scan.h"
+
 /* The shared view rebuilt on the device: the whole-map cloud and its uniform grid in fixed-capacity buffers, every count read from
  * device memory, and the corridor entry point that takes them with the grid on.  A header of its own, part of this section and of
  * this ABI version. */
