@@ -8,7 +8,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfrp_nmpc_amd.so")
 SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip"]
-HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
+HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", "frp_occmap_raywalk.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_batch.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_points.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_check.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_render.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_render_scan.h"),
@@ -122,7 +122,8 @@ PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS,  # (what else a solver uni
                     # the batched fusion is the same code per frame, and computes on the device what the single-frame call computes on the
                     # host (the inverse rotation, the ray box): the same roundings
                     "frp_occmap_fuse_batch.hip": ["-ffp-contract=off"],
-                    # point scans run the same stages from the ray set-up on, and compute the clipped end and the ray box with the same roundings
+                    # point scans run the batch unit's stage kernels from the ray set-up on (this unit holds describe and load alone), and
+                    # compute the clipped end and the ray box with the same roundings
                     "frp_occmap_fuse_points.hip": ["-ffp-contract=off"],
                     # the safety checks take every probe's voxel index as the reference does: pos + i * resolution is a product and a sum, no FMA
                     "frp_occmap_check.hip": ["-ffp-contract=off"],

@@ -1,8 +1,9 @@
 // What the translation units of frp_nmpc.h section (8) share (frp_occmap.hip, frp_occmap_fuse.hip): the map's geometry as the kernels take
-// it, the reference's index arithmetic (posToIndex, occ_map.cpp:71-75) and the argument checks of every call.
+// it, the reference's index arithmetic (posToIndex, occ_map.cpp:71-75), the finiteness test and the argument checks of every call.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
@@ -26,6 +27,13 @@ __host__ __device__ inline int clamp_id(double f)
     if (!(f >= -ID_LIM)) f = -ID_LIM; // NaN as well
     if (f > ID_LIM) f = ID_LIM;
     return (int)f;
+}
+
+__host__ __device__ inline bool finite_all(const double *a, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (!(fabs(a[i]) <= DBL_MAX)) return false; // std::isfinite
+    return true;
 }
 
 inline size_t plane_bytes(const frp_nmpc_occmap *m) { return (size_t)m->grid[0] * m->grid[1] * ((m->grid[2] + 31) / 32) * sizeof(uint32_t); }

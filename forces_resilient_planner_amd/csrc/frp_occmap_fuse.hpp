@@ -1,13 +1,13 @@
 // What the translation units of ray-cast fusion share (frp_occmap_fuse.hip: one depth frame per call; frp_occmap_fuse_batch.hip: F depth
 // frames per call; frp_occmap_fuse_points.hip: S point scans per call): the frame description and workspace layout, the reference's
-// index arithmetic and ray caster, the bodies of the per-pixel / per-ray stages, the batch's descriptors and ordered update, and the
-// host checks of a description.  All of them are compiled with -ffp-contract=off; everything here that computes a double does it in
+// index arithmetic and ray caster, the bodies of the per-pixel / per-ray stages, the batch's descriptors, ordered update and shared
+// launch sequence, and the host checks of a description.  All of them are compiled with -ffp-contract=off; everything here that computes a double does it in
 // the order tests/occmap_fusion_oracle.py writes down, on the host and on the device alike.
 #pragma once
 #include <cfloat>
 #include <climits>
 
-#include "frp_occmap.hpp"
+#include "frp_occmap_raywalk.hpp"
 
 namespace frp {
 namespace occmap {
@@ -19,7 +19,6 @@ constexpr int HDR_INTS = 264;             // [1 .. 255] changed flag of round r,
 constexpr int H_NRAYS = 256, H_NLIST = 257, H_CONVERGED = 258;
 constexpr int NO_RAY = -2, OUTSIDE = -1;  // end voxel of a point: dropped before the ray / outside the map (INVALID_IDX)
 constexpr unsigned NO_MARK = 0xFFFFFFFFu;
-constexpr int MAX_STEPS = 4096;
 
 struct Frame {
     int rows, cols, margin, skip, nu, N;
@@ -276,13 +275,6 @@ __device__ inline void write_voxel(const Geo &g, int x, int y, int z, double nv,
 
 // ---- the pose: what is computed once per frame, on the host for the single-frame call and by one lane per frame for the batch ----
 
-__host__ __device__ inline bool finite_all(const double *a, int n)
-{
-    for (int i = 0; i < n; i++)
-        if (!(fabs(a[i]) <= DBL_MAX)) return false; // std::isfinite
-    return true;
-}
-
 // last_T_wc.block<3,3>(0,0).inverse() (:382) as adjugate / determinant, in the order tests/occmap_fusion_oracle.py inverse3 writes down
 __host__ __device__ inline bool inverse3(const double *T, double *Ri)
 {
@@ -345,8 +337,9 @@ inline bool plan_rays(const frp_nmpc_occmap *m, long long N, double hit_log, dou
     const double par[4] = {hit_log, miss_log, min_len, max_len};
     if (!finite_all(par, 4) || max_len < min_len) return false;
     if (max_rounds < 0 || max_rounds > MAX_ROUNDS) return false;
-    const double cells = std::ceil(max_len / m->resolution), nb = 3.0 * (cells + 2.0);
-    if (!(nb <= (double)MAX_STEPS)) return false;
+    const double cells = std::ceil(max_len / m->resolution);
+    double nb;
+    if (!step_bound(max_len, m->resolution, &nb)) return false;
     if (N < 0 || N > MAX_PIXELS) return false;
     Frame &f = out->f;
     f.N = (int)N;
@@ -459,16 +452,26 @@ inline void plan_slices(BatchPlan *bp, int frames)
     bp->bytes = bp->desc_bytes + (size_t)frames * bp->p.bytes;
 }
 
-inline Batch batch_at(void *fuse_workspace, const BatchPlan &bp, int frames)
+// the batch laid out in the caller's fuse workspace; false: no workspace, too small a one or a misaligned one
+inline bool batch_at(void *fuse_workspace, size_t fuse_workspace_bytes, const BatchPlan &bp, int frames, Batch *b)
 {
-    Batch b;
-    b.desc = static_cast<Desc *>(fuse_workspace);
-    b.slices = static_cast<char *>(fuse_workspace) + bp.desc_bytes;
-    b.slice = bp.p.bytes;
-    for (int i = 0; i < 9; i++) b.off[i] = bp.p.off[i];
-    b.frames = frames;
-    return b;
+    if (!fuse_workspace || fuse_workspace_bytes < bp.bytes || ((uintptr_t)fuse_workspace & 7) != 0) return false;
+    b->desc = static_cast<Desc *>(fuse_workspace);
+    b->slices = static_cast<char *>(fuse_workspace) + bp.desc_bytes;
+    b->slice = bp.p.bytes;
+    for (int i = 0; i < 9; i++) b->off[i] = bp.p.off[i];
+    b->frames = frames;
+    return true;
 }
+
+// 256-lane workgroups over n lanes per frame: a frame's count and box are known on the device only, the grids take their bounds
+inline dim3 blocks(const Batch &b, size_t n) { return dim3((unsigned)((n > 0 ? n : 1) + 255) / 256, (unsigned)b.frames); }
+
+// The launches every route shares, around its own first stage (describe, then project or load, which fill the descriptors and the
+// rays' ends): init after describe; then setup, the mark / stop rounds, status, count and the ordered update.  With the route's two
+// that is 2 * max_rounds + 7 launches.  The kernels are frp_occmap_fuse_batch.hip's, the only copy in the library.
+void launch_init(const Batch &b, const Plan &p, hipStream_t st);
+int launch_from_setup(const Batch &b, const Plan &p, const frp_nmpc_occmap *map, void *workspace, hipStream_t st); // FRP_OK or FRP_ERR_HIP
 
 } // namespace batch
 

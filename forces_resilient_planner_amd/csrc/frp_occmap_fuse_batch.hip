@@ -14,7 +14,8 @@
 //            the update of :512-531 for frames j, j + 1, ..., F - 1 in order, for every fused frame whose box holds the voxel with
 //            all > 0, on a value carried in a register, and writes log_odds, occ and the bit of the plane once.  Exactly one lane
 //            owns a voxel, so no two lanes update the same voxel, and no kernel waits for another workgroup.
-// Launches: 2 * max_rounds + 7, whatever F.
+// Launches: 2 * max_rounds + 7, whatever F.  All but describe and project are launched by launch_init / launch_from_setup below, which
+// the point scans' call (frp_occmap_fuse_points.hip) runs too, behind its own describe and load: the library holds these kernels once.
 #include "frp_nmpc_occmap_fuse_batch.h"
 #include "frp_occmap_fuse.hpp"
 
@@ -135,6 +136,28 @@ static bool plan(const frp_nmpc_occmap *m, const frp_nmpc_occmap_fuse_batch *q, 
     return true;
 }
 
+static_assert(FRP_OCCMAP_FUSE_POINTS_MAX_SCANS == FRP_OCCMAP_FUSE_MAX_FRAMES, "one lane per frame or scan: the status launch serves both routes");
+
+void launch_init(const Batch &b, const Plan &p, hipStream_t st)
+{
+    hipLaunchKernelGGL(init_kernel, blocks(b, p.nbmax > (size_t)HDR_INTS ? p.nbmax : (size_t)HDR_INTS), dim3(256), 0, st, b);
+}
+
+int launch_from_setup(const Batch &b, const Plan &p, const frp_nmpc_occmap *map, void *workspace, hipStream_t st)
+{
+    const Geo g = geo(map);
+    const dim3 rays = blocks(b, (size_t)p.f.N), box = blocks(b, p.nbmax);
+    hipLaunchKernelGGL(setup_kernel, rays, dim3(256), 0, st, b, g);
+    for (int r = 1; r <= p.f.max_rounds; r++) {
+        hipLaunchKernelGGL(mark_kernel, rays, dim3(256), 0, st, b, g, r);
+        hipLaunchKernelGGL(stop_kernel, rays, dim3(256), 0, st, b, g, r);
+    }
+    hipLaunchKernelGGL(status_kernel, dim3(1), dim3(FRP_OCCMAP_FUSE_MAX_FRAMES), 0, st, b);
+    hipLaunchKernelGGL(count_kernel, rays, dim3(256), 0, st, b, g);
+    hipLaunchKernelGGL(update_kernel, box, dim3(256), 0, st, b, g, map->log_odds, map->occ, static_cast<uint32_t *>(workspace));
+    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+}
+
 } // namespace batch
 } // namespace fuse
 } // namespace occmap
@@ -157,28 +180,16 @@ int frp_nmpc_occmap_fuse_depth_batch(const frp_nmpc_occmap *map, const frp_nmpc_
     BatchPlan bp;
     if (!args_ok(map, workspace, workspace_bytes) || !plan(map, q, &bp)) return FRP_ERR_ARG;
     if (!q->depth || !q->T_wc || !q->status || (q->last_depth && !q->last_T_wc)) return FRP_ERR_ARG;
-    if (!fuse_workspace || fuse_workspace_bytes < bp.bytes || ((uintptr_t)fuse_workspace & 7) != 0) return FRP_ERR_ARG;
+    Batch b;
+    if (!batch_at(fuse_workspace, fuse_workspace_bytes, bp, q->frames, &b)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Plan &p = bp.p;
-    const Batch b = batch_at(fuse_workspace, bp, q->frames);
-    const Geo g = geo(map);
-    const unsigned F = (unsigned)q->frames;
-    const auto blocks = [F](size_t n) { return dim3((unsigned)((n > 0 ? n : 1) + 255) / 256, F); };
-    const dim3 rays = blocks((size_t)p.f.N), box = blocks(p.nbmax); // a frame's box is known on the device only: the grids take its bound
-    hipLaunchKernelGGL(describe_kernel, dim3(1), dim3(FRP_OCCMAP_FUSE_MAX_FRAMES), 0, st, b, g, p.f, q->depth, q->last_depth, q->T_wc, q->last_T_wc,
+    hipLaunchKernelGGL(describe_kernel, dim3(1), dim3(FRP_OCCMAP_FUSE_MAX_FRAMES), 0, st, b, geo(map), p.f, q->depth, q->last_depth, q->T_wc, q->last_T_wc,
                        q->active, q->status, p.nbmax);
-    hipLaunchKernelGGL(init_kernel, blocks(p.nbmax > (size_t)HDR_INTS ? p.nbmax : (size_t)HDR_INTS), dim3(256), 0, st, b);
-    hipLaunchKernelGGL(project_kernel, rays, dim3(256), 0, st, b, g);
-    hipLaunchKernelGGL(setup_kernel, rays, dim3(256), 0, st, b, g);
-    for (int r = 1; r <= p.f.max_rounds; r++) {
-        hipLaunchKernelGGL(mark_kernel, rays, dim3(256), 0, st, b, g, r);
-        hipLaunchKernelGGL(stop_kernel, rays, dim3(256), 0, st, b, g, r);
-    }
-    hipLaunchKernelGGL(status_kernel, dim3(1), dim3(FRP_OCCMAP_FUSE_MAX_FRAMES), 0, st, b);
-    hipLaunchKernelGGL(count_kernel, rays, dim3(256), 0, st, b, g);
-    hipLaunchKernelGGL(update_kernel, box, dim3(256), 0, st, b, g, map->log_odds, map->occ, static_cast<uint32_t *>(workspace));
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    launch_init(b, p, st);
+    hipLaunchKernelGGL(project_kernel, blocks(b, (size_t)p.f.N), dim3(256), 0, st, b, geo(map));
+    return launch_from_setup(b, p, map, workspace, st);
 }
 
 } // extern "C"

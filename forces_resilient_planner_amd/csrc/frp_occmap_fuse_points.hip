@@ -1,7 +1,8 @@
 // frp_nmpc.h section (8), frp_nmpc_occmap_fuse_points.h: S point-cloud scans ray-cast into the device occupancy map in one call --
 // OccMap::raycastProcess (occ_grid/src/occ_map.cpp:441-533) for every scan, to the bit of running it scan after scan.  The scans are the
-// frames of the batched depth call (frp_occmap_fuse_batch.hip): the descriptors, the workspace slices, the stages' bodies from the ray
-// set-up on and the ordered update are frp_occmap_fuse.hpp's, shared, not copied.  What is this file's own:
+// frames of the batched depth call (frp_occmap_fuse_batch.hip): the descriptors, the workspace slices and the stage kernels from init
+// and the ray set-up on are that unit's, launched through fuse::batch::launch_init / launch_from_setup (frp_occmap_fuse.hpp), not
+// copied.  What is this file's own:
 //
 //   describe one lane per scan: the number of points (count[s] clamped to [0, P]), the sensor position and the ray box around it
 //            (set_ray_box) into the scan's descriptor; status of an inactive ({0, 0}) or refused (a non-finite origin) scan
@@ -10,7 +11,7 @@
 //            then takes its point from there, widens a float exactly, drops a point with a non-finite coordinate (it keeps its
 //            index) and runs the head of raycastProcess's loop (end_lane: length test, clip, setCacheOccupancy on the end voxel, the
 //            atomic minimum of the point index that is cache_rayend_'s dedup).  Nothing beyond count[s] points is read.
-//   init, setup, mark / stop rounds, status, count, update: as in frp_occmap_fuse_batch.hip.
+//   init, setup, mark / stop rounds, status, count, update: frp_occmap_fuse_batch.hip's kernels, the scan as the frame.
 // Launches: 2 * max_rounds + 7, whatever S and P.  No kernel waits for another workgroup.  Compiled with -ffp-contract=off like the
 // other fusion units.
 #include "frp_nmpc_occmap_fuse_points.h"
@@ -26,7 +27,7 @@ using batch::BatchPlan;
 using batch::Desc;
 using batch::ws_of;
 
-constexpr int TILE = 256; // points per workgroup of the load stage = its lanes
+constexpr int TILE = 256; // points per workgroup of the load stage = its lanes = those of batch::blocks
 
 __global__ void describe_kernel(Batch b, Geo g, Frame shape, int P, const int *count, const double *origin, const int *active, int *status,
                                 size_t nbmax)
@@ -63,14 +64,6 @@ __global__ void describe_kernel(Batch b, Geo g, Frame shape, int P, const int *c
     b.desc[k].fused = 0;
 }
 
-__global__ __launch_bounds__(256) void init_kernel(Batch b)
-{
-    const Desc &d = b.desc[blockIdx.y];
-    if (!d.live) return;
-    const Frame f = d.f;
-    init_lane(f, ws_of(b, blockIdx.y), blockIdx.x * blockDim.x + threadIdx.x);
-}
-
 // T = double or float; `all` = [S][P][3].  Every lane of a workgroup takes the same branches up to the barrier: what they depend on
 // (the scan's descriptor, the block's first point) is the same for all of them.
 template <class T>
@@ -93,58 +86,6 @@ __global__ __launch_bounds__(TILE) void load_kernel(Batch b, Geo g, const T *all
     double p[3] = {(double)tile[3 * lane], (double)tile[3 * lane + 1], (double)tile[3 * lane + 2]};
     if (!finite_all(p, 3)) return; // "no return": not in the scan
     end_lane(g, f, w, n, p);
-}
-
-__global__ __launch_bounds__(256) void setup_kernel(Batch b, Geo g)
-{
-    const Desc &d = b.desc[blockIdx.y];
-    if (!d.live) return;
-    const Frame f = d.f;
-    setup_lane(g, f, ws_of(b, blockIdx.y), blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-__global__ __launch_bounds__(256) void mark_kernel(Batch b, Geo g, int round)
-{
-    const Desc &d = b.desc[blockIdx.y];
-    if (!d.live) return;
-    const Ws w = ws_of(b, blockIdx.y);
-    if (round > 1 && w.hdr[round - 1] == 0) return; // the round before changed nothing: the scan is final
-    const Frame f = d.f;
-    mark_lane(g, f, w, round, blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-__global__ __launch_bounds__(256) void stop_kernel(Batch b, Geo g, int round)
-{
-    const Desc &d = b.desc[blockIdx.y];
-    if (!d.live) return;
-    const Ws w = ws_of(b, blockIdx.y);
-    if (round > 1 && w.hdr[round - 1] == 0) return;
-    const Frame f = d.f;
-    stop_lane(g, f, w, round, blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-__global__ void status_kernel(Batch b)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= b.frames) return;
-    Desc &d = b.desc[k];
-    if (!d.live) return; // fused stays 0
-    const Ws w = ws_of(b, k);
-    status_lane(d.f, w);
-    d.fused = w.hdr[H_CONVERGED];
-}
-
-__global__ __launch_bounds__(256) void count_kernel(Batch b, Geo g)
-{
-    const Desc &d = b.desc[blockIdx.y];
-    if (!d.fused) return;
-    const Frame f = d.f;
-    count_lane(g, f, ws_of(b, blockIdx.y), blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-__global__ __launch_bounds__(256) void update_kernel(Batch b, Geo g, double *log_odds, unsigned char *occ, uint32_t *plane)
-{
-    batch::update_lane(b, g, log_odds, occ, plane);
 }
 
 // Everything that can be refused on the host: the shape of the scans and the parameters (no origin, no pointer)
@@ -180,29 +121,19 @@ int frp_nmpc_occmap_fuse_points_batch(const frp_nmpc_occmap *map, const frp_nmpc
     if (!args_ok(map, workspace, workspace_bytes) || !plan(map, q, &bp)) return FRP_ERR_ARG;
     if (!q->origin || !q->status) return FRP_ERR_ARG;
     if (q->P > 0 && (q->points != nullptr) == (q->points_f32 != nullptr)) return FRP_ERR_ARG;
-    if (!fuse_workspace || fuse_workspace_bytes < bp.bytes || ((uintptr_t)fuse_workspace & 7) != 0) return FRP_ERR_ARG;
+    Batch b;
+    if (!batch::batch_at(fuse_workspace, fuse_workspace_bytes, bp, q->scans, &b)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Plan &p = bp.p;
-    const Batch b = batch::batch_at(fuse_workspace, bp, q->scans);
     const Geo g = geo(map);
-    const unsigned S = (unsigned)q->scans;
-    const auto blocks = [S](size_t n) { return dim3((unsigned)((n > 0 ? n : 1) + 255) / 256, S); };
-    const dim3 rays = blocks((size_t)q->P), box = blocks(p.nbmax); // a scan's count and box are known on the device only: the grids take their bounds
+    const dim3 tiles = batch::blocks(b, (size_t)p.f.N); // (plan_rays: N = P; a scan's count is known on the device only)
     hipLaunchKernelGGL(describe_kernel, dim3(1), dim3(FRP_OCCMAP_FUSE_POINTS_MAX_SCANS), 0, st, b, g, p.f, q->P, q->count, q->origin, q->active, q->status,
                        p.nbmax);
-    hipLaunchKernelGGL(init_kernel, blocks(p.nbmax > (size_t)HDR_INTS ? p.nbmax : (size_t)HDR_INTS), dim3(256), 0, st, b);
-    if (q->points_f32 && q->P > 0) hipLaunchKernelGGL(load_kernel<float>, rays, dim3(TILE), 0, st, b, g, q->points_f32, q->P);
-    else hipLaunchKernelGGL(load_kernel<double>, rays, dim3(TILE), 0, st, b, g, q->points, q->P); // (P = 0: no scan has a point, nothing is read)
-    hipLaunchKernelGGL(setup_kernel, rays, dim3(256), 0, st, b, g);
-    for (int r = 1; r <= p.f.max_rounds; r++) {
-        hipLaunchKernelGGL(mark_kernel, rays, dim3(256), 0, st, b, g, r);
-        hipLaunchKernelGGL(stop_kernel, rays, dim3(256), 0, st, b, g, r);
-    }
-    hipLaunchKernelGGL(status_kernel, dim3(1), dim3(FRP_OCCMAP_FUSE_POINTS_MAX_SCANS), 0, st, b);
-    hipLaunchKernelGGL(count_kernel, rays, dim3(256), 0, st, b, g);
-    hipLaunchKernelGGL(update_kernel, box, dim3(256), 0, st, b, g, map->log_odds, map->occ, static_cast<uint32_t *>(workspace));
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    batch::launch_init(b, p, st);
+    if (q->points_f32 && q->P > 0) hipLaunchKernelGGL(load_kernel<float>, tiles, dim3(TILE), 0, st, b, g, q->points_f32, q->P);
+    else hipLaunchKernelGGL(load_kernel<double>, tiles, dim3(TILE), 0, st, b, g, q->points, q->P); // (P = 0: no scan has a point, nothing is read)
+    return batch::launch_from_setup(b, p, map, workspace, st);
 }
 
 } // extern "C"

@@ -8,13 +8,14 @@
 //             status[f][0] carries it: no scratch.
 //   render    one lane per pixel, one 8 x 8 pixel tile per wavefront (four tiles, 16 x 16 pixels, per workgroup): neighbouring rays
 //             walk neighbouring columns of the bit plane and share its cache lines, and a tile's rays are of similar length, which
-//             is what bounds the divergence of the walk.  The frame's flag and pose are read through wave-uniform addresses.  A lane
+//             is what bounds the divergence of the walk (the same text as frp_occmap_render_scan.hip's: frp_occmap_raywalk.hpp says why).  The frame's flag and pose are read through wave-uniform addresses.  A lane
 //             keeps the last word of the plane it loaded: a step along z inside a word costs no load.  status[f][1] is one ballot
 //             count and one vector atomic per wavefront.  Every loop is bounded by the step bound, at most MAX_STEPS.
 //   poses     one lane per planner: T_wc = T_wb(state) * T_bc with the model's rotation (frp_model.hpp).
 #include "frp_nmpc_occmap_render.h"
 #include "frp_model.hpp"
 #include "frp_occmap_fuse.hpp"
+#include "frp_occmap_raywalk.hpp"
 
 namespace frp {
 namespace occmap {
@@ -33,17 +34,12 @@ __global__ void describe_kernel(int frames, const double *T_wc, const int *activ
     if (k >= frames) return;
     int flag = 1;
     if (active && active[k] == 0) flag = 0;
-    else if (!fuse::finite_all(T_wc + 16 * (size_t)k, 16)) flag = FRP_OCCMAP_FUSE_REFUSED;
+    else if (!finite_all(T_wc + 16 * (size_t)k, 16)) flag = FRP_OCCMAP_FUSE_REFUSED;
     status[2 * k] = flag;
     status[2 * k + 1] = 0;
 }
 
-// the axis of the smallest crossing: the comparison tree of RayCaster::step (raycast.cpp:336-363)
-__device__ inline int next_axis(const double *s_next)
-{
-    if (s_next[0] < s_next[1]) return s_next[0] < s_next[2] ? 0 : 2;
-    return s_next[1] < s_next[2] ? 1 : 2;
-}
+using raywalk::next_axis;
 
 __global__ __launch_bounds__(256) void render_kernel(Shape sh, Geo g, const double *T_wc, const uint32_t *plane, unsigned short *depth, int *voxel,
                                                      int *status)
@@ -148,11 +144,11 @@ static bool plan(const frp_nmpc_occmap *m, const frp_nmpc_occmap_render *r, Shap
     if (!valid(m) || !r) return false;
     if (r->frames < 1 || r->frames > FRP_OCCMAP_FUSE_MAX_FRAMES) return false;
     if (r->rows < 1 || r->cols < 1 || (long long)r->rows * r->cols > (long long)fuse::MAX_PIXELS) return false;
-    if (!fuse::finite_all(r->K, 9) || r->K[0] == 0.0 || r->K[4] == 0.0) return false;
+    if (!finite_all(r->K, 9) || r->K[0] == 0.0 || r->K[4] == 0.0) return false;
     const double par[2] = {r->depth_scale, r->max_range};
-    if (!fuse::finite_all(par, 2) || !(r->depth_scale > 0.0) || !(r->max_range > 0.0)) return false;
-    const double nb = 3.0 * (std::ceil(r->max_range / m->resolution) + 2.0);
-    if (!(nb <= (double)fuse::MAX_STEPS)) return false;
+    if (!finite_all(par, 2) || !(r->depth_scale > 0.0) || !(r->max_range > 0.0)) return false;
+    double nb;
+    if (!step_bound(r->max_range, m->resolution, &nb)) return false;
     sh->frames = r->frames; sh->rows = r->rows; sh->cols = r->cols;
     sh->tiles_u = (r->cols + BLOCK_PIX - 1) / BLOCK_PIX;
     sh->nb = (int)nb;

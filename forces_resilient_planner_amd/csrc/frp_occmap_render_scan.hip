@@ -1,7 +1,7 @@
 // frp_nmpc.h section (8), frp_nmpc_occmap_render_scan.h: S point scans rendered from the device occupancy map's bit plane, one ray per
 // entry of a table of beam directions -- the point-scan sibling of frp_occmap_render.hip.  The reference has no counterpart:
 // tests/occmap_scan_oracle.py is the specification, and every double computed here is computed in the order it writes down.  Compiled
-// with -ffp-contract=off like frp_occmap_render.hip.  The walk is that unit's, restated (its device code is left as it is).
+// with -ffp-contract=off like frp_occmap_render.hip.  The walk is that unit's, restated (frp_occmap_raywalk.hpp says why).
 //
 //   describe  one lane per scan: status[s] = {1, 0} rendered, {0, 0} inactive, {FRP_OCCMAP_FUSE_REFUSED, 0} a non-finite T_ws[s];
 //             count[s] = P or 0; origin[s] = the translation of T_ws[s] as it stands (not for an inactive scan).  status[s][0] hands the
@@ -15,7 +15,7 @@
 //             the mirror image of frp_occmap_fuse_points.hip's load stage.  status[s][1] is one ballot count and one vector atomic per
 //             wavefront.  Every loop is bounded by the step bound, at most MAX_STEPS.
 #include "frp_nmpc_occmap_render_scan.h"
-#include "frp_occmap_fuse.hpp"
+#include "frp_occmap_raywalk.hpp"
 
 namespace frp {
 namespace occmap {
@@ -36,7 +36,7 @@ __global__ void describe_kernel(int scans, int P, const double *T_ws, const int 
     const double *T = T_ws + 16 * (size_t)k;
     int flag = 1;
     if (active && active[k] == 0) flag = 0;
-    else if (!fuse::finite_all(T, 16)) flag = FRP_OCCMAP_FUSE_REFUSED;
+    else if (!finite_all(T, 16)) flag = FRP_OCCMAP_FUSE_REFUSED;
     status[2 * k] = flag;
     status[2 * k + 1] = 0;
     if (count) count[k] = flag == 1 ? P : 0;
@@ -44,12 +44,7 @@ __global__ void describe_kernel(int scans, int P, const double *T_ws, const int 
         for (int i = 0; i < 3; i++) origin[3 * (size_t)k + i] = T[4 * i + 3];
 }
 
-// the axis of the smallest crossing: the comparison tree of RayCaster::step (raycast.cpp:336-363)
-__device__ inline int next_axis(const double *s_next)
-{
-    if (s_next[0] < s_next[1]) return s_next[0] < s_next[2] ? 0 : 2;
-    return s_next[1] < s_next[2] ? 1 : 2;
-}
+using raywalk::next_axis;
 
 __global__ __launch_bounds__(WAVE) void render_kernel(Shape sh, Geo g, const double *beams, const double *T_ws, const uint32_t *plane, double *points,
                                                       float *points_f32, double *range, int *voxel, int *status)
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(WAVE) void render_kernel(Shape sh, Geo g, const dou
             t[i] = T[4 * i + 3];
         }
         const double length = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-        if (fuse::finite_all(b, 3) && length > 0.0 && fuse::finite_all(&length, 1)) { // the beam is fired
+        if (finite_all(b, 3) && length > 0.0 && finite_all(&length, 1)) { // the beam is fired
             for (int k = 0; k < 3; k++) {
                 c[k] = clamp_id(floored(t[k], g.origin[k], g.res_inv)); // posToIndex
                 step[k] = 0; s_next[k] = INFINITY; s_step[k] = INFINITY;
@@ -155,10 +150,10 @@ static bool plan(const frp_nmpc_occmap *m, const frp_nmpc_occmap_render_scan *r,
     if (r->scans < 1 || r->scans > FRP_OCCMAP_FUSE_POINTS_MAX_SCANS) return false;
     if (r->P < 1 || r->P > MAX_BEAMS) return false;
     const double par[3] = {r->min_range, r->max_range, r->far_range};
-    if (!fuse::finite_all(par, 3) || !(r->min_range >= 0.0) || !(r->max_range > 0.0) || r->min_range > r->max_range) return false;
+    if (!finite_all(par, 3) || !(r->min_range >= 0.0) || !(r->max_range > 0.0) || r->min_range > r->max_range) return false;
     if (r->far_range != 0.0 && !(r->far_range >= r->max_range)) return false;
-    const double nb = 3.0 * (std::ceil(r->max_range / m->resolution) + 2.0);
-    if (!(nb <= (double)fuse::MAX_STEPS)) return false;
+    double nb;
+    if (!step_bound(r->max_range, m->resolution, &nb)) return false;
     sh->scans = r->scans; sh->P = r->P; sh->nb = (int)nb;
     sh->min_range = r->min_range; sh->max_range = r->max_range; sh->far_range = r->far_range;
     return true;

@@ -736,11 +736,7 @@ class OccupancyMap:
         _check(getattr(lib(), name)(ctypes.byref(m), *args, ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes, ctypes.c_void_p(s.cuda_stream)), name)
 
     def _dev(self, a, dtype):
-        t = self.torch
-        if not t.is_tensor(a):
-            a = t.from_numpy(np.ascontiguousarray(a, dtype={t.float64: np.float64, t.float32: np.float32, t.int32: np.int32}[dtype]))
-        a = a.to(self.device, dtype=dtype).contiguous()
-        return a
+        return self._upload(a, dtype).to(self.device, dtype=dtype).contiguous()
 
     def astar_world(self):
         """The constants AstarPlanner reads: the world this map was built from, or the launch-file defaults around its geometry."""
@@ -772,6 +768,84 @@ class OccupancyMap:
         if stream is not None:
             pts.record_stream(stream)
 
+    # ---- what the sensor routes below share: one argument path ----
+
+    def _upload(self, a, dtype, what=""):
+        """An array as a device tensor of `dtype` (uint16: the array `what` has to be uint16 already); a tensor as it is."""
+        t = self.torch
+        if t.is_tensor(a):
+            return a
+        if dtype == t.uint16:
+            a = np.ascontiguousarray(a)
+            if a.dtype != np.uint16:
+                raise TypeError(f"{what} must be uint16 (the reference's depth_image.at<uint16_t>)")
+            return t.from_numpy(a.view(np.int16)).to(self.device).view(t.uint16)
+        return t.from_numpy(np.ascontiguousarray(a, dtype={t.float64: np.float64, t.float32: np.float32, t.int32: np.int32}[dtype])).to(self.device)
+
+    def _tensor(self, a, dtype, shape, message, exc=TypeError, upload=False):
+        """The checked device tensor behind an argument: an array is uploaded first (upload), a tensor is used in place.
+        shape: a tuple, None for an extent that is free.  Anything but a contiguous tensor of that dtype and shape on the map's
+        device: exc(message)."""
+        t = self.torch
+        if upload:
+            a = self._upload(a, dtype)
+        if (not t.is_tensor(a) or a.dtype != dtype or a.dim() != len(shape) or any(n is not None and n != m for n, m in zip(shape, a.shape))
+                or a.device != self.log_odds.device or not a.is_contiguous()):
+            raise exc(message)
+        return a
+
+    def _image(self, a, shape, what):
+        """depth / last_depth of fuse_depth_batch (uploaded when an array)"""
+        return self._tensor(self._upload(a, self.torch.uint16, what), self.torch.uint16, shape, f"{what} must be a contiguous [F, rows, cols] uint16 tensor on the map's device")
+
+    def _fuse_params(self, f, method, params, keys=None):
+        """The ray and filter parameters of the description f (`keys`; None: all): OCCMAP_FUSE_DEFAULTS under the caller's params."""
+        keys = keys or tuple(OCCMAP_FUSE_DEFAULTS)
+        unknown = set(params) - set(keys)
+        if unknown:
+            raise TypeError(f"{method}: unknown parameters {sorted(unknown)}")
+        for k in keys:
+            v = params.get(k, OCCMAP_FUSE_DEFAULTS[k])
+            setattr(f, k, int(v) if k in ("depth_filter_margin", "skip_pixel", "max_rounds") else float(v))
+
+    def _stream(self, stream):
+        return stream if stream is not None else self.torch.cuda.current_stream(self.device)
+
+    def _fuse(self, name, query, ws, f, refused, stream):
+        """A fusion call: the workspace description f asks for (`query`; 0: ValueError(refused)), kept in self.<ws> and grown when a
+        larger description needs it, then the call on the stream."""
+        m = self._map()
+        need = int(getattr(lib(), query)(ctypes.byref(m), ctypes.byref(f)))
+        if need == 0:
+            raise ValueError(refused)
+        w = getattr(self, ws)
+        if w is None or w.numel() < need:
+            w = self.torch.empty((need,), dtype=self.torch.uint8, device=self.device)
+            setattr(self, ws, w)
+        _check(getattr(lib(), name)(ctypes.byref(m), ctypes.byref(f), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes, ctypes.c_void_p(w.data_ptr()),
+                                    int(w.numel()), ctypes.c_void_p(self._stream(stream).cuda_stream)), name)
+
+    def _render(self, name, r, header, stream):
+        """A render call on the stream; ValueError for a description the library refuses."""
+        m = self._map()
+        rc = getattr(lib(), name)(ctypes.byref(m), ctypes.byref(r), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
+                                  ctypes.c_void_p(self._stream(stream).cuda_stream))
+        if rc == -1003:  # FRP_ERR_ARG
+            raise ValueError(f"{name} refuses this description (see include/{header})")
+        _check(rc, name)
+
+    @staticmethod
+    def _record(stream, *tensors):
+        """The tensors a call on a stream of the caller's reads or writes stay allocated until it has run."""
+        if stream is not None:
+            for a in tensors:
+                if a is not None:
+                    a.record_stream(stream)
+
+    @staticmethod
+    def _ptr(a):
+        return a.data_ptr() if a is not None else None
+
     def fuse_depth(self, depth, K, T_wc, *, shift_filter=False, status=None, stream=None, **params):
         """One camera frame into the map (OccMap::depthCallback's projectDepthImage + raycastProcess, occ_map.cpp:291-292):
         depth [rows, cols] uint16 (device tensor or array), K 3 x 3 intrinsics, T_wc 4 x 4 camera-to-world pose (host values).
@@ -782,15 +856,9 @@ class OccupancyMap:
         itself; the first filtered frame fuses nothing (has_first_depth_, :360-361) and returns [0, 0].
         status: a tensor to write into (a captured graph replays into the same buffer)."""
         t = self.torch
-        unknown = set(params) - set(OCCMAP_FUSE_DEFAULTS)
-        if unknown:
-            raise TypeError(f"fuse_depth: unknown parameters {sorted(unknown)}")
-        d = dict(OCCMAP_FUSE_DEFAULTS); d.update(params)
-        if not t.is_tensor(depth):
-            a = np.ascontiguousarray(depth)
-            if a.dtype != np.uint16:
-                raise TypeError("depth must be uint16 (the reference's depth_image.at<uint16_t>)")
-            depth = t.from_numpy(a.view(np.int16)).to(self.device).view(t.uint16)
+        f = OccMapFuse()
+        self._fuse_params(f, "fuse_depth", params)
+        depth = self._upload(depth, t.uint16, "depth")
         if depth.dtype != t.uint16 or depth.dim() != 2 or depth.device != self.log_odds.device:
             raise TypeError("depth must be a [rows, cols] uint16 tensor on the map's device")
         depth = depth.contiguous()
@@ -799,13 +867,12 @@ class OccupancyMap:
         if status is None:
             status = t.zeros((2,), dtype=t.int32, device=self.device)
         assert status.dtype == t.int32 and status.numel() >= 2 and status.is_contiguous() and status.device == self.log_odds.device
-        s = stream if stream is not None else t.cuda.current_stream(self.device)
         last = None
         if shift_filter:
             # The copy kept for the next frame is made on the stream of the call, behind whatever produced `depth` there (the caller
             # may reuse its tensor).  The previous frame stays referenced (_fusing_against) until the next call replaces it, so its
             # memory cannot go back to the allocator while this call's kernels, which read it, are still queued.
-            with t.cuda.stream(s):
+            with t.cuda.stream(self._stream(stream)):
                 keep = depth.clone()
             last, self._last_frame = self._last_frame, (keep, T.copy())
             self._fusing_against = last
@@ -814,7 +881,6 @@ class OccupancyMap:
                 return status
             if tuple(last[0].shape) != tuple(depth.shape):
                 raise ValueError("shift_filter: the frame size changed")
-        f = OccMapFuse()
         f.rows, f.cols = int(depth.shape[0]), int(depth.shape[1])
         f.depth = depth.data_ptr()
         f.last_depth = last[0].data_ptr() if last is not None else None
@@ -822,23 +888,10 @@ class OccupancyMap:
             f.last_T_wc[:] = [float(v) for v in last[1].ravel()]
         f.K[:] = [float(v) for v in Kh.ravel()]
         f.T_wc[:] = [float(v) for v in T.ravel()]
-        for k in ("depth_scale", "depth_filter_mindist", "depth_filter_tolerance", "prob_hit_log", "prob_miss_log", "min_ray_length", "max_ray_length"):
-            setattr(f, k, float(d[k]))
-        f.depth_filter_margin, f.skip_pixel, f.max_rounds = int(d["depth_filter_margin"]), int(d["skip_pixel"]), int(d["max_rounds"])
         f.status = status.data_ptr()
-        m = self._map()
-        need = int(lib().frp_nmpc_occmap_fuse_workspace_bytes(ctypes.byref(m), ctypes.byref(f)))
-        if need == 0:
-            raise ValueError("frp_nmpc_occmap_fuse_depth refuses this frame description (see include/frp_nmpc_occmap_fuse.h)")
-        if self.fuse_ws is None or self.fuse_ws.numel() < need:
-            self.fuse_ws = t.empty((need,), dtype=t.uint8, device=self.device)
-        _check(lib().frp_nmpc_occmap_fuse_depth(ctypes.byref(m), ctypes.byref(f), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
-                                                ctypes.c_void_p(self.fuse_ws.data_ptr()), int(self.fuse_ws.numel()), ctypes.c_void_p(s.cuda_stream)),
-               "frp_nmpc_occmap_fuse_depth")
-        if stream is not None:
-            depth.record_stream(stream)
-            if last is not None:
-                last[0].record_stream(stream)
+        self._fuse("frp_nmpc_occmap_fuse_depth", "frp_nmpc_occmap_fuse_workspace_bytes", "fuse_ws", f,
+                   "frp_nmpc_occmap_fuse_depth refuses this frame description (see include/frp_nmpc_occmap_fuse.h)", stream)
+        self._record(stream, depth, last[0] if last is not None else None)
         return status
 
     def fuse_depth_batch(self, depth, K, T_wc, *, last_depth=None, last_T_wc=None, active=None, status=None, stream=None, **params):
@@ -854,72 +907,32 @@ class OccupancyMap:
         [0, 0] for an inactive frame, [OCCMAP_FUSE_REFUSED, 0] for a pose fuse_depth would refuse (non-finite, singular last rotation).
         status: a tensor to write into.  ValueError: a description the library refuses."""
         t = self.torch
-        unknown = set(params) - set(OCCMAP_FUSE_DEFAULTS)
-        if unknown:
-            raise TypeError(f"fuse_depth_batch: unknown parameters {sorted(unknown)}")
-        d = dict(OCCMAP_FUSE_DEFAULTS); d.update(params)
-
-        def image(a, what):
-            if not t.is_tensor(a):
-                a = np.ascontiguousarray(a)
-                if a.dtype != np.uint16:
-                    raise TypeError(f"{what} must be uint16 (the reference's depth_image.at<uint16_t>)")
-                a = t.from_numpy(a.view(np.int16)).to(self.device).view(t.uint16)
-            if a.dtype != t.uint16 or a.dim() != 3 or a.device != self.log_odds.device or not a.is_contiguous():
-                raise TypeError(f"{what} must be a contiguous [F, rows, cols] uint16 tensor on the map's device")
-            return a
-
-        def poses(a, what):
-            if not t.is_tensor(a):
-                a = t.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)
-            if a.dtype != t.float64 or tuple(a.shape) != (F, 4, 4) or a.device != self.log_odds.device or not a.is_contiguous():
-                raise TypeError(f"{what} must be a contiguous [F, 4, 4] float64 tensor on the map's device")
-            return a
-
-        depth = image(depth, "depth")
+        f = OccMapFuseBatch()
+        self._fuse_params(f, "fuse_depth_batch", params)
+        depth = self._image(depth, (None, None, None), "depth")
         F = int(depth.shape[0])
-        T = poses(T_wc, "T_wc")
+        T = self._tensor(T_wc, t.float64, (F, 4, 4), "T_wc must be a contiguous [F, 4, 4] float64 tensor on the map's device", upload=True)
         if (last_depth is None) != (last_T_wc is None):
             raise ValueError("fuse_depth_batch: last_depth and last_T_wc go together")
         last = lastT = None
         if last_depth is not None:
-            last, lastT = image(last_depth, "last_depth"), poses(last_T_wc, "last_T_wc")
+            last = self._image(last_depth, (None, None, None), "last_depth")
+            lastT = self._tensor(last_T_wc, t.float64, (F, 4, 4), "last_T_wc must be a contiguous [F, 4, 4] float64 tensor on the map's device", upload=True)
             if tuple(last.shape) != tuple(depth.shape):
                 raise ValueError("fuse_depth_batch: last_depth has another shape than depth")
         if active is not None:
-            if not t.is_tensor(active):
-                active = t.from_numpy(np.ascontiguousarray(active, dtype=np.int32)).to(self.device)
-            if active.dtype != t.int32 or tuple(active.shape) != (F,) or active.device != self.log_odds.device or not active.is_contiguous():
-                raise TypeError("active must be a contiguous [F] int32 tensor on the map's device")
+            active = self._tensor(active, t.int32, (F,), "active must be a contiguous [F] int32 tensor on the map's device", upload=True)
         if status is None:
             status = t.zeros((F, 2), dtype=t.int32, device=self.device)
-        if status.dtype != t.int32 or tuple(status.shape) != (F, 2) or status.device != self.log_odds.device or not status.is_contiguous():
-            raise TypeError("status must be a contiguous [F, 2] int32 tensor on the map's device")
+        self._tensor(status, t.int32, (F, 2), "status must be a contiguous [F, 2] int32 tensor on the map's device")
         Kh = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
-        s = stream if stream is not None else t.cuda.current_stream(self.device)
-        f = OccMapFuseBatch()
         f.frames, f.rows, f.cols = F, int(depth.shape[1]), int(depth.shape[2])
         f.depth, f.T_wc, f.status = depth.data_ptr(), T.data_ptr(), status.data_ptr()
-        f.last_depth = last.data_ptr() if last is not None else None
-        f.last_T_wc = lastT.data_ptr() if lastT is not None else None
-        f.active = active.data_ptr() if active is not None else None
+        f.last_depth, f.last_T_wc, f.active = self._ptr(last), self._ptr(lastT), self._ptr(active)
         f.K[:] = [float(v) for v in Kh.ravel()]
-        for k in ("depth_scale", "depth_filter_mindist", "depth_filter_tolerance", "prob_hit_log", "prob_miss_log", "min_ray_length", "max_ray_length"):
-            setattr(f, k, float(d[k]))
-        f.depth_filter_margin, f.skip_pixel, f.max_rounds = int(d["depth_filter_margin"]), int(d["skip_pixel"]), int(d["max_rounds"])
-        m = self._map()
-        need = int(lib().frp_nmpc_occmap_fuse_batch_workspace_bytes(ctypes.byref(m), ctypes.byref(f)))
-        if need == 0:
-            raise ValueError("frp_nmpc_occmap_fuse_depth_batch refuses this batch description (see include/frp_nmpc_occmap_fuse_batch.h)")
-        if self.fuse_batch_ws is None or self.fuse_batch_ws.numel() < need:
-            self.fuse_batch_ws = t.empty((need,), dtype=t.uint8, device=self.device)
-        _check(lib().frp_nmpc_occmap_fuse_depth_batch(ctypes.byref(m), ctypes.byref(f), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
-                                                      ctypes.c_void_p(self.fuse_batch_ws.data_ptr()), int(self.fuse_batch_ws.numel()),
-                                                      ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_occmap_fuse_depth_batch")
-        if stream is not None:
-            for a in (depth, T, last, lastT, active):
-                if a is not None:
-                    a.record_stream(stream)
+        self._fuse("frp_nmpc_occmap_fuse_depth_batch", "frp_nmpc_occmap_fuse_batch_workspace_bytes", "fuse_batch_ws", f,
+                   "frp_nmpc_occmap_fuse_depth_batch refuses this batch description (see include/frp_nmpc_occmap_fuse_batch.h)", stream)
+        self._record(stream, depth, T, last, lastT, active)
         return status
 
     def fuse_points(self, points, origin, *, count=None, active=None, status=None, stream=None, **params):
@@ -937,10 +950,8 @@ class OccupancyMap:
         [-max_rounds, rays] for a scan that did not converge, [0, 0] inactive, [OCCMAP_FUSE_REFUSED, 0] for a non-finite origin.
         status: a tensor to write into.  ValueError: arguments of another kind than described, or a description the library refuses."""
         t = self.torch
-        unknown = set(params) - set(OCCMAP_FUSE_POINTS_PARAMS)
-        if unknown:
-            raise TypeError(f"fuse_points: unknown parameters {sorted(unknown)}")
-        d = dict(OCCMAP_FUSE_DEFAULTS); d.update(params)
+        f = OccMapFusePoints()
+        self._fuse_params(f, "fuse_points", params, OCCMAP_FUSE_POINTS_PARAMS)
         if not t.is_tensor(points) or points.device != self.log_odds.device:
             raise ValueError("fuse_points: points must be a tensor on the map's device")
         if points.dtype not in (t.float64, t.float32):
@@ -952,13 +963,11 @@ class OccupancyMap:
         S, P = (1, int(points.shape[0])) if points.dim() == 2 else (int(points.shape[0]), int(points.shape[1]))
 
         def per_scan(a, dtype, shape, what):
-            if not t.is_tensor(a):
-                a = t.from_numpy(np.ascontiguousarray(a, dtype={t.float64: np.float64, t.int32: np.int32}[dtype])).to(self.device)
+            a = self._upload(a, dtype)
             if S == 1 and a.dim() == len(shape) - 1 and a.is_contiguous():
                 a = a.reshape(shape)  # one scan given without its leading dimension: a view, still the caller's storage
-            if a.dtype != dtype or tuple(a.shape) != shape or a.device != self.log_odds.device or not a.is_contiguous():
-                raise ValueError(f"fuse_points: {what} must be a contiguous {list(shape)} {dtype} tensor on the map's device (or an array of that shape)")
-            return a
+            return self._tensor(a, dtype, shape, f"fuse_points: {what} must be a contiguous {list(shape)} {dtype} tensor on the map's device "
+                                "(or an array of that shape)", ValueError)
 
         origin = per_scan(origin, t.float64, (S, 3), "origin")
         if count is not None:
@@ -967,32 +976,15 @@ class OccupancyMap:
             active = per_scan(active, t.int32, (S,), "active")
         if status is None:
             status = t.zeros((S, 2), dtype=t.int32, device=self.device)
-        if not t.is_tensor(status) or status.dtype != t.int32 or tuple(status.shape) != (S, 2) or status.device != self.log_odds.device or not status.is_contiguous():
-            raise ValueError("fuse_points: status must be a contiguous [S, 2] int32 tensor on the map's device")
-        s = stream if stream is not None else t.cuda.current_stream(self.device)
-        f = OccMapFusePoints()
+        self._tensor(status, t.int32, (S, 2), "fuse_points: status must be a contiguous [S, 2] int32 tensor on the map's device", ValueError)
         f.scans, f.P = S, P
         f.points = points.data_ptr() if P > 0 and points.dtype == t.float64 else None
         f.points_f32 = points.data_ptr() if P > 0 and points.dtype == t.float32 else None
-        f.count = count.data_ptr() if count is not None else None
-        f.active = active.data_ptr() if active is not None else None
+        f.count, f.active = self._ptr(count), self._ptr(active)
         f.origin, f.status = origin.data_ptr(), status.data_ptr()
-        for k in ("prob_hit_log", "prob_miss_log", "min_ray_length", "max_ray_length"):
-            setattr(f, k, float(d[k]))
-        f.max_rounds = int(d["max_rounds"])
-        m = self._map()
-        need = int(lib().frp_nmpc_occmap_fuse_points_workspace_bytes(ctypes.byref(m), ctypes.byref(f)))
-        if need == 0:
-            raise ValueError(f"frp_nmpc_occmap_fuse_points_batch refuses this description: {S} scans of {P} points (see include/frp_nmpc_occmap_fuse_points.h)")
-        if self.fuse_points_ws is None or self.fuse_points_ws.numel() < need:
-            self.fuse_points_ws = t.empty((need,), dtype=t.uint8, device=self.device)
-        _check(lib().frp_nmpc_occmap_fuse_points_batch(ctypes.byref(m), ctypes.byref(f), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
-                                                       ctypes.c_void_p(self.fuse_points_ws.data_ptr()), int(self.fuse_points_ws.numel()),
-                                                       ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_occmap_fuse_points_batch")
-        if stream is not None:
-            for a in (points, origin, count, active):
-                if a is not None:
-                    a.record_stream(stream)
+        self._fuse("frp_nmpc_occmap_fuse_points_batch", "frp_nmpc_occmap_fuse_points_workspace_bytes", "fuse_points_ws", f,
+                   f"frp_nmpc_occmap_fuse_points_batch refuses this description: {S} scans of {P} points (see include/frp_nmpc_occmap_fuse_points.h)", stream)
+        self._record(stream, points, origin, count, active)
         return status
 
     def render_depth(self, T_wc, K, rows, cols, *, max_range, depth_scale=1000.0, active=None, out=None, voxel=None, status=None, stream=None):
@@ -1005,45 +997,28 @@ class OccupancyMap:
         int32 tensor [F, 2] for {1, returns} / {0, 0} inactive / {OCCMAP_FUSE_REFUSED, 0} a non-finite pose.  Returns the depth
         tensor; nothing is synchronised.  ValueError: a description the library refuses."""
         t = self.torch
-        dev = self.log_odds.device
-        if not t.is_tensor(T_wc):
-            T_wc = t.from_numpy(np.ascontiguousarray(T_wc, dtype=np.float64)).to(self.device)
-        if T_wc.dtype != t.float64 or T_wc.dim() != 3 or tuple(T_wc.shape[1:]) != (4, 4) or T_wc.device != dev or not T_wc.is_contiguous():
-            raise TypeError("T_wc must be a contiguous [F, 4, 4] float64 tensor on the map's device")
+        T_wc = self._tensor(T_wc, t.float64, (None, 4, 4), "T_wc must be a contiguous [F, 4, 4] float64 tensor on the map's device", upload=True)
         F, rows, cols = int(T_wc.shape[0]), int(rows), int(cols)
         if active is not None:
-            if not t.is_tensor(active):
-                active = t.from_numpy(np.ascontiguousarray(active, dtype=np.int32)).to(self.device)
-            if active.dtype != t.int32 or tuple(active.shape) != (F,) or active.device != dev or not active.is_contiguous():
-                raise TypeError("active must be a contiguous [F] int32 tensor on the map's device")
+            active = self._tensor(active, t.int32, (F,), "active must be a contiguous [F] int32 tensor on the map's device", upload=True)
         if F < 1 or rows < 1 or cols < 1:
             raise ValueError("render_depth: at least one frame, one row and one column")
         if out is None:
             out = t.zeros((F, rows, cols), dtype=t.int16, device=self.device).view(t.uint16)
-        if out.dtype != t.uint16 or tuple(out.shape) != (F, rows, cols) or out.device != dev or not out.is_contiguous():
-            raise TypeError("out must be a contiguous [F, rows, cols] uint16 tensor on the map's device")
-        if voxel is not None and (voxel.dtype != t.int32 or tuple(voxel.shape) != (F, rows, cols) or voxel.device != dev or not voxel.is_contiguous()):
-            raise TypeError("voxel must be a contiguous [F, rows, cols] int32 tensor on the map's device")
+        self._tensor(out, t.uint16, (F, rows, cols), "out must be a contiguous [F, rows, cols] uint16 tensor on the map's device")
+        if voxel is not None:
+            self._tensor(voxel, t.int32, (F, rows, cols), "voxel must be a contiguous [F, rows, cols] int32 tensor on the map's device")
         if status is None:
             status = t.zeros((F, 2), dtype=t.int32, device=self.device)
-        if status.dtype != t.int32 or tuple(status.shape) != (F, 2) or status.device != dev or not status.is_contiguous():
-            raise TypeError("status must be a contiguous [F, 2] int32 tensor on the map's device")
+        self._tensor(status, t.int32, (F, 2), "status must be a contiguous [F, 2] int32 tensor on the map's device")
         r = OccMapRender()
         r.frames, r.rows, r.cols = F, rows, cols
-        r.T_wc, r.active = T_wc.data_ptr(), active.data_ptr() if active is not None else None
+        r.T_wc, r.active = T_wc.data_ptr(), self._ptr(active)
         r.K[:] = [float(v) for v in np.ascontiguousarray(K, dtype=np.float64).reshape(9)]
         r.depth_scale, r.max_range = float(depth_scale), float(max_range)
-        r.depth, r.voxel, r.status = out.data_ptr(), voxel.data_ptr() if voxel is not None else None, status.data_ptr()
-        s = stream if stream is not None else t.cuda.current_stream(self.device)
-        m = self._map()
-        rc = lib().frp_nmpc_occmap_render_depth(ctypes.byref(m), ctypes.byref(r), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes, ctypes.c_void_p(s.cuda_stream))
-        if rc == -1003:  # FRP_ERR_ARG
-            raise ValueError("frp_nmpc_occmap_render_depth refuses this description (see include/frp_nmpc_occmap_render.h)")
-        _check(rc, "frp_nmpc_occmap_render_depth")
-        if stream is not None:
-            for a in (T_wc, active, out, voxel, status):
-                if a is not None:
-                    a.record_stream(stream)
+        r.depth, r.voxel, r.status = out.data_ptr(), self._ptr(voxel), status.data_ptr()
+        self._render("frp_nmpc_occmap_render_depth", r, "frp_nmpc_occmap_render.h", stream)
+        self._record(stream, T_wc, active, out, voxel, status)
         return out
 
     def render_scan(self, T_ws, beams, *, max_range, min_range=0.0, far_range=0.0, dtype=None, active=None, points=None, points_f32=None,
@@ -1064,25 +1039,20 @@ class OccupancyMap:
         non-finite pose, its points NaN).  Returns (points, origin, count, status); nothing is synchronised.  ValueError: a
         description the library refuses."""
         t = self.torch
-        dev = self.log_odds.device
 
-        def given(a, dt, shape, what, upload=False):
-            if upload and not t.is_tensor(a):
-                a = t.from_numpy(np.ascontiguousarray(a, dtype={t.float64: np.float64, t.int32: np.int32}[dt])).to(self.device)
-            if not t.is_tensor(a) or a.dtype != dt or (shape is not None and tuple(a.shape) != shape) or a.device != dev or not a.is_contiguous():
-                raise TypeError(f"render_scan: {what} must be a contiguous {list(shape) if shape else ''} {dt} tensor on the map's device")
-            return a
+        def given(a, dt, shape, what, free=False, upload=False):  # free: the shape was checked by the caller, its message says none
+            return self._tensor(a, dt, shape, f"render_scan: {what} must be a contiguous {'' if free else list(shape)} {dt} tensor on the map's device",
+                                upload=upload)
 
-        if not t.is_tensor(T_ws):
-            T_ws = t.from_numpy(np.ascontiguousarray(T_ws, dtype=np.float64)).to(self.device)
+        T_ws = self._upload(T_ws, t.float64)
         if T_ws.dim() != 3 or tuple(T_ws.shape[1:]) != (4, 4):
             raise TypeError("render_scan: T_ws must be [S, 4, 4]")
-        T_ws = given(T_ws, t.float64, None, "T_ws")
+        T_ws = given(T_ws, t.float64, (None, 4, 4), "T_ws", free=True)
         if not t.is_tensor(beams):
             beams = t.from_numpy(np.array(beams, dtype=np.float64, order="C")).to(self.device)  # (a copy: a table kept read-only uploads too)
         if beams.dim() != 2 or beams.shape[1] != 3:
             raise TypeError("render_scan: beams must be [P, 3]")
-        beams = given(beams, t.float64, None, "beams")
+        beams = given(beams, t.float64, (None, 3), "beams", free=True)
         S, P = int(T_ws.shape[0]), int(beams.shape[0])
         if S < 1 or P < 1:
             raise ValueError("render_scan: at least one scan and one beam")
@@ -1109,23 +1079,14 @@ class OccupancyMap:
             voxel = given(voxel, t.int32, (S, P), "voxel")
         r = OccMapRenderScan()
         r.scans, r.P = S, P
-        r.beams, r.T_ws, r.active = beams.data_ptr(), T_ws.data_ptr(), active.data_ptr() if active is not None else None
+        r.beams, r.T_ws, r.active = beams.data_ptr(), T_ws.data_ptr(), self._ptr(active)
         r.min_range, r.max_range, r.far_range = float(min_range), float(max_range), float(far_range)
         r.points = points.data_ptr() if points.dtype == t.float64 else None
-        r.points_f32 = points.data_ptr() if points.dtype == t.float32 else points_f32.data_ptr() if points_f32 is not None else None
+        r.points_f32 = points.data_ptr() if points.dtype == t.float32 else self._ptr(points_f32)
         r.origin, r.count, r.status = origin.data_ptr(), count.data_ptr(), status.data_ptr()
-        r.range, r.voxel = range.data_ptr() if range is not None else None, voxel.data_ptr() if voxel is not None else None
-        s = stream if stream is not None else t.cuda.current_stream(self.device)
-        m = self._map()
-        rc = lib().frp_nmpc_occmap_render_scan_batch(ctypes.byref(m), ctypes.byref(r), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes,
-                                                     ctypes.c_void_p(s.cuda_stream))
-        if rc == -1003:  # FRP_ERR_ARG
-            raise ValueError("frp_nmpc_occmap_render_scan_batch refuses this description (see include/frp_nmpc_occmap_render_scan.h)")
-        _check(rc, "frp_nmpc_occmap_render_scan_batch")
-        if stream is not None:
-            for a in (T_ws, beams, active, points, points_f32, origin, count, range, voxel, status):
-                if a is not None:
-                    a.record_stream(stream)
+        r.range, r.voxel = self._ptr(range), self._ptr(voxel)
+        self._render("frp_nmpc_occmap_render_scan_batch", r, "frp_nmpc_occmap_render_scan.h", stream)
+        self._record(stream, T_ws, beams, active, points, points_f32, origin, count, range, voxel, status)
         return points, origin, count, status
 
     def camera_poses(self, state, T_bc, out=None, stream=None):
@@ -1133,21 +1094,17 @@ class OccupancyMap:
         place, or array) and the body-to-camera transform T_bc 4 x 4 (host): what render_depth and fuse_depth_batch take as poses,
         computed where the states are (frp_nmpc_occmap_camera_poses).  out: the tensor to write into."""
         t = self.torch
-        st = state if t.is_tensor(state) else self._dev(state, t.float64)
-        if st.dtype != t.float64 or st.dim() != 2 or st.shape[1] != 9 or st.device != self.log_odds.device or not st.is_contiguous():
-            raise TypeError("state must be a contiguous [B, 9] float64 tensor on the map's device")
+        st = self._tensor(state, t.float64, (None, 9), "state must be a contiguous [B, 9] float64 tensor on the map's device", upload=True)
         B = int(st.shape[0])
         if out is None:
             out = t.zeros((B, 4, 4), dtype=t.float64, device=self.device)
-        if out.dtype != t.float64 or tuple(out.shape) != (B, 4, 4) or out.device != self.log_odds.device or not out.is_contiguous():
-            raise TypeError("out must be a contiguous [B, 4, 4] float64 tensor on the map's device")
+        self._tensor(out, t.float64, (B, 4, 4), "out must be a contiguous [B, 4, 4] float64 tensor on the map's device")
         Tb = (ctypes.c_double * 16)(*[float(v) for v in np.ascontiguousarray(T_bc, dtype=np.float64).reshape(16)])
-        s = stream if stream is not None else t.cuda.current_stream(self.device)
         _check(lib().frp_nmpc_occmap_camera_poses(B, ctypes.c_void_p(st.data_ptr()) if B else None, Tb, ctypes.c_void_p(out.data_ptr()) if B else None,
-                                                  ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_occmap_camera_poses")
-        if stream is not None:
-            st.record_stream(stream); out.record_stream(stream)
+                                                  ctypes.c_void_p(self._stream(stream).cuda_stream)), "frp_nmpc_occmap_camera_poses")
+        self._record(stream, st, out)
         return out
+
 
     def local_view(self, centres, P, out=None, stream=None):
         """local_box + localOccVisCallback's cloud (occ_map.cpp:177-215) of every planner: centres [B,3] f64 (device tensor or

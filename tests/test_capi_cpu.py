@@ -459,8 +459,12 @@ def test_static_archives_with_the_references_file_names_link_and_fail_loudly_wit
         assert r.returncode == 0 and r.stdout.split()[:2] == ["-100", "-100"], r.stdout + r.stderr
 
 
-def _kernel_instantiations(so, tmp_path):
-    """Demangled names of the nmpc_ipm_lds_kernel instantiations in the gfx950 code objects of a built library: every
+SOLVER_KERNEL = r"void (\S+::nmpc_ipm_lds_kernel<[^>]*>)\(frp::KernelArgs\) \(\.kd\)$"
+
+
+def _kernel_instantiations(so, tmp_path, pattern=SOLVER_KERNEL):
+    """Demangled names of the nmpc_ipm_lds_kernel instantiations (or of the kernels whose descriptor line matches another
+    `pattern`, group 1 = the name) in the gfx950 code objects of a built library: every
     clang offload bundle of its .hip_fatbin section (one per translation unit) is unbundled here and its kernel descriptors
     listed, demangled, with the ROCm LLVM tools.  Returns {name: number of bundles that hold it}."""
     import struct
@@ -483,7 +487,7 @@ def _kernel_instantiations(so, tmp_path):
             co = tmp_path / f"co{bundles}.elf"
             co.write_bytes(data[pos + o:pos + o + size])
             syms = subprocess.run([f"{llvm}/llvm-readelf", "-s", "-C", "--wide", str(co)], check=True, capture_output=True, text=True).stdout
-            kern = [re.search(r"void (\S+::nmpc_ipm_lds_kernel<[^>]*>)\(frp::KernelArgs\) \(\.kd\)$", ln) for ln in syms.splitlines()]
+            kern = [re.search(pattern, ln) for ln in syms.splitlines()]
             kern = {m.group(1) for m in kern if m}  # (.dynsym and .symtab list each descriptor)
             for nm in kern:
                 names[nm] = names.get(nm, 0) + 1
@@ -518,6 +522,20 @@ def test_slot_reuse_cases_cover_every_kernel_instantiation_that_ships(tmp_path):
     names, _ = _kernel_instantiations(solver.LIB_PATH, tmp_path)
     covered = {l[1] for l in LAUNCHES}
     assert set(names) == covered, (sorted(set(names) - covered), sorted(covered - set(names)))
+
+
+def test_batch_fusion_stage_kernels_ship_once(tmp_path):
+    """The seven stage kernels that depth frames and point scans share exist once in the built library, under
+    frp::occmap::fuse::batch (frp_occmap_fuse_batch.hip); frp::occmap::fuse::points holds its own first stage alone.  Symbol names only."""
+    from forces_resilient_planner_amd import build
+    if not os.path.exists(solver.LIB_PATH):
+        build.build_native(force=False, verbose=False)
+    names, _ = _kernel_instantiations(solver.LIB_PATH, tmp_path, r"\s(?:void )?(frp::occmap::fuse::(?:batch|points)::\w+(?:<[^>]*>)?)\(.*\) \(\.kd\)$")
+    assert all(c == 1 for c in names.values()), names
+    stages = {"init", "setup", "mark", "stop", "status", "count", "update"}
+    assert {n for n in names if "::batch::" in n} == {f"frp::occmap::fuse::batch::{k}_kernel" for k in stages | {"describe", "project"}}, names
+    assert {n for n in names if "::points::" in n} == {"frp::occmap::fuse::points::describe_kernel", "frp::occmap::fuse::points::load_kernel<float>",
+                                                       "frp::occmap::fuse::points::load_kernel<double>"}, names
 
 
 def test_solver_sources_carry_no_experiment_knobs():

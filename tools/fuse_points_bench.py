@@ -12,10 +12,12 @@ Timed, in ONE process, the three routes ALTERNATING window by window, their orde
   * fuse_points on the scans as float32 (rounded once on the host; its rays are those of the rounded points, checked on their own).
 Per route: median, p10, p90, min and max over the windows; the p10 - p90 spread of the depth route is the yardstick for a
 difference.  Also recorded: launches per call, the rounds and rays per scan, the bytes of the fusion workspaces.
-Where a difference comes from needs per-kernel times: run `--profile N` (N calls per route, nothing timed) under
-rocprofv3 --kernel-trace --stats --output-format csv in a run of its own, then `--merge-stats <..._kernel_stats.csv>` adds each
-route's microseconds per call and kernel (the routes' kernels differ in their namespace: fuse::batch:: / fuse::points::) to the JSON.
-   python tools/fuse_points_bench.py [--frames 16] [--reps 10] [--windows 15] [--out FILE] | --profile N | --merge-stats CSV --calls N"""
+Where a difference comes from needs per-kernel times.  Both routes run the same stage kernels (frp::occmap::fuse::batch::, the only
+copy in the library), so a trace cannot tell them apart: profile ONE route per run -- `--profile N --route depth` and `--profile N
+--route points` (N calls of that route, nothing timed), each under rocprofv3 --kernel-trace --stats --output-format csv in a run of
+its own -- then `--merge-stats <..._kernel_stats.csv> --route ROUTE --calls N` once per run adds that route's microseconds per call
+and kernel to the JSON.
+   python tools/fuse_points_bench.py [--frames 16] [--reps 10] [--windows 15] [--out FILE] | --profile N --route R | --merge-stats CSV --route R --calls N"""
 import argparse
 import csv
 import ctypes
@@ -60,33 +62,35 @@ def map_sha(dm):
     return hashlib.sha256(dm.log_odds.cpu().numpy().tobytes() + dm.occ.cpu().numpy().tobytes() + dm.ws[:dm.ws_bytes // 4].cpu().numpy().tobytes()).hexdigest()
 
 
-def merge_stats(path, out, calls):
-    """Per-kernel totals of a rocprofv3 kernel-stats CSV of a --profile run -> microseconds per call, per route and kernel."""
+def merge_stats(path, out, calls, route):
+    """Per-kernel totals of a rocprofv3 kernel-stats CSV of a --profile --route run -> that route's microseconds per call and kernel."""
     with open(path, newline="") as f:
         rows = list(csv.DictReader(f))
-    us = {"depth": {}, "points": {}}
+    us = {}
     for r in rows:
         name = r.get("Name") or r.get("KernelName") or ""
         ns = float(r.get("TotalDurationNs") or r.get("TotalDuration(ns)") or 0)
-        m = re.search(r"fuse::(batch|points)::(\w+)_kernel", name)
+        m = re.search(r"fuse::(?:batch|points)::(\w+)_kernel", name)
         if m:
-            route = "depth" if m.group(1) == "batch" else "points"
-            us[route][m.group(2)] = us[route].get(m.group(2), 0.0) + ns / 1000.0 / calls
-    if not us["depth"] or not us["points"]:
-        raise SystemExit(f"{path}: no frp::occmap::fuse::batch / ::points kernels in it")
+            us[m.group(1)] = us.get(m.group(1), 0.0) + ns / 1000.0 / calls
+    if ("load" in us) != (route == "points") or ("project" in us) != (route == "depth"):
+        raise SystemExit(f"{path}: not a trace of the {route} route alone (its first stage: {'load' if route == 'points' else 'project'})")
     with open(out) as f:
         res = json.load(f)
-    res["kernel_us_per_call"] = dict(source="rocprofv3 --kernel-trace --stats, a run of its own (--profile): depth = fuse_depth_batch, points = fuse_points on "
-                                            "float64 and float32 scans in equal numbers (load is the mean of the two)", calls_per_route=calls,
-                                     depth=us["depth"], points=us["points"], depth_total=sum(us["depth"].values()), points_total=sum(us["points"].values()))
+    k = res.setdefault("kernel_us_per_call", {})
+    k["source"] = ("rocprofv3 --kernel-trace --stats, one run per route (--profile --route): depth = fuse_depth_batch, points = fuse_points on "
+                   "float64 and float32 scans in equal numbers (load is the mean of the two)")
+    k["calls_per_route"] = calls
+    k[route], k[route + "_total"] = us, sum(us.values())
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
-    print(json.dumps(res["kernel_us_per_call"]))
+    print(json.dumps(k))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--profile", type=int, default=0, metavar="N", help="N calls of fuse_depth_batch and N of fuse_points (half float64, half float32), nothing timed")
+    ap.add_argument("--profile", type=int, default=0, metavar="N", help="N calls of the --route, nothing timed")
+    ap.add_argument("--route", choices=("depth", "points"), help="with --profile / --merge-stats: fuse_depth_batch, or fuse_points (half float64, half float32)")
     ap.add_argument("--merge-stats", metavar="CSV")
     ap.add_argument("--calls", type=int, default=0, help="with --merge-stats: the N of the --profile run")
     ap.add_argument("--frames", type=int, default=16)
@@ -94,8 +98,10 @@ def main():
     ap.add_argument("--windows", type=int, default=15)
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
+    if (a.merge_stats or a.profile) and not a.route:
+        ap.error("--profile and --merge-stats take one --route per run: both routes run the same kernels")
     if a.merge_stats:
-        return merge_stats(a.merge_stats, a.out, a.calls if a.calls > 0 else 1)
+        return merge_stats(a.merge_stats, a.out, a.calls if a.calls > 0 else 1, a.route)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("fuse_points_bench needs a GPU: nothing here is a CPU number")
@@ -125,8 +131,7 @@ def main():
 
     if a.profile:
         for k in range(a.profile):
-            run["depth"]()
-            run["points_f64" if k % 2 == 0 else "points_f32"]()
+            run["depth" if a.route == "depth" else "points_f64" if k % 2 == 0 else "points_f32"]()
         torch.cuda.synchronize()
         return
 

@@ -1,18 +1,25 @@
 #!/usr/bin/env python3
-"""Is the gfx950 code of the solver kernels in two source trees the same, byte for byte?
+"""Is the gfx950 code of the kernels in two source trees the same, byte for byte?
 
     python tools/solver_identity.py                      # HEAD (git archive) against the working tree
     python tools/solver_identity.py --parent REV         # another parent commit
     python tools/solver_identity.py --a DIR --b DIR      # any two trees
     python tools/solver_identity.py --out profiles/x.txt # write the report to a file as well
+    python tools/solver_identity.py --units frp_occmap_render.hip frp_occmap_render_scan.hip   # other units than the solver's five
+    python tools/solver_identity.py --units frp_occmap_fuse_points.hip:frp_occmap_fuse_batch.hip --rename fuse::points::=fuse::batch:: --common
+                                                         # side A's unit against ANOTHER unit of side B, kernel by namesake
 
-For each of the five solver translation units, and for each flag set that ships -- the unit's PER_SOURCE_FLAGS of its own
+For each translation unit (by default the five of the solver), and for each flag set that ships -- the unit's PER_SOURCE_FLAGS of its own
 tree's build.py and, for the main unit, the same without the -mllvm switches (build_default_flags_lib) -- the unit is compiled
 device-only, its code object unbundled, and compared: the raw bytes of .text and .rodata (as sha256), the kernel symbols with
 their demangled names, and each kernel's metadata from the notes (registers, LDS, scratch, spills, workgroup size).  Whole
 ELF files are not compared: they carry a compilation-unit id derived from the output path.
 
-A refactoring of the solver sources is harmless when every unit reports "identical".  Exit status 1 otherwise.
+Kernels are paired by demangled name.  --rename OLD=NEW rewrites side A's names first, so that a kernel that moved to another
+namespace meets its namesake; --common compares the kernels both sides have and only lists the others (a unit that lost or gained
+kernels: the sections then differ by construction and are not compared).
+
+A refactoring of the sources is harmless when every unit reports "identical".  Exit status 1 otherwise.
 The tool needs a compiler and a parent commit and no GPU; it is not part of the test suite.
 """
 import argparse
@@ -97,7 +104,7 @@ def inspect(tree, B, unit, label, flags, work):
     for n, d in zip(names, demangled):
         addr, size = syms[n][:2]
         code = raw[".text"][addr - text_addr: addr - text_addr + size]
-        out["kernels"][n] = {"demangled": d, "size": size, "sha256": hashlib.sha256(code).hexdigest(), "meta": meta.get(n, {})}
+        out["kernels"][d] = {"symbol": n, "size": size, "sha256": hashlib.sha256(code).hexdigest(), "meta": meta.get(n, {})}
     return out
 
 
@@ -120,18 +127,30 @@ def kernel_metadata(notes):
     return out
 
 
-def compare(a, b):
-    """'' when identical, else what differs first."""
-    if sorted(a["kernels"]) != sorted(b["kernels"]):
+def renamed(r, renames):
+    """Side A's description with its kernels under the names they have on side B."""
+    def name(d):
+        for old, new in renames:
+            d = d.replace(old, new)
+        return d
+    return {"sections": r["sections"], "kernels": {name(d): k for d, k in r["kernels"].items()}}
+
+
+def compare(a, b, common=False):
+    """'' when identical, else what differs first.  common: only the kernels both sides have, and not the sections."""
+    if not common and sorted(a["kernels"]) != sorted(b["kernels"]):
         only = sorted(set(a["kernels"]) ^ set(b["kernels"]))
-        return "kernel symbol sets differ: " + ", ".join(only[:4])
-    for n in sorted(a["kernels"]):
+        return "kernel sets differ: " + ", ".join(only[:4])
+    both = sorted(set(a["kernels"]) & set(b["kernels"]))
+    if not both:
+        return "no kernel in common"
+    for n in both:
         ka, kb = a["kernels"][n], b["kernels"][n]
         if ka["meta"] != kb["meta"]:
-            return f"metadata of {ka['demangled']} differs: {ka['meta']} / {kb['meta']}"
+            return f"metadata of {n} differs: {ka['meta']} / {kb['meta']}"
         if ka["sha256"] != kb["sha256"] or ka["size"] != kb["size"]:
-            return f"code of {ka['demangled']} differs ({ka['size']} / {kb['size']} bytes)"
-    for sec in (".text", ".rodata"):
+            return f"code of {n} differs ({ka['size']} / {kb['size']} bytes)"
+    for sec in () if common else (".text", ".rodata"):
         if a["sections"][sec] != b["sections"][sec]:
             return f"{sec} differs outside the kernels' own code (device functions, tables)"
     return ""
@@ -143,6 +162,11 @@ def main():
     ap.add_argument("--a", help="side A: a source tree (instead of --parent)")
     ap.add_argument("--b", help="side B: a source tree (default: the tree this script is in)")
     ap.add_argument("--out", help="write the report here as well")
+    ap.add_argument("--units", nargs="+", default=UNITS, metavar="UNIT[:UNIT_B]",
+                    help="translation units under csrc/ (default: the solver's five); UNIT:UNIT_B compares side A's UNIT with side B's UNIT_B")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="replace OLD by NEW in side A's demangled kernel names before pairing (repeatable)")
+    ap.add_argument("--common", action="store_true", help="compare the kernels both sides have; list the others without failing")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("-v", "--verbose", action="store_true", help="list every kernel with its metadata")
     args = ap.parse_args()
@@ -165,16 +189,18 @@ def main():
                 B = load_build(tree)
                 work = os.path.join(tmp, tag)
                 os.makedirs(work)
-                sides.append({(u, l): pool.submit(inspect, tree, B, u, l, f, work) for u in UNITS for l, f in flag_sets(B, u)})
+                units = [u.split(":")[0 if tag == "a" else -1] for u in args.units]
+                sides.append({(pair, l): pool.submit(inspect, tree, B, u, l, f, work) for pair, u in zip(args.units, units) for l, f in flag_sets(B, u)})
             res = [{k: f.result() for k, f in s.items()} for s in sides]
+        renames = [r.split("=", 1) for r in args.rename]
         B = load_build(b_tree)
-        lines = ["solver kernels: device code of two source trees, gfx950",
+        lines = ["kernels: device code of two source trees, gfx950",
                  "compiler: " + run([B.hipcc(), "--version"]).splitlines()[1].strip(),
                  "A = " + a_name, "B = " + ("the tree of this report" if not args.b else b_tree), ""]
         bad = 0
         for key in res[0]:
-            a, b = res[0][key], res[1][key]
-            diff = compare(a, b)
+            a, b = renamed(res[0][key], renames), res[1][key]
+            diff = compare(a, b, args.common)
             bad += bool(diff)
             lines.append(f"{key[0]} [{key[1]} flags]: " + ("IDENTICAL" if not diff else "DIFFERENT -- " + diff))
             for sec in (".text", ".rodata"):
@@ -185,12 +211,15 @@ def main():
                 for side, r in (("A", a), ("B", b)):
                     for n in sorted(r["kernels"]):
                         k = r["kernels"][n]
-                        lines.append(f"    {side} {k['demangled']}\n        {n}  {k['size']} B  " +
+                        lines.append(f"    {side} {n}\n        {k['symbol']}  {k['size']} B  " +
                                      " ".join(f"{m[1:]}={k['meta'].get(m)}" for m in META))
-            elif a["kernels"]:
-                for n in sorted(a["kernels"]):
+            else:
+                for n in sorted(set(a["kernels"]) & set(b["kernels"])):
                     k = a["kernels"][n]
-                    lines.append(f"    {k['demangled']}: " + " ".join(f"{m[1:]}={k['meta'].get(m)}" for m in META))
+                    lines.append(f"    {n}: {k['size']} B " + " ".join(f"{m[1:]}={k['meta'].get(m)}" for m in META))
+                for side, r, other in (("A", a, b), ("B", b, a)):
+                    for n in sorted(set(r["kernels"]) - set(other["kernels"])):
+                        lines.append(f"    only in {side}: {n}")
         lines.append("")
         lines.append("RESULT: " + ("all units identical" if not bad else f"{bad} unit / flag set(s) differ"))
     text = "\n".join(lines) + "\n"
