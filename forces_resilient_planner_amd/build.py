@@ -7,13 +7,14 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfrp_nmpc_amd.so")
-SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip"]
+SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip", "frp_command.hip"]
 HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", "frp_occmap_raywalk.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_batch.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_points.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_check.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_render.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_render_scan.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_view.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_corridor_large.h")]
+           os.path.join(ROOT, "include", "frp_nmpc_corridor_large.h"),
+           os.path.join(ROOT, "include", "frp_nmpc_command.h")]
 
 
 def hipcc():
@@ -134,7 +135,10 @@ PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS,  # (what else a solver uni
                     # t + s_mid * d_w is a product and a sum
                     "frp_occmap_render_scan.hip": ["-ffp-contract=off"],
                     # the shared view's cloud is the local view's to the bit: the same voxel centres, one rounding per operation
-                    "frp_occmap_view.hip": ["-ffp-contract=off"]}
+                    "frp_occmap_view.hip": ["-ffp-contract=off"],
+                    # the command timer's index, fraction and interpolated row are the host's operations, one rounding each:
+                    # row[i] + w * (row[i + 1] - row[i]) is no FMA
+                    "frp_command.hip": ["-ffp-contract=off"]}
 OBJDIR = os.path.join(PKG, "_build")
 
 

@@ -157,6 +157,14 @@ class CorridorLarge(ctypes.Structure):  # frp_nmpc_corridor_large (include/frp_n
     _fields_ = [("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("overflow", ctypes.c_void_p)]
 
 
+class Command(ctypes.Structure):  # frp_nmpc_command (include/frp_nmpc_command.h)
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("S", ctypes.c_int), ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("g", ctypes.c_double),
+                ("pre_plan", ctypes.c_void_p), ("t_cur", ctypes.c_void_p), ("status", ctypes.c_void_p), ("have_traj", ctypes.c_void_p),
+                ("pub_end", ctypes.c_void_p), ("end_pt", ctypes.c_void_p), ("odom", ctypes.c_void_p), ("init_yaw", ctypes.c_void_p),
+                ("t_yaw", ctypes.c_void_p), ("cmd", ctypes.c_void_p), ("kind", ctypes.c_void_p), ("finish", ctypes.c_void_p),
+                ("reset_output", ctypes.c_void_p)]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -211,6 +219,14 @@ CORRIDOR_LARGE_GROUPS = 512          # FRP_CORRIDOR_LARGE_GROUPS
 CHECK_EXPORTS = ["frp_nmpc_occmap_check_surround", "frp_nmpc_occmap_check_paths", "frp_nmpc_occmap_check_goals"]
 OCCMAP_BODY = (0.27, 0.0425)  # occ_map/ego_r, ego_h of the reference's launch file
 SAFETY_INFLATE_CHECK, SAFETY_INFLATE_SEARCH = 1.2, 1.5  # checkReplanCallback's two ratios (nmpc_manage.cpp:291, :308, :333)
+
+
+# the command timer (include/frp_nmpc_command.h)
+COMMAND_EXPORTS = ["frp_nmpc_command_snapshot", "frp_nmpc_command_batch"]
+CMD_INIT_POSITION, CMD_ROTATE_YAW, CMD_PUB_END, CMD_PUB_TRAJ, CMD_WAIT = range(5)  # FRP_CMD_*: enum CMD_STATUS (nmpc_utils.h:115-122)
+COMMAND_NONE, COMMAND_TRAJ, COMMAND_END, COMMAND_YAW, COMMAND_NO_YAW_INPUT = 0, 1, 2, 3, -1  # FRP_COMMAND_*: kind[b][s]
+COMMAND_STRIDE = 16  # FRP_COMMAND_STRIDE: position 0-2, quaternion x y z w 3-6, linear velocity 7-9, body rates 10-12, linear acceleration 13-15
+COMMAND_DEFAULTS = dict(Ts=0.05, mass=0.74, g=9.81)  # nmpc_utils.h:189, nmpc/mass, the g of nmpc_solver.cpp
 
 
 def goal_search_table():
@@ -365,7 +381,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -399,6 +415,8 @@ def lib():
         l.frp_nmpc_occmap_check_surround.argtypes = [pm, pb, cd, ci, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_paths.argtypes = [pm, pb, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_goals.argtypes = [pm, pb, cd, cd, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, sz, vp]
+        l.frp_nmpc_command_snapshot.argtypes = [ci, ci, vp, vp, vp, vp, vp]
+        l.frp_nmpc_command_batch.argtypes = [ctypes.POINTER(Command), vp]
         _lib = l
     return _lib
 
@@ -657,6 +675,70 @@ def reference_batch_host(kino_path, time_offset, mpc_output, kino_size=None, Ts=
     reference_batch_device(dev(kino_path), dev(time_offset), dev(mpc_output), rp, ry, fl, ks, Ts)
     torch.cuda.synchronize(device)
     return rp.cpu().numpy(), ry.cpu().numpy(), fl.cpu().numpy()
+
+
+class Commands:
+    """What command_batch_device / DeviceFleet.commands return (device tensors): cmd [B,S,16] f64 (position 0-2, quaternion x y z w 3-6,
+    linear velocity 7-9, body rates 10-12, linear acceleration 13-15), kind [B,S] int32 (COMMAND_*), finish [B] int32 (finish_mpc_cmd_; written
+    only where a callback touched it), reset_output [B] int32 (1 where PUB_END ran: cold-start that planner; written nowhere else) and
+    status [B] int32, the caller's own tensor updated in place.  Pass the object back as `out` to reuse its buffers: finish and
+    reset_output then carry over from call to call, as the reference's members do."""
+
+    def __init__(self, cmd, kind, finish, reset_output, status):
+        self.cmd, self.kind, self.finish, self.reset_output, self.status = cmd, kind, finish, reset_output, status
+
+
+def command_snapshot_device(z, accept, pre_plan, have_traj, stream=None):
+    """frp_nmpc_command_snapshot on device tensors: where accept [B] int32 != 0, pre_plan [B,N,17] <- z [B,N,17] (pre_mpc_output_ =
+    mpc_output_, nmpc_solver.cpp:527, the solver's rows before the yaw wrap of :531-543) and have_traj [B] int32 <- 1."""
+    import torch
+    B, N, nz = z.shape
+    assert nz == L.NZ and tuple(pre_plan.shape) == (B, N, L.NZ) and tuple(accept.shape) == (B,) and tuple(have_traj.shape) == (B,)
+    assert z.dtype == pre_plan.dtype == torch.float64 and accept.dtype == have_traj.dtype == torch.int32
+    assert z.is_contiguous() and pre_plan.is_contiguous() and accept.is_contiguous() and have_traj.is_contiguous()
+    s = stream if stream is not None else torch.cuda.current_stream(z.device)
+    vp = ctypes.c_void_p
+    _check(lib().frp_nmpc_command_snapshot(B, N, vp(z.data_ptr()), vp(accept.data_ptr()), vp(pre_plan.data_ptr()), vp(have_traj.data_ptr()),
+                                           vp(s.cuda_stream)), "frp_nmpc_command_snapshot")
+
+
+def command_batch_device(pre_plan, have_traj, t_cur, status, pub_end, end_pt, odom=None, init_yaw=None, t_yaw=None, out=None, Ts=None,
+                         mass=None, g=None, stream=None):
+    """frp_nmpc_command_batch on device tensors: S consecutive callbacks of NMPCSolver::cmdTrajCallback (nmpc_solver.cpp:865-987) for
+    each of B planners in one launch.  pre_plan [B,N,17] f64 + have_traj [B] int32 (command_snapshot_device), t_cur [B,S] f64 seconds
+    since pre_mpc_start_time_, status [B] int32 CMD_* (updated IN PLACE), pub_end [B] int32, end_pt [B,3] f64; the yaw rotation's odom
+    [B,9] f64, init_yaw [B] f64 and t_yaw [B,S] f64 seconds since change_yaw_time_: all three or none -- with none a planner in
+    CMD_ROTATE_YAW gets kind COMMAND_NO_YAW_INPUT and zeros.  Ts, mass, g: COMMAND_DEFAULTS.  Returns a Commands object (out, when
+    given: nothing is allocated then, so the call can be captured)."""
+    import torch
+    B, N, nz = pre_plan.shape
+    assert nz == L.NZ and t_cur.dim() == 2 and t_cur.shape[0] == B
+    S = t_cur.shape[1]
+    yaw_in = (odom, init_yaw, t_yaw)
+    if any(a is None for a in yaw_in) and not all(a is None for a in yaw_in):
+        raise ValueError("odom, init_yaw and t_yaw go together: all three or none (frp_nmpc_command.odom)")
+    f64 = [(pre_plan, (B, N, L.NZ)), (t_cur, (B, S)), (end_pt, (B, 3))] + ([(odom, (B, 9)), (init_yaw, (B,)), (t_yaw, (B, S))] if odom is not None else [])
+    i32 = [(status, (B,)), (have_traj, (B,)), (pub_end, (B,))]
+    dev = pre_plan.device
+    if out is None:
+        out = Commands(torch.zeros((B, S, COMMAND_STRIDE), dtype=torch.float64, device=dev), torch.zeros((B, S), dtype=torch.int32, device=dev),
+                       torch.zeros((B,), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev), status)
+    out.status = status
+    f64.append((out.cmd, (B, S, COMMAND_STRIDE)))
+    i32 += [(out.kind, (B, S)), (out.finish, (B,)), (out.reset_output, (B,))]
+    for t, shape in f64:
+        assert t.dtype == torch.float64 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (tuple(t.shape), shape, t.dtype)
+    for t, shape in i32:
+        assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (tuple(t.shape), shape, t.dtype)
+    k = dict(COMMAND_DEFAULTS)
+    k.update({n: float(v) for n, v in (("Ts", Ts), ("mass", mass), ("g", g)) if v is not None})
+    ptr = lambda a: a.data_ptr() if a is not None else None
+    c = Command(B, N, S, k["Ts"], k["mass"], k["g"], pre_plan.data_ptr(), t_cur.data_ptr(), status.data_ptr(), have_traj.data_ptr(),
+                pub_end.data_ptr(), end_pt.data_ptr(), ptr(odom), ptr(init_yaw), ptr(t_yaw), out.cmd.data_ptr(), out.kind.data_ptr(),
+                out.finish.data_ptr(), out.reset_output.data_ptr())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    _check(lib().frp_nmpc_command_batch(ctypes.byref(c), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_command_batch")
+    return out
 
 
 class LocalView:
@@ -1698,3 +1780,33 @@ class DeviceFleet:
         self.pack(external_acc, ref_pos, ref_yaw, stream)
         self.solver.solve(stream)
         self.update(stream)
+
+    def snapshot_commands(self, accept=None, stream=None):
+        """pre_mpc_output_ = mpc_output_; have_mpc_traj_ = true (nmpc_solver.cpp:527-528) for the planners whose last solve is accepted:
+        self.pre_plan [B,N,17] <- solver.z, self.have_traj [B] <- 1 there; every other planner keeps both.  Both tensors belong to the
+        fleet and are allocated (zeros: no trajectory yet) on first use -- call once outside a graph capture.
+        pre_plan is NOT mpc_output: the reference copies before it wraps the yaw and duplicates the last row (:527 against :531-543).
+        accept [B] int32, non-zero = accepted.  None: solver.exitflag == 1, which is only the FIRST branch of the reference's rule
+        (:398-421): it also accepts a MAXIT result after repeated failures (replan_count_ > 3 && exit_code == 0), a policy that stays
+        with the caller -- who passes its own mask."""
+        t = self.torch
+        ds = self.solver
+        s = stream if stream is not None else t.cuda.current_stream(ds.device)
+        if getattr(self, "pre_plan", None) is None:
+            self.pre_plan = t.zeros((self.B, self.N, L.NZ), dtype=t.float64, device=ds.device)
+            self.have_traj = t.zeros((self.B,), dtype=t.int32, device=ds.device)
+            self._accept = t.zeros((self.B,), dtype=t.int32, device=ds.device)       # the default mask, and
+            self._accept_bool = t.zeros((self.B,), dtype=t.bool, device=ds.device)   # the comparison it is converted from
+        if accept is None:
+            with t.cuda.stream(s):
+                t.eq(ds.exitflag, 1, out=self._accept_bool)
+                self._accept.copy_(self._accept_bool)
+            accept = self._accept
+        command_snapshot_device(ds.z, accept, self.pre_plan, self.have_traj, s)
+
+    def commands(self, t_cur, status, pub_end, end_pt, odom=None, init_yaw=None, t_yaw=None, out=None, stream=None, Ts=None, mass=None, g=None):
+        """The 100 Hz command timer (NMPCSolver::cmdTrajCallback, nmpc_solver.cpp:865-987) for all B planners: S = t_cur.shape[1]
+        consecutive callbacks sampled from the snapshot of snapshot_commands(), in one launch -- command_batch_device has the arguments.
+        t_cur counts from pre_mpc_start_time_, which the reference resets at EVERY solveNMPC call (:359), rejected ones included."""
+        assert getattr(self, "pre_plan", None) is not None, "call snapshot_commands() first: it owns pre_plan / have_traj"
+        return command_batch_device(self.pre_plan, self.have_traj, t_cur, status, pub_end, end_pt, odom, init_yaw, t_yaw, out, Ts, mass, g, stream)

@@ -590,6 +590,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * points, beside the entries above, which keep their limit.  A header of its own, part of this section and of this ABI version. */
 #include "frp_nmpc_corridor_large.h"
 
+/* ---- (9) the command timer: every planner's 100 Hz setpoints from its last accepted plan ---- */
+/* NMPCSolver::cmdTrajCallback (plan_manage/src/nmpc_solver.cpp:865-987) for S consecutive callbacks of B planners in one launch, and
+ * the snapshot pre_mpc_output_ = mpc_output_ (:527-528) it samples.  A header of its own, part of this ABI version. */
+#include "frp_nmpc_command.h"
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 
