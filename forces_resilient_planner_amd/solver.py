@@ -165,6 +165,18 @@ class Command(ctypes.Structure):  # frp_nmpc_command (include/frp_nmpc_command.h
                 ("reset_output", ctypes.c_void_p)]
 
 
+class Tick(ctypes.Structure):  # frp_nmpc_tick (include/frp_nmpc_outcome.h)
+    _fields_ = [("B", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in ("fail_count", "replan_count", "kino_replan", "exit_code", "initialized", "cmd_status",
+                                                                        "pub_end", "cmd_end_pt", "exec_mpc", "gate", "keep", "accept", "result", "replan")]
+
+
+class TickIn(ctypes.Structure):  # frp_nmpc_tick_in (include/frp_nmpc_outcome.h)
+    _fields_ = [("N", ctypes.c_int), ("K", ctypes.c_int), ("Ts", ctypes.c_double), ("z", ctypes.c_void_p), ("exitflag", ctypes.c_void_p),
+                ("mpc_output", ctypes.c_void_p), ("state", ctypes.c_void_p), ("end_pt", ctypes.c_void_p), ("end_per_planner", ctypes.c_int),
+                ("kino_path", ctypes.c_void_p), ("path_per_planner", ctypes.c_int), ("kino_size", ctypes.c_void_p), ("size_per_planner", ctypes.c_int),
+                ("time_offset", ctypes.c_void_p), ("ref_replan", ctypes.c_void_p), ("mode", ctypes.c_void_p)]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -227,6 +239,11 @@ CMD_INIT_POSITION, CMD_ROTATE_YAW, CMD_PUB_END, CMD_PUB_TRAJ, CMD_WAIT = range(5
 COMMAND_NONE, COMMAND_TRAJ, COMMAND_END, COMMAND_YAW, COMMAND_NO_YAW_INPUT = 0, 1, 2, 3, -1  # FRP_COMMAND_*: kind[b][s]
 COMMAND_STRIDE = 16  # FRP_COMMAND_STRIDE: position 0-2, quaternion x y z w 3-6, linear velocity 7-9, body rates 10-12, linear acceleration 13-15
 COMMAND_DEFAULTS = dict(Ts=0.05, mass=0.74, g=9.81)  # nmpc_utils.h:189, nmpc/mass, the g of nmpc_solver.cpp
+
+# the tick outcome (include/frp_nmpc_outcome.h)
+OUTCOME_EXPORTS = ["frp_nmpc_tick_begin", "frp_nmpc_tick_end"]
+TICK_RUN, TICK_IDLE, TICK_AT_END, TICK_ENDING = range(4)  # FRP_TICK_*: gate[b]
+TICK_RESULT_IDLE = -4  # FRP_TICK_RESULT_IDLE: result[b] of a planner whose mpcCallback returned before solveNMPC
 
 
 def goal_search_table():
@@ -381,7 +398,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -417,6 +434,8 @@ def lib():
         l.frp_nmpc_occmap_check_goals.argtypes = [pm, pb, cd, cd, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_command_snapshot.argtypes = [ci, ci, vp, vp, vp, vp, vp]
         l.frp_nmpc_command_batch.argtypes = [ctypes.POINTER(Command), vp]
+        l.frp_nmpc_tick_begin.argtypes = [ctypes.POINTER(Tick), vp, vp]
+        l.frp_nmpc_tick_end.argtypes = [ctypes.POINTER(Tick), ctypes.POINTER(TickIn), vp]
         _lib = l
     return _lib
 
@@ -739,6 +758,78 @@ def command_batch_device(pre_plan, have_traj, t_cur, status, pub_end, end_pt, od
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     _check(lib().frp_nmpc_command_batch(ctypes.byref(c), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_command_batch")
     return out
+
+
+class TickState:
+    """The per-planner state the tick outcome keeps on the device (frp_nmpc_tick, include/frp_nmpc_outcome.h), all [B] int32 unless noted:
+    fail_count, replan_count, kino_replan, exit_code (the last solve that RAN for the planner, not solver.exitflag), initialized, cmd_status
+    (CMD_*: the tensor DeviceFleet.commands walks), pub_end, cmd_end_pt [B,3] f64, exec_mpc; the outputs gate (TICK_*), keep, accept, result,
+    replan of tick_begin / tick_end; and ref_replan, which receives the references' replan flag inside DeviceFleet.full_tick.
+    As the reference's constructor leaves them: counters 0, exit_code 0, initialized 0, cmd_status INIT_POSITION, pub_end 0; exec_mpc 1.
+    Constructing it also makes fleet.pre_plan / fleet.have_traj exist (DeviceFleet.snapshot_commands allocates them on first use otherwise),
+    so that a capture of full_tick(tick=...) allocates nothing.
+    The loop without a host: DeviceFleet.full_tick(..., tick=ts) -> DeviceFleet.commands(t_cur, ts.cmd_status, ts.pub_end, ts.cmd_end_pt, ...)
+    with ts.reset_output = the returned Commands.reset_output -> DeviceFleet.replan(..., replan=ts.replan, tick=ts)."""
+
+    INT_FIELDS = ("fail_count", "replan_count", "kino_replan", "exit_code", "initialized", "cmd_status", "pub_end", "exec_mpc",
+                  "gate", "keep", "accept", "result", "replan", "ref_replan")
+
+    def __init__(self, fleet):
+        t = fleet.torch
+        dev = fleet.solver.device
+        self.B = fleet.B
+        for n in self.INT_FIELDS:
+            setattr(self, n, t.zeros((self.B,), dtype=t.int32, device=dev))
+        self.cmd_status.fill_(CMD_INIT_POSITION)
+        self.exec_mpc.fill_(1)
+        self.cmd_end_pt = t.zeros((self.B, 3), dtype=t.float64, device=dev)
+        self._sizes = {}
+        self.reset_output = None  # set it to Commands.reset_output of DeviceFleet.commands: every DeviceFleet.full_tick(tick=self) consumes and clears it
+        fleet._command_buffers()
+
+    def struct(self):
+        p = lambda n: getattr(self, n).data_ptr()
+        return Tick(self.B, *[p(n) for n, _ in Tick._fields_[1:]])
+
+    def path_size(self, K):
+        """kino_size [1] = K for a caller that passes whole paths (allocated on first use per K: call once outside a graph capture)."""
+        if K not in self._sizes:
+            self._sizes[K] = self.gate.new_full((1,), K)
+        return self._sizes[K]
+
+    def begin(self, reset_output=None, stream=None):
+        """frp_nmpc_tick_begin: gate and keep of this tick; reset_output [B] int32 (Commands.reset_output) is consumed and cleared."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream(self.gate.device)
+        if reset_output is not None:
+            assert reset_output.dtype == torch.int32 and tuple(reset_output.shape) == (self.B,) and reset_output.is_contiguous()
+        t = self.struct()
+        _check(lib().frp_nmpc_tick_begin(ctypes.byref(t), ctypes.c_void_p(reset_output.data_ptr()) if reset_output is not None else None,
+                                         ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_tick_begin")
+
+    def end(self, z, exitflag, mpc_output, state, end_pt, kino_path, kino_size, time_offset, ref_replan=None, Ts=0.05, mode=None, stream=None):
+        """frp_nmpc_tick_end on device tensors: z [B,N,17], exitflag [B] int32, mpc_output [B,N+1,17] (before the update), state [B,9],
+        end_pt [3] or [B,3], kino_path [K,3] or [B,K,3], kino_size int32 [1] or [B], time_offset [B], ref_replan [B] int32 (None: this
+        object's own), mode [B] int32 or None."""
+        import torch
+        B, N, nz = z.shape
+        K = kino_path.shape[-2]
+        ref_replan = self.ref_replan if ref_replan is None else ref_replan
+        per_end, per_path, per_size = end_pt.dim() == 2, kino_path.dim() == 3, kino_size.numel() > 1
+        f64 = [(z, (B, N, L.NZ)), (mpc_output, (B, N + 1, L.NZ)), (state, (B, 9)), (end_pt, (B, 3) if per_end else (3,)),
+               (kino_path, (B, K, 3) if per_path else (K, 3)), (time_offset, (B,))]
+        i32 = [(exitflag, (B,)), (kino_size, (B,) if per_size else (1,)), (ref_replan, (B,))] + ([(mode, (B,))] if mode is not None else [])
+        assert B == self.B
+        for a, shape in f64:
+            assert a.dtype == torch.float64 and tuple(a.shape) == shape and a.is_contiguous(), (tuple(a.shape), shape, a.dtype)
+        for a, shape in i32:
+            assert a.dtype == torch.int32 and tuple(a.shape) == shape and a.is_contiguous(), (tuple(a.shape), shape, a.dtype)
+        s = stream if stream is not None else torch.cuda.current_stream(z.device)
+        t = self.struct()
+        i = TickIn(N, K, float(Ts), z.data_ptr(), exitflag.data_ptr(), mpc_output.data_ptr(), state.data_ptr(), end_pt.data_ptr(), int(per_end),
+                   kino_path.data_ptr(), int(per_path), kino_size.data_ptr(), int(per_size), time_offset.data_ptr(), ref_replan.data_ptr(),
+                   mode.data_ptr() if mode is not None else None)
+        _check(lib().frp_nmpc_tick_end(ctypes.byref(t), ctypes.byref(i), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_tick_end")
 
 
 class LocalView:
@@ -1651,11 +1742,14 @@ class DeviceFleet:
         _check(lib().frp_nmpc_pack_batch(ctypes.byref(pk), ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_pack_batch")
         ds._packed_by = self
 
-    def update(self, stream=None, keep_failed=True):
+    def update(self, stream=None, keep_failed=True, accept=None):
+        """accept [B] int32: the planners whose result is taken over are those with accept == 1 (TickState.accept, the reference's whole
+        rule) instead of those with solver.exitflag == 1 (its first branch)."""
         s = stream if stream is not None else self.torch.cuda.current_stream(self.solver.device)
         ds = self.solver
+        flags = accept if accept is not None else ds.exitflag
         _check(lib().frp_nmpc_update_batch(self.B, self.N, ctypes.c_void_p(ds.z.data_ptr()),
-                                           ctypes.c_void_p(ds.exitflag.data_ptr()) if keep_failed else None,
+                                           ctypes.c_void_p(flags.data_ptr()) if keep_failed else None,
                                            ctypes.c_void_p(self.mpc_output.data_ptr()), ctypes.c_void_p(s.cuda_stream)),
                "frp_nmpc_update_batch")
 
@@ -1682,12 +1776,15 @@ class DeviceFleet:
         corridor() call)."""
         return self.poly_count < 0
 
-    def coldstart(self, state=None, only_failed=True, thrust=7.3, stream=None):
+    def coldstart(self, state=None, only_failed=True, thrust=7.3, stream=None, keep=None):
         """initMPCOutput for the planners whose last solve failed (nmpc_solver.cpp:363-364, :265-286), on the device.
-        state [B,9] = stateMpc_ (odometry), or None: each planner restarts from its plan's stage-1 state."""
+        state [B,9] = stateMpc_ (odometry), or None: each planner restarts from its plan's stage-1 state.
+        keep [B] int32: the planners with keep == 1 keep their plan (TickState.keep: :363's whole condition, and never a gated planner)
+        instead of those with solver.exitflag == 1."""
         s = stream if stream is not None else self.torch.cuda.current_stream(self.solver.device)
+        flags = keep if keep is not None else self.solver.exitflag
         _check(lib().frp_nmpc_coldstart_batch(self.B, self.N, ctypes.c_void_p(state.data_ptr()) if state is not None else None,
-                                              ctypes.c_void_p(self.solver.exitflag.data_ptr()) if only_failed else None,
+                                              ctypes.c_void_p(flags.data_ptr()) if only_failed else None,
                                               float(thrust), ctypes.c_void_p(self.mpc_output.data_ptr()),
                                               ctypes.c_void_p(s.cuda_stream)), "frp_nmpc_coldstart_batch")
 
@@ -1697,7 +1794,7 @@ class DeviceFleet:
         reference_batch_device(kino_path, time_offset, self.mpc_output, ref_pos, ref_yaw, replan, kino_size, Ts, stream)
 
     def replan(self, planner, end_pt, external_acc, replan, time_offset=None, end_vel=None, init=True, mass=0.74, g=9.81, stream=None,
-               t_cur=None, odom=None, Ts=0.05, local_box=None):
+               t_cur=None, odom=None, Ts=0.05, local_box=None, tick=None):
         """The FSM's REPLAN_TRAJ step (nmpc_manage.cpp:215-235 -> NMPCSolver::getKinoPath, nmpc_solver.cpp:145-223) for the planners
         whose tick raised kino_replan_ (`replan` [B] int32, as written by references() / full_tick): a kinodynamic A* to end_pt
         [B,3] with external_acc [B,3] in the primitives, on the device (AstarPlanner = frp_nmpc_astar_batch).
@@ -1711,6 +1808,9 @@ class DeviceFleet:
         path.  Planners that found a path get time_offset = 0 (kino_start_time_ = now, :219) and go back to the normal solver (:218).
         local_box: int32 [B,6] of OccupancyMap.local_view for a planner built on that map (voxels outside a planner's box read as free,
         occ_map.cpp:101-102); None: the whole map is local.
+        tick: a TickState.  "The last solve succeeded" is then tick.exit_code == 1 -- the last solve that ran for the planner, as in the
+        reference, where solver.exitflag also holds the discarded solves of gated planners -- and the planners that got a path also get
+        cmd_status <- PUB_TRAJ and pub_end <- 0 (:222-223); tick.replan is the natural `replan` argument.
         Returns the mask (bool [B]) of planners that received a new path.  Everything here -- the state gather, the search, the
         masks -- is enqueued on `stream` (torch's current stream when None)."""
         t = self.torch
@@ -1720,7 +1820,7 @@ class DeviceFleet:
             rows = self.mpc_output[:, :N]                      # pre_mpc_output_: rows 0..N-1 of the deque
             tc = t_cur if t_cur is not None else t.zeros((B,), dtype=t.float64, device=rows.device)
             idx = t.floor(tc / Ts).to(t.int64)
-            use_plan = (self.solver.exitflag == 1) & (idx < N - 1) & (tc >= 0.0)
+            use_plan = ((tick.exit_code if tick is not None else self.solver.exitflag) == 1) & (idx < N - 1) & (tc >= 0.0)
             i0 = idx.clamp(0, N - 2)
             ar = t.arange(B, device=rows.device)
             r0, r1 = rows[ar, i0], rows[ar, i0 + 1]
@@ -1749,11 +1849,14 @@ class DeviceFleet:
                 time_offset.masked_fill_(ok, 0.0)
             if self.mode is not None:
                 self.mode.masked_fill_(ok, L.MODEL_NORMAL)
+            if tick is not None:
+                tick.cmd_status.masked_fill_(ok, CMD_PUB_TRAJ)
+                tick.pub_end.masked_fill_(ok, 0)
         return ok
 
     def full_tick(self, external_acc, kino_path, time_offset, cloud, ref_pos, ref_yaw, stream=None, replan=None,
                   kino_size=None, tube_consts=None, corridor_consts=None, Ts=0.05, coldstart=True, state=None, grid=None, cloud_count=None, cut=None,
-                  view=None):
+                  view=None, tick=None, end_pt=None):
         """The reference's whole per-tick computation downstream of the A* (NMPCSolver::solveNMPC,
         nmpc_solver.cpp:351-482) for B planners, asynchronous on `stream`, nothing touching the host:
         stage references (f-4) -> tube (f-2) -> corridor (f-3) -> parameter packing (f-1) -> NLP solve -> result
@@ -1762,7 +1865,16 @@ class DeviceFleet:
         cloud [B,P,3] with cloud_count [B]: per-planner clouds, as OccupancyMap.local_view exports them; or the shared cloud and grid
         of OccupancyMap.shared_view() with cut = OccupancyMap.cut(local_box): the same polytopes without the per-planner copies; or
         cloud = None and view = a SharedView (OccupancyMap.shared_view_device) updated on this stream, with the same cut: the same
-        again for a map that changes every tick."""
+        again for a map that changes every tick.
+        tick: a TickState -- the whole of solveNMPC with its decisions (include/frp_nmpc_outcome.h), state [B,9] and end_pt ([3] or [B,3])
+        required: tick_begin -> cold start of the planners tick.keep names -> references (their flag goes to tick.ref_replan; `replan`
+        is not used) -> tube -> corridor -> pack -> solve -> tick_end -> update of the planners tick.accept names ->
+        snapshot_commands(accept=tick.accept).  Planners that do not run this tick (tick.gate != TICK_RUN) stay in the batch: it remains
+        one launch of every stage, their solve is discarded and neither their plan nor their state changes.  With a fleet that carries
+        modes, tick_end applies the switch rule (update_mode is not needed).  tick.reset_output, when set, is consumed by tick_begin."""
+        if tick is not None:
+            return self._full_tick_outcome(tick, external_acc, kino_path, time_offset, cloud, ref_pos, ref_yaw, stream, kino_size, tube_consts,
+                                           corridor_consts, Ts, state, grid, cloud_count, cut, view, end_pt)
         if coldstart:
             self.coldstart(state, True, stream=stream)
         self.references(kino_path, time_offset, ref_pos, ref_yaw, replan, kino_size, Ts, stream)
@@ -1771,6 +1883,22 @@ class DeviceFleet:
         self.pack(external_acc, ref_pos, ref_yaw, stream)
         self.solver.solve(stream)
         self.update(stream)
+
+    def _full_tick_outcome(self, tick, external_acc, kino_path, time_offset, cloud, ref_pos, ref_yaw, stream, kino_size, tube_consts, corridor_consts,
+                           Ts, state, grid, cloud_count, cut, view, end_pt):
+        assert state is not None and end_pt is not None, "full_tick(tick=...) needs the odometry `state` and the goal `end_pt`"
+        tick.begin(tick.reset_output, stream)
+        self.coldstart(state, True, stream=stream, keep=tick.keep)
+        self.references(kino_path, time_offset, ref_pos, ref_yaw, tick.ref_replan, kino_size, Ts, stream)
+        self.tube(tube_consts, stream)
+        self.corridor(cloud, ref_pos, ref_yaw, corridor_consts, stream, cloud_count=cloud_count, grid=grid, cut=cut, view=view)
+        self.pack(external_acc, ref_pos, ref_yaw, stream)
+        self.solver.solve(stream)
+        ds = self.solver
+        tick.end(ds.z, ds.exitflag, self.mpc_output, state, end_pt, kino_path, kino_size if kino_size is not None else tick.path_size(kino_path.shape[-2]),
+                 time_offset, Ts=Ts, mode=self.mode, stream=stream)
+        self.update(stream, accept=tick.accept)
+        self.snapshot_commands(accept=tick.accept, stream=stream)
 
     def tick(self, external_acc, ref_pos, ref_yaw, stream=None, tube_consts=None, propagate_tube=False):
         """One receding-horizon tick of all B planners, asynchronous on `stream`.  With propagate_tube the
@@ -1781,22 +1909,27 @@ class DeviceFleet:
         self.solver.solve(stream)
         self.update(stream)
 
+    def _command_buffers(self):
+        t = self.torch
+        ds = self.solver
+        if getattr(self, "pre_plan", None) is None:
+            self.pre_plan = t.zeros((self.B, self.N, L.NZ), dtype=t.float64, device=ds.device)
+            self.have_traj = t.zeros((self.B,), dtype=t.int32, device=ds.device)
+            self._accept = t.zeros((self.B,), dtype=t.int32, device=ds.device)       # the default mask, and
+            self._accept_bool = t.zeros((self.B,), dtype=t.bool, device=ds.device)   # the comparison it is converted from
+
     def snapshot_commands(self, accept=None, stream=None):
         """pre_mpc_output_ = mpc_output_; have_mpc_traj_ = true (nmpc_solver.cpp:527-528) for the planners whose last solve is accepted:
         self.pre_plan [B,N,17] <- solver.z, self.have_traj [B] <- 1 there; every other planner keeps both.  Both tensors belong to the
         fleet and are allocated (zeros: no trajectory yet) on first use -- call once outside a graph capture.
         pre_plan is NOT mpc_output: the reference copies before it wraps the yaw and duplicates the last row (:527 against :531-543).
         accept [B] int32, non-zero = accepted.  None: solver.exitflag == 1, which is only the FIRST branch of the reference's rule
-        (:398-421): it also accepts a MAXIT result after repeated failures (replan_count_ > 3 && exit_code == 0), a policy that stays
-        with the caller -- who passes its own mask."""
+        (:398-421): it also accepts a MAXIT result after repeated failures (replan_count_ > 3 && exit_code == 0).  TickState.accept is
+        the whole rule, computed on the device (full_tick(tick=...) passes it); any other policy is the caller's own mask."""
         t = self.torch
         ds = self.solver
         s = stream if stream is not None else t.cuda.current_stream(ds.device)
-        if getattr(self, "pre_plan", None) is None:
-            self.pre_plan = t.zeros((self.B, self.N, L.NZ), dtype=t.float64, device=ds.device)
-            self.have_traj = t.zeros((self.B,), dtype=t.int32, device=ds.device)
-            self._accept = t.zeros((self.B,), dtype=t.int32, device=ds.device)       # the default mask, and
-            self._accept_bool = t.zeros((self.B,), dtype=t.bool, device=ds.device)   # the comparison it is converted from
+        self._command_buffers()
         if accept is None:
             with t.cuda.stream(s):
                 t.eq(ds.exitflag, 1, out=self._accept_bool)

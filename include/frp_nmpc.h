@@ -595,6 +595,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * the snapshot pre_mpc_output_ = mpc_output_ (:527-528) it samples.  A header of its own, part of this ABI version. */
 #include "frp_nmpc_command.h"
 
+/* ---- (10) the tick outcome: who runs, whether a solve is accepted, what solveNMPC returns ---- */
+/* mpcCallback's guard and the decision in the middle of NMPCSolver::solveNMPC (plan_manage/src/nmpc_solver.cpp:355-364, :397-421,
+ * :435-481) for B planners, one launch before the cold start and one after the solve.  A header of its own, part of this ABI version. */
+#include "frp_nmpc_outcome.h"
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 

@@ -9,8 +9,9 @@
  *     init_yaw_dot_                                             callInitYaw, :237-257              frp_nmpc_command_batch
  *     eulerToRot                                                :554-564                           frp_nmpc_command_batch
  *     CMD_STATUS                                                plan_manage/nmpc_utils.h:115-122   FRP_CMD_*
- * What is NOT here: whether a solve is accepted (fail_count_ / replan_count_, :398-421) -- the caller hands over the mask; the FSM
- * that calls callInitYaw and raises pub_end_; the clock -- t_cur and t_yaw are the caller's; ROS messages.  mav_msgs is not part of
+ * What is NOT here: whether a solve is accepted (fail_count_ / replan_count_, :398-421) -- the caller hands over the mask, and
+ * frp_nmpc_tick_end (frp_nmpc_outcome.h) computes the reference's on the device, together with pub_end_ and cmd_end_pt_; the FSM
+ * that calls callInitYaw; the clock -- t_cur and t_yaw are the caller's; ROS messages.  mav_msgs is not part of
  * the reference tree, so msgMultiDofJointTrajectoryFromPositionYaw (:889) is not restated: a ROTATE_YAW sample carries the position,
  * the yaw and the quaternion of a rotation about z by it, and the caller fills its message from them.
  * tests/command_oracle.py is the executable statement.
