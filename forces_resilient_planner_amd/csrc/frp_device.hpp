@@ -174,6 +174,69 @@ __device__ __forceinline__ bool ldl4(const double *a, double *m6, double *dinv)
     return (d0 > 0.0) && (d1 > 0.0) && (d2 > 0.0) && (d3 > 0.0);
 }
 
+// The 16-lane rows named in ROWS (bit g = lanes 16 g .. 16 g + 15) take the wave-uniform u, the other rows keep v: ONE 64-bit DPP move
+// with a row mask (row_newbcast:0 -- every lane reads lane 0 of its own row, which holds the same u) where a select on a lane predicate
+// is two v_cndmask_b32 and a mask in scalar registers.  Bits are copied, never computed: NaN and Inf pass like any other value.
+template <int ROWS>
+__device__ __forceinline__ double rows_take(double v, double u)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_update_dpp(v, u, 0x150 /*row_newbcast:0*/, ROWS, 0xF, false);
+#else
+    return v;
+#endif
+}
+
+// ldl4 for the tiles' pivot hand-over: the same operations in the same order on the same (uniform) inputs, but what only the lanes of ONE
+// row group g = lane >> 4 ever read is made for that row alone.  The pivots d_0..d_3 are spread over the rows first (three row-masked moves),
+// and ONE reciprocal and ONE sign test run on the spread value: dg = fast_rcp(d_g) is bit for bit the dinv[g] the selects of the uniform
+// form handed to row g, at 4 + 3 + 1 instructions instead of 4 + 6 + 4 (reciprocal of d_3, select ladder, four compares).
+// The return value is LANE-VARYING: true where the pivot of the lane's own row is positive; the caller and-s it over the stages and reduces
+// it over the wave once (wave_all).
+__device__ __forceinline__ bool ldl4_rows(const double *a, double *m6, double &dg)
+{
+    const double a00 = a[0], a11 = a[5], a21 = a[9], a22 = a[10];
+    const double a31 = a[13], a32 = a[14], a33 = a[15];
+    // (one copy to vector registers each: see spd4_inverse -- here as ONE 64-bit move per value, where the compiler, left to copy a
+    // scalar pair, writes two 32-bit ones)
+    double a10 = a[4], a20 = a[8], a30 = a[12];
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_mov_b64 %0, %1" : "=v"(a10) : "s"(a[4]));
+    asm("v_mov_b64 %0, %1" : "=v"(a20) : "s"(a[8]));
+    asm("v_mov_b64 %0, %1" : "=v"(a30) : "s"(a[12]));
+#endif
+    const double d0 = a00;
+    const double i0 = fast_rcp(d0);
+    const double l10 = a10 * i0, l20 = a20 * i0, l30 = a30 * i0;
+    const double d1 = a11 - l10 * a10;
+    const double i1 = fast_rcp(d1);
+    const double t21 = a21 - l20 * a10, t31 = a31 - l30 * a10;
+    const double l21 = t21 * i1, l31 = t31 * i1;
+    const double d2 = a22 - l20 * a20 - l21 * t21;
+    const double i2 = fast_rcp(d2);
+    const double t32 = a32 - l30 * a20 - l31 * t21;
+    const double l32 = t32 * i2;
+    const double d3 = a33 - l30 * a30 - l31 * t31 - l32 * t32;
+    double ds = d3;
+    ds = rows_take<4>(ds, d2); ds = rows_take<2>(ds, d1); ds = rows_take<1>(ds, d0);
+    dg = fast_rcp(ds);
+    const double m10 = -l10, m21 = -l21, m32 = -l32;
+    const double m20 = -l20 - l21 * m10;
+    const double m31 = -l31 - l32 * m21;
+    const double m30 = -l30 - l31 * m10 - l32 * m20;
+    m6[0] = m10; m6[1] = m20; m6[2] = m21; m6[3] = m30; m6[4] = m31; m6[5] = m32;
+    return ds > 0.0;
+}
+// true in every lane when p holds in every lane of the wavefront
+__device__ __forceinline__ bool wave_all(bool p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true);
+#else
+    return p;
+#endif
+}
+
 // Explicit global address space: inside non-inlined device functions a plain double* is a GENERIC
 // pointer and compiles to flat_load/flat_store, which also count on lgkmcnt and therefore make every
 // LDS wait drain the in-flight prefetches.

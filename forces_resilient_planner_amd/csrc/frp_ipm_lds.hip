@@ -505,6 +505,17 @@ __device__ __forceinline__ void gst(const double *base, unsigned boff, double v)
 #define FRP_GP_PARAM
 #define FRP_GP_ARG(x)
 #endif
+// The hand-over of the 4 x 4 pivot to the lanes in the factorisation sweep: D^-1 and the pivot test per 16-lane row (ldl4_rows) instead of
+// uniform values spread by selects -- on the layouts with P in global memory (the headline's four-per-CU kernel and the Q30 one).  On
+// the plain layout the sweep keeps the uniform form: with the row form two of its instantiations ((20, 2) untwisted and the re-reading
+// (20, 10)) gain spilled registers (profiles/pivot_handover_after.txt).  The arrival sweep of the twisted solve, a function of its own, has
+// the row form except in the re-reading unit, whose twisted (20, 10) instantiation would gain ten.
+constexpr bool PIVOT_ROWS = QP;
+#if defined(FRP_LDS_MEM_TU)
+constexpr bool ARRIVE_ROWS = false;
+#else
+constexpr bool ARRIVE_ROWS = true;
+#endif
 #ifdef FRP_INLINE_FACTOR
 #define FRP_FACTOR_LINKAGE __forceinline__
 #else
@@ -610,12 +621,22 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
             pqn = p_pq[OG];
         }
         // ---- pivot block Guu = L D L' (4 x 4): lower triangle to uniform registers, factored redundantly
-        double q[16], Mi[6], Di[4];
+        double q[16], Mi[6];
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
             for (int j = 0; j <= i; j++) q[i * 4 + j] = lane_bcast(G[0], 16 * i + j);
-        ok &= ldl4(q, Mi, Di); // (a failed pivot poisons the rest of the sweep, which is discarded: no branch in the loop)
+        double dg; // D^-1[g]
+        if constexpr (PIVOT_ROWS) {
+            // (a failed pivot poisons the rest of the sweep, which is discarded: no branch in the loop; ok is per lane here -- the pivot of
+            // the lane's row -- and reduced over the wave once, behind the last stage)
+            ok &= ldl4_rows(q, Mi, dg);
+        } else {
+            double Di[4];
+            ok &= ldl4(q, Mi, Di);
+            dg = Di[3]; // (a chain, not a nested conditional: the nested form compiles to EXEC-masked regions)
+            dg = g == 2 ? Di[2] : dg; dg = g == 1 ? Di[1] : dg; dg = g == 0 ? Di[0] : dg;
+        }
         // the uniform factors reach the lanes through selects on lane-constant predicates (an LDS round trip costs ~250 cycles
         // of the dependency chain)
         double me = msel == 6 ? 1.0 : Mi[0];
@@ -623,14 +644,12 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
         for (int i = 1; i < 6; i++) me = msel == i ? Mi[i] : me;
         // elimination in factored form: an explicit inverse of Guu cancels O(1e10) barrier terms against cond(Guu) eps errors
         const double m_gc = m_lower ? me : 0.0, m_cg = m_upper ? me : 0.0; // m[g][c & 3], m[c & 3][g]
-        double dg = Di[3]; // (a chain, not a nested conditional: the nested form compiles to EXEC-masked regions)
-        dg = g == 2 ? Di[2] : dg; dg = g == 1 ? Di[1] : dg; dg = g == 0 ? Di[0] : dg;
-        const double md = dg * m_gc;
         const double K0 = mfma4(m_cg, G[0], 0.0);  // K = m G_u          (4 x 16, register-0 layout)
-        const double Kd = dg * K0;
         // [R | Kbar_x | kbar] = m' D^-1 [m | K_x | k] in one 4x4x4 product: column block 0 of the B operand carries D^-1 m
-        // instead of D^-1 K_u (which is not needed: K_u = D L')
-        const double tsel = mfma4(m_gc, c < 4 ? md : Kd, 0.0); // T' of the sweeps; its columns 14, 15 are zero
+        // instead of D^-1 K_u (which is not needed: K_u = D L').  The same register is the A operand of S below: its u columns
+        // there make the tile rows 0..3 of S, which nothing reads (P[0] is the closed form) -- one scaling serves both.
+        const double Kd = dg * (c < 4 ? m_gc : K0);
+        const double tsel = mfma4(m_gc, Kd, 0.0); // T' of the sweeps; its columns 14, 15 are zero
         // (the u columns of rows 4.. would come out as G_xu - K_x' D^-1 K_u, zero only up to rounding RELATIVE TO G_xu, which carries
         //  barrier terms: they are taken out of both operands instead -- three multiplies -- and the block is exactly -hc K_x' D^-1 m)
         const double hcm = hc * m4;
@@ -692,6 +711,7 @@ __device__ FRP_FACTOR_LINKAGE int sweep_factor(ldouble *recs, ldouble *xs, int N
     }
     stage(integral_constant<int, 0>{}, std::true_type{}); // stage 0
     SEG_FLUSH();
+    if constexpr (PIVOT_ROWS) ok = wave_all(ok);
     int fail = ok ? 0 : 1;
     if constexpr (twist) {
 #pragma unroll
@@ -1065,22 +1085,27 @@ __device__ __noinline__ int sweep_arrive(ldouble *recs, ldouble *xs, ldouble *tw
         d4 Z;
         Z[0] = Qn[0] + pq;
         Z[1] = __builtin_fma(m4c, C[1], Qn[1]); Z[2] = __builtin_fma(m4c, C[2], Qn[2]); Z[3] = __builtin_fma(m4c, C[3], Qn[3]);
-        double q[16], Mi[6], Di[4];
+        double q[16], Mi[6];
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
             for (int j = 0; j <= i; j++) q[i * 4 + j] = lane_bcast(Z[0], 16 * i + j);
-        ok &= ldl4(q, Mi, Di);
+        double dg; // (the hand-over of the backward stage: see sweep_factor; row form: ok is per lane, reduced behind the loop)
+        if constexpr (ARRIVE_ROWS) {
+            ok &= ldl4_rows(q, Mi, dg);
+        } else {
+            double Di[4];
+            ok &= ldl4(q, Mi, Di);
+            dg = Di[3];
+            dg = g == 2 ? Di[2] : dg; dg = g == 1 ? Di[1] : dg; dg = g == 0 ? Di[0] : dg;
+        }
         double me = msel == 6 ? 1.0 : Mi[0];
 #pragma unroll
         for (int i = 1; i < 6; i++) me = msel == i ? Mi[i] : me;
         const double m_gc = m_lower ? me : 0.0, m_cg = m_upper ? me : 0.0;
-        double dg = Di[3];
-        dg = g == 2 ? Di[2] : dg; dg = g == 1 ? Di[1] : dg; dg = g == 0 ? Di[0] : dg;
-        const double md = dg * m_gc;
         const double K0 = mfma4(m_cg, Z[0], 0.0);
-        const double Kd = dg * K0;
-        const double tsel = mfma4(m_gc, c < 4 ? md : Kd, 0.0);
+        const double Kd = dg * (c < 4 ? m_gc : K0);
+        const double tsel = mfma4(m_gc, Kd, 0.0);
         const double hcm = hc * m4;
         const double Kb = __builtin_fma(hcm, m_gc, K0 * m4c);
         d4 S = Z;
@@ -1110,6 +1135,7 @@ __device__ __noinline__ int sweep_arrive(ldouble *recs, ldouble *xs, ldouble *tw
 #pragma unroll
     for (int r = 0; r < 4; r++) tw[sqo[r]] = Qn[r];
     WSYNC();
+    if constexpr (ARRIVE_ROWS) ok = wave_all(ok);
     return ok ? 0 : 1;
 }
 
