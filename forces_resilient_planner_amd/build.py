@@ -7,7 +7,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfrp_nmpc_amd.so")
-SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip", "frp_command.hip", "frp_outcome.hip"]
+SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip", "frp_command.hip", "frp_outcome.hip", "frp_fsm.hip"]
 HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", "frp_occmap_raywalk.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_batch.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_points.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_check.h"),
@@ -15,7 +15,8 @@ HEADERS = ["frp_kernels.h", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp"
            os.path.join(ROOT, "include", "frp_nmpc_occmap_view.h"),
            os.path.join(ROOT, "include", "frp_nmpc_corridor_large.h"),
            os.path.join(ROOT, "include", "frp_nmpc_command.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_outcome.h")]
+           os.path.join(ROOT, "include", "frp_nmpc_outcome.h"),
+           os.path.join(ROOT, "include", "frp_nmpc_fsm.h")]
 
 
 def hipcc():
@@ -141,7 +142,10 @@ PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS,  # (what else a solver uni
                     # row[i] + w * (row[i + 1] - row[i]) is no FMA
                     "frp_command.hip": ["-ffp-contract=off"],
                     # the tick outcome decides by comparing three norms with constants: d0 * d0 + d1 * d1 is two products and a sum, no FMA
-                    "frp_outcome.hip": ["-ffp-contract=off"]}
+                    "frp_outcome.hip": ["-ffp-contract=off"],
+                    # the state machine's replan start is the command timer's interpolation, one rounding per operation, and its world
+                    # acceleration that file's quaternion products term by term
+                    "frp_fsm.hip": ["-ffp-contract=off"]}
 OBJDIR = os.path.join(PKG, "_build")
 
 

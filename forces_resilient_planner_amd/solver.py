@@ -177,6 +177,19 @@ class TickIn(ctypes.Structure):  # frp_nmpc_tick_in (include/frp_nmpc_outcome.h)
                 ("time_offset", ctypes.c_void_p), ("ref_replan", ctypes.c_void_p), ("mode", ctypes.c_void_p)]
 
 
+class Fsm(ctypes.Structure):  # frp_nmpc_fsm (include/frp_nmpc_fsm.h)
+    _fields_ = [("B", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in ("state", "have_odom", "have_target", "have_traj", "trigger", "call_init_yaw",
+                                                                        "consider_force", "replan_force_surpass", "surpass_count", "plan_fail_count",
+                                                                        "exec_mpc", "cmd_status", "pub_end", "end_pt", "external_acc", "last_external_acc",
+                                                                        "init_yaw", "yaw_odom", "change_yaw_time", "kino_start_time", "mode")]
+
+
+class FsmExecIn(ctypes.Structure):  # frp_nmpc_fsm_exec_in (include/frp_nmpc_fsm.h)
+    _fields_ = [("N", ctypes.c_int), ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("g", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("state", "pre_plan", "exit_code", "t_cur", "now", "search", "start_pt", "start_vel", "start_acc",
+                                               "retry_pt", "retry_vel")]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -244,6 +257,12 @@ COMMAND_DEFAULTS = dict(Ts=0.05, mass=0.74, g=9.81)  # nmpc_utils.h:189, nmpc/ma
 OUTCOME_EXPORTS = ["frp_nmpc_tick_begin", "frp_nmpc_tick_end"]
 TICK_RUN, TICK_IDLE, TICK_AT_END, TICK_ENDING = range(4)  # FRP_TICK_*: gate[b]
 TICK_RESULT_IDLE = -4  # FRP_TICK_RESULT_IDLE: result[b] of a planner whose mpcCallback returned before solveNMPC
+
+# the fleet state machine (include/frp_nmpc_fsm.h)
+FSM_EXPORTS = ["frp_nmpc_fsm_goal", "frp_nmpc_fsm_force", "frp_nmpc_fsm_mpc", "frp_nmpc_fsm_safety", "frp_nmpc_fsm_exec_begin", "frp_nmpc_fsm_exec_end"]
+FSM_INIT, FSM_WAIT_TARGET, FSM_INIT_YAW, FSM_GEN_NEW_TRAJ, FSM_REPLAN_TRAJ, FSM_EXEC_TRAJ = range(6)  # FRP_FSM_*: enum FSM_EXEC_STATE, in its order
+FSM_EXT_NOISE_BOUND = 0.5  # nmpc/ext_noise_bound (nmpc_manage.cpp:13)
+FSM_EXEC_PERIOD = 0.01     # the period of exec_timer_ (nmpc_manage.cpp:44) = that of the command timer
 
 
 def goal_search_table():
@@ -398,7 +417,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS + FSM_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -436,6 +455,13 @@ def lib():
         l.frp_nmpc_command_batch.argtypes = [ctypes.POINTER(Command), vp]
         l.frp_nmpc_tick_begin.argtypes = [ctypes.POINTER(Tick), vp, vp]
         l.frp_nmpc_tick_end.argtypes = [ctypes.POINTER(Tick), ctypes.POINTER(TickIn), vp]
+        pf = ctypes.POINTER(Fsm)
+        l.frp_nmpc_fsm_goal.argtypes = [pf, vp, vp, vp]
+        l.frp_nmpc_fsm_force.argtypes = [pf, vp, vp, cd, vp]
+        l.frp_nmpc_fsm_mpc.argtypes = [pf, vp, vp]
+        l.frp_nmpc_fsm_safety.argtypes = [pf, vp, vp, vp]
+        l.frp_nmpc_fsm_exec_begin.argtypes = [pf, ctypes.POINTER(FsmExecIn), vp]
+        l.frp_nmpc_fsm_exec_end.argtypes = [pf, vp, vp, vp, vp]
         _lib = l
     return _lib
 
@@ -1448,7 +1474,7 @@ class AstarPlanner:
         self.ws_bytes = int(lib().frp_nmpc_astar_workspace_bytes(ctypes.byref(a)))
         self.ws = torch.empty((self.ws_bytes // 8 + 1,), **f64)
 
-    def _args(self, init=True, local_box=None, active=None):
+    def _args(self, init=True, local_box=None, active=None, end_pt=None, end_vel=None, external_acc=None):
         w = self.world
         a = Astar()
         a.B = self.B; a.occ = self.occ.data_ptr(); a.grid[:] = tuple(self.occ.shape); a.origin[:] = w["origin"]; a.map_size[:] = w["map_size"]
@@ -1458,6 +1484,10 @@ class AstarPlanner:
             setattr(a, k, w[k])
         a.allocate_num = self.allocate_num
         a.start_pt, a.start_vel, a.start_acc, a.end_pt, a.end_vel, a.external_acc = (t.data_ptr() for t in self._q)
+        for name, over in (("end_pt", end_pt), ("end_vel", end_vel), ("external_acc", external_acc)):  # a caller's own [B,3] in place of the uploaded one
+            if over is not None:
+                assert over.dtype == self.torch.float64 and tuple(over.shape) == (self.B, 3) and over.is_contiguous() and over.device == self.device
+                setattr(a, name, over.data_ptr())
         a.active = active.data_ptr() if active is not None else None
         a.init_search = 1 if init else 0
         a.Ts = self.Ts; a.K = self.K
@@ -1481,12 +1511,14 @@ class AstarPlanner:
                 self._retry = [t.zeros_like(self._q[0]), t.zeros_like(self._q[0])]
             cp(self._retry[0], retry[0]); cp(self._retry[1], retry[1])
 
-    def plan(self, init=True, local_box=None, stream=None, active=None):
+    def plan(self, init=True, local_box=None, stream=None, active=None, end_pt=None, end_vel=None, external_acc=None):
         """Asynchronous on `stream` (or torch's current stream): every planner's search + retry + getKinoTraj.
         active: int32 [B] device tensor -- only planners with a non-zero entry search (the others keep their path);
-        a planner whose search ends in NO_PATH keeps its previous path as well."""
+        a planner whose search ends in NO_PATH keeps its previous path as well.
+        end_pt / end_vel / external_acc: [B,3] f64 device tensors read in place of the uploaded ones (FleetFSM hands over its own
+        end_pt and external_acc: no copy)."""
         s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
-        a = self._args(init, local_box, active)
+        a = self._args(init, local_box, active, end_pt, end_vel, external_acc)
         _check(lib().frp_nmpc_astar_batch(ctypes.byref(a), ctypes.c_void_p(self.ws.data_ptr()), self.ws_bytes, ctypes.c_void_p(s.cuda_stream)),
                "frp_nmpc_astar_batch")
 
@@ -1943,3 +1975,202 @@ class DeviceFleet:
         t_cur counts from pre_mpc_start_time_, which the reference resets at EVERY solveNMPC call (:359), rejected ones included."""
         assert getattr(self, "pre_plan", None) is not None, "call snapshot_commands() first: it owns pre_plan / have_traj"
         return command_batch_device(self.pre_plan, self.have_traj, t_cur, status, pub_end, end_pt, odom, init_yaw, t_yaw, out, Ts, mass, g, stream)
+
+
+class FleetFSM:
+    """NMPCManage (plan_manage/src/nmpc_manage.cpp) for the B planners of a DeviceFleet, on the device (include/frp_nmpc_fsm.h): a fleet goes
+    goal -> yaw alignment -> plan -> execute -> replan on force / collision / failure -> goal reached -> next goal without the host reading
+    anything back.  Owns the state tensors, [B] int32 unless noted: state (FSM_*, INIT at first), have_odom (the CALLER sets it: the
+    odometry callbacks are not restated), have_target, have_traj (NMPCManage's have_traj_, not fleet.have_traj = have_mpc_traj_), trigger,
+    call_init_yaw, consider_force, replan_force_surpass, surpass_count, plan_fail_count; end_pt, external_acc, last_external_acc [B,3] f64,
+    init_yaw [B] f64, yaw_odom [B,9] f64, change_yaw_time / kino_start_time [B] f64 on the caller's clock, all zero at first (the reference
+    leaves the doubles uninitialised); search [B], the mask of the last exec_step; mpc_start [B] f64, pre_mpc_start_time_ as period() keeps it.
+    Shares exec_mpc, cmd_status and pub_end with `tick` (a TickState, made here when None) and mode with the fleet; exec_mpc is ZEROED
+    here: under the state machine a planner solves only after its first successful search (the reference's exec_mpc_ = false).
+    The command timer's yaw inputs are this object's: DeviceFleet.commands(..., odom=fsm.yaw_odom, init_yaw=fsm.init_yaw, t_yaw=fsm.t_yaw(...)).
+    This layer is structurally unpinned: the reference has no test vectors for it; tests/fsm_oracle.py is the restatement it is held to."""
+
+    INT_FIELDS = ("state", "have_odom", "have_target", "have_traj", "trigger", "call_init_yaw", "consider_force", "replan_force_surpass",
+                  "surpass_count", "plan_fail_count")
+    F64_FIELDS = (("end_pt", 3), ("external_acc", 3), ("last_external_acc", 3), ("init_yaw", 0), ("yaw_odom", 9), ("change_yaw_time", 0),
+                  ("kino_start_time", 0))
+    MAX_STEPS = 5   # exec steps per period: exec_timer_ runs at 100 Hz, the tick at 20 Hz
+    S = 5           # command callbacks per period
+
+    def __init__(self, fleet, tick=None, ext_noise_bound=FSM_EXT_NOISE_BOUND):
+        t = fleet.torch
+        dev = fleet.solver.device
+        self.torch, self.fleet, self.B = t, fleet, fleet.B
+        self.tick = tick if tick is not None else TickState(fleet)
+        assert self.tick.B == self.B
+        self.ext_noise_bound = float(ext_noise_bound)
+        for n in self.INT_FIELDS + ("search",):
+            setattr(self, n, t.zeros((self.B,), dtype=t.int32, device=dev))
+        self.state.fill_(FSM_INIT)
+        for n, w in self.F64_FIELDS:
+            setattr(self, n, t.zeros((self.B, w) if w else (self.B,), dtype=t.float64, device=dev))
+        self.exec_mpc, self.cmd_status, self.pub_end, self.mode = self.tick.exec_mpc, self.tick.cmd_status, self.tick.pub_end, fleet.mode
+        self.exec_mpc.zero_()
+        f64 = dict(dtype=t.float64, device=dev)
+        self.mpc_start = t.zeros((self.B,), **f64)
+        # period()'s own buffers: a capture of it allocates nothing of the caller's
+        z = lambda: t.zeros((self.B,), dtype=t.int32, device=dev)
+        self.safety_out = SafetyCheck(z(), z(), z(), z())
+        self.ref_pos, self.ref_yaw = t.zeros((self.B, fleet.N, 3), **f64), t.zeros((self.B, fleet.N), **f64)
+        self.t_step, self.toff = t.zeros((self.B,), **f64), t.zeros((self.B,), **f64)
+        self.t_cmd, self.t_rot = t.zeros((self.B, self.S), **f64), t.zeros((self.B, self.S), **f64)
+        self._ramp = t.arange(self.S, **f64) * FSM_EXEC_PERIOD
+        self._ran = t.zeros((self.B,), dtype=t.bool, device=dev)
+        self.commands_out = None
+
+    def struct(self):
+        p = lambda n: getattr(self, n).data_ptr() if getattr(self, n) is not None else None
+        return Fsm(self.B, *[p(n) for n, _ in Fsm._fields_[1:]])
+
+    def arrays(self):
+        """Every state array on the host (a synchronising read-back: tests and logs)."""
+        names = self.INT_FIELDS + ("exec_mpc", "cmd_status", "pub_end", "search") + tuple(n for n, _ in self.F64_FIELDS)
+        return {n: getattr(self, n).cpu().numpy() for n in names}
+
+    def _stream(self, stream):
+        return stream if stream is not None else self.torch.cuda.current_stream(self.state.device)
+
+    def _arg(self, a, dtype, shape):
+        assert self.torch.is_tensor(a) and a.dtype == dtype and tuple(a.shape) == shape and a.is_contiguous() and a.device == self.state.device, \
+            (tuple(a.shape), shape, a.dtype)
+        return ctypes.c_void_p(a.data_ptr())
+
+    def goal(self, goal, fresh, stream=None):
+        """goalCallback (nmpc_manage.cpp:481-493): goal [B,3] f64, fresh [B] int32 (non-zero: a message for this planner)."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_goal(ctypes.byref(f), self._arg(goal, t.float64, (self.B, 3)), self._arg(fresh, t.int32, (self.B,)),
+                                       ctypes.c_void_p(self._stream(stream).cuda_stream)), "frp_nmpc_fsm_goal")
+
+    def force(self, force, fresh, stream=None):
+        """extforceCallback (nmpc_manage.cpp:366-418): force [B,3] f64 (mass-normalised), fresh [B] int32."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_force(ctypes.byref(f), self._arg(force, t.float64, (self.B, 3)), self._arg(fresh, t.int32, (self.B,)),
+                                        self.ext_noise_bound, ctypes.c_void_p(self._stream(stream).cuda_stream)), "frp_nmpc_fsm_force")
+
+    def mpc_result(self, result=None, stream=None):
+        """The switch of mpcCallback (nmpc_manage.cpp:60-97) on result [B] int32 (None: tick.result, as full_tick(tick=...) left it)."""
+        f = self.struct()
+        result = self.tick.result if result is None else result
+        _check(lib().frp_nmpc_fsm_mpc(ctypes.byref(f), self._arg(result, self.torch.int32, (self.B,)), ctypes.c_void_p(self._stream(stream).cuda_stream)),
+               "frp_nmpc_fsm_mpc")
+
+    def safety_verdict(self, goal_blocked, first_hit, stream=None):
+        """The transitions of checkReplanCallback (nmpc_manage.cpp:318-325, :333-338) for verdicts [B] int32 the caller holds."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_safety(ctypes.byref(f), self._arg(goal_blocked, t.int32, (self.B,)), self._arg(first_hit, t.int32, (self.B,)),
+                                         ctypes.c_void_p(self._stream(stream).cuda_stream)), "frp_nmpc_fsm_safety")
+
+    def safety(self, occmap, planner, local_box=None, stride=5, stream=None, out=None):
+        """One checkReplanCallback (nmpc_manage.cpp:285-341): OccupancyMap.safety_check on this object's end_pt (moved in place where the
+        search finds a free goal) / have_target / have_traj and the planner's kino_path / kino_size, then the transitions.  Returns the
+        SafetyCheck (out, or this object's own safety_out)."""
+        out = out if out is not None else self.safety_out
+        occmap.safety_check(self.end_pt, planner.kino_path, planner.kino_size, have_target=self.have_target, have_traj=self.have_traj,
+                            local_box=local_box, stride=stride, stream=stream, out=out)
+        self.safety_verdict(out.goal_blocked, out.first_hit, stream)
+        return out
+
+    def bind(self, planner):
+        """Makes the planner's retry buffers exist (an allocation: period() and exec_step() call it; call it once before a capture)."""
+        assert planner.B == self.B and planner.device == self.state.device
+        if planner._retry is None:
+            planner._retry = [self.torch.zeros_like(planner._q[0]), self.torch.zeros_like(planner._q[0])]
+
+    def exec_step(self, planner, state, t_cur, now, local_box=None, end_vel=None, stream=None, Ts=None, mass=None, g=None):
+        """One execFSMCallback (nmpc_manage.cpp:109-260) for every planner: frp_nmpc_fsm_exec_begin writes self.search and, for the planners
+        that search, the start / retry state straight into the AstarPlanner's own buffers; planner.plan(active=self.search) with this
+        object's end_pt and external_acc; frp_nmpc_fsm_exec_end applies the verdict (planner.status).  state [B,9] f64 odometry, t_cur [B]
+        f64 seconds since pre_mpc_start_time_, now [1] f64; end_vel [B,3] or None: the planner's uploaded one (zeros at first).
+        Ts / mass / g: COMMAND_DEFAULTS.  Planners that do not search keep their A* rows and their path."""
+        self.bind(planner)
+        s = self._stream(stream)
+        self.exec_begin(state, t_cur, now, planner._q[0], planner._q[1], planner._q[2], planner._retry[0], planner._retry[1], s, Ts, mass, g)
+        planner.plan(init=True, local_box=local_box, stream=s, active=self.search, end_pt=self.end_pt, end_vel=end_vel, external_acc=self.external_acc)
+        self.exec_end(planner.status, now, s)
+
+    def exec_begin(self, state, t_cur, now, start_pt, start_vel, start_acc, retry_pt, retry_vel, stream=None, Ts=None, mass=None, g=None):
+        """frp_nmpc_fsm_exec_begin: the first half of exec_step, for a caller with its own search.  Writes self.search and, for the
+        planners that search alone, the five [B,3] f64 start / retry tensors; reads the fleet's pre_plan and the tick's exit_code."""
+        t = self.torch
+        k = dict(COMMAND_DEFAULTS)
+        k.update({n: float(v) for n, v in (("Ts", Ts), ("mass", mass), ("g", g)) if v is not None})
+        fl, B = self.fleet, self.B
+        f = self.struct()
+        v = lambda a: self._arg(a, t.float64, (B, 3)).value
+        i = FsmExecIn(fl.N, k["Ts"], k["mass"], k["g"], self._arg(state, t.float64, (B, 9)).value, self._arg(fl.pre_plan, t.float64, (B, fl.N, L.NZ)).value,
+                      self._arg(self.tick.exit_code, t.int32, (B,)).value, self._arg(t_cur, t.float64, (B,)).value, self._arg(now, t.float64, (1,)).value,
+                      self.search.data_ptr(), v(start_pt), v(start_vel), v(start_acc), v(retry_pt), v(retry_vel))
+        _check(lib().frp_nmpc_fsm_exec_begin(ctypes.byref(f), ctypes.byref(i), ctypes.c_void_p(self._stream(stream).cuda_stream)), "frp_nmpc_fsm_exec_begin")
+
+    def exec_end(self, astar_status, now, stream=None):
+        """frp_nmpc_fsm_exec_end: the second half of exec_step, on self.search and astar_status [B] int32 (AstarPlanner.status)."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_exec_end(ctypes.byref(f), ctypes.c_void_p(self.search.data_ptr()), self._arg(astar_status, t.int32, (self.B,)),
+                                           self._arg(now, t.float64, (1,)), ctypes.c_void_p(self._stream(stream).cuda_stream)), "frp_nmpc_fsm_exec_end")
+
+    def time_offset(self, mpc_start, out=None):
+        """(mpc_start_time_ - kino_start_time_).toSec() (nmpc_solver.cpp:436) on the device: mpc_start [1] or [B] f64 -> [B]."""
+        return self.torch.sub(mpc_start, self.kino_start_time, out=out)
+
+    def t_yaw(self, now, S, out=None):
+        """(now - change_yaw_time_).toSec() (nmpc_solver.cpp:885) of S command callbacks at now, now + 0.01, ...: now [1] f64 -> [B,S]."""
+        t = self.torch
+        ramp = self._ramp if S == self.S else t.arange(S, dtype=t.float64, device=now.device) * FSM_EXEC_PERIOD
+        return t.sub((now + ramp)[None, :], self.change_yaw_time[:, None], out=out)
+
+    def period(self, planner, occmap, state, clock, cloud=None, *, goal=None, goal_fresh=None, force=None, force_fresh=None, fsm_steps=1,
+               local_box=None, end_vel=None, stream=None, **tick_args):
+        """One 50 ms period of the fleet, everything enqueued on `stream` (torch's current stream when None), nothing read back, in this
+        fixed order:
+          1. goal(goal, goal_fresh) and force(force, force_fresh), each where given;
+          2. safety(occmap, planner, local_box);
+          3. fsm_steps (1 ... 5) exec_step()s, step k at clock[k] with t_cur = clock[k] - mpc_start;
+          4. fleet.full_tick(external_acc, planner.kino_path, time_offset, cloud, ..., kino_size=planner.kino_size, state=state, tick=self.tick,
+             end_pt=self.end_pt, **tick_args) at clock[fsm_steps], with time_offset = clock[fsm_steps] - kino_start_time; mpc_start <- that
+             time for the planners that got past solveNMPC's gates (tick.gate == TICK_RUN; nmpc_solver.cpp:358-359);
+          5. mpc_result();
+          6. fleet.commands with S = 5 callbacks at clock[fsm_steps + 1], + 0.01, ...: t_cur from mpc_start, t_yaw from change_yaw_time, the
+             yaw inputs this object's; tick.reset_output <- the returned reset_output.
+        clock: [fsm_steps + 2] f64 device tensor on the caller's clock (clock_for() fills the reference's timer periods in).  state [B,9]
+        f64 odometry.  cloud and tick_args (grid, cut, view, cloud_count, tube_consts, corridor_consts, Ts) are full_tick's.  A
+        captured period replays with new contents of goal / goal_fresh / force / force_fresh / state / clock.  Returns the Commands."""
+        t = self.torch
+        assert 1 <= int(fsm_steps) <= self.MAX_STEPS and tuple(clock.shape) == (int(fsm_steps) + 2,) and clock.dtype == t.float64
+        fl, tk = self.fleet, self.tick
+        s = self._stream(stream)
+        self.bind(planner)
+        if goal is not None:
+            self.goal(goal, goal_fresh, s)
+        if force is not None:
+            self.force(force, force_fresh, s)
+        self.safety(occmap, planner, local_box=local_box, stream=s)
+        with t.cuda.stream(s):
+            for k in range(int(fsm_steps)):
+                now = clock[k:k + 1]
+                t.sub(now, self.mpc_start, out=self.t_step)
+                self.exec_step(planner, state, self.t_step, now, local_box=local_box, end_vel=end_vel, stream=s, Ts=tick_args.get("Ts"))
+            now = clock[fsm_steps:fsm_steps + 1]
+            self.time_offset(now, out=self.toff)
+            fl.full_tick(self.external_acc, planner.kino_path, self.toff, cloud, self.ref_pos, self.ref_yaw, stream=s, kino_size=planner.kino_size,
+                         state=state, tick=tk, end_pt=self.end_pt, **tick_args)
+            t.eq(tk.gate, TICK_RUN, out=self._ran)
+            t.where(self._ran, now, self.mpc_start, out=self.mpc_start)
+            self.mpc_result(stream=s)
+            first = clock[fsm_steps + 1:fsm_steps + 2]
+            t.sub((first + self._ramp)[None, :], self.mpc_start[:, None], out=self.t_cmd)
+            self.t_yaw(first, self.S, out=self.t_rot)
+            self.commands_out = fl.commands(self.t_cmd, self.cmd_status, self.pub_end, tk.cmd_end_pt, odom=self.yaw_odom, init_yaw=self.init_yaw,
+                                            t_yaw=self.t_rot, out=self.commands_out, stream=s, Ts=tick_args.get("Ts"))
+            tk.reset_output = self.commands_out.reset_output
+        return self.commands_out
+
+    @staticmethod
+    def clock_for(t0, fsm_steps):
+        """The reference's timers for a period starting at t0 (host floats): exec steps at t0, t0 + 0.01, ..., the tick and the first
+        command callback one exec period after the last step and after the tick."""
+        return [t0 + FSM_EXEC_PERIOD * k for k in range(int(fsm_steps) + 2)]

@@ -600,6 +600,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * :435-481) for B planners, one launch before the cold start and one after the solve.  A header of its own, part of this ABI version. */
 #include "frp_nmpc_outcome.h"
 
+/* ---- (11) the fleet state machine: goals, forces, safety verdicts, solveNMPC's return value and execFSMCallback ---- */
+/* NMPCManage (plan_manage/src/nmpc_manage.cpp) for B planners, one launch per callback, execFSMCallback split around the A*.  A header of
+ * its own, part of this ABI version. */
+#include "frp_nmpc_fsm.h"
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 

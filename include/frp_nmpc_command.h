@@ -11,7 +11,7 @@
  *     CMD_STATUS                                                plan_manage/nmpc_utils.h:115-122   FRP_CMD_*
  * What is NOT here: whether a solve is accepted (fail_count_ / replan_count_, :398-421) -- the caller hands over the mask, and
  * frp_nmpc_tick_end (frp_nmpc_outcome.h) computes the reference's on the device, together with pub_end_ and cmd_end_pt_; the FSM
- * that calls callInitYaw; the clock -- t_cur and t_yaw are the caller's; ROS messages.  mav_msgs is not part of
+ * that calls callInitYaw (section (11), frp_nmpc_fsm.h: frp_nmpc_fsm_exec_begin writes odom, init_yaw and the ROTATE_YAW status); the clock -- t_cur and t_yaw are the caller's; ROS messages.  mav_msgs is not part of
  * the reference tree, so msgMultiDofJointTrajectoryFromPositionYaw (:889) is not restated: a ROTATE_YAW sample carries the position,
  * the yaw and the quaternion of a rotation about z by it, and the caller fills its message from them.
  * tests/command_oracle.py is the executable statement.

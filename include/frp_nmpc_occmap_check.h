@@ -7,7 +7,7 @@
  * What is restated: OccMap::checkPosSurround (occ_grid/src/occ_map.cpp:625-643) and the two halves of its only caller,
  * NMPCManage::checkReplanCallback (plan_manage/src/nmpc_manage.cpp:285-341): the goal test with the search for another goal
  * (:289-316) and the walk along the kinodynamic path (:329-340).  The FSM transitions that follow them stay with the caller, who
- * reads goal_blocked and first_hit.  tests/occmap_check_oracle.py is the executable statement.
+ * reads goal_blocked and first_hit -- or hands both to frp_nmpc_fsm_safety (section (11), frp_nmpc_fsm.h), which restates them.  tests/occmap_check_oracle.py is the executable statement.
  *
  * checkPosSurround(pos, ratio) probes getVoxelState(pos + Vector3d(i, j, k) * resolution) for |i|, |j| <= ceil(ego_r * ratio /
  * resolution) and |k| <= ceil(ego_h * ratio / resolution) and returns true ("free") when every probe is 0: a probe outside the

@@ -14,6 +14,7 @@
  *     the return module                                         :452-481                           frp_nmpc_tick_end   (result)
  *     exec_mpc_ = false for 0, -2, -3                           nmpc_manage.cpp:60-97              frp_nmpc_tick_end   (exec_mpc)
  * What is NOT here: execFSMCallback, the transitions of checkReplanCallback, extforceCallback and plan_fail_count_ (nmpc_manage.cpp);
+ * (those four are section (11), frp_nmpc_fsm.h, which shares exec_mpc, cmd_status and pub_end with this struct);
  * initMPCOutput's pre_mpc_output_ = mpc_output_ (:284) -- a cold start does not overwrite the command timer's snapshot; the clocks --
  * time_offset is the caller's.  The reference holds no test vectors for this rule: tests/outcome_oracle.py is a line-by-line
  * restatement, and the executable statement of what these two calls do.
