@@ -190,6 +190,12 @@ class FsmExecIn(ctypes.Structure):  # frp_nmpc_fsm_exec_in (include/frp_nmpc_fsm
                                                "retry_pt", "retry_vel")]
 
 
+class VehicleArgs(ctypes.Structure):  # frp_nmpc_vehicle (include/frp_nmpc_vehicle.h)
+    _fields_ = [("B", ctypes.c_int), ("S", ctypes.c_int), ("n_sub", ctypes.c_int), ("mass", ctypes.c_double), ("g", ctypes.c_double), ("dt_cmd", ctypes.c_double),
+                ("kp", ctypes.c_double * 3), ("kv", ctypes.c_double * 3), ("ka", ctypes.c_double * 3)] + \
+               [(n, ctypes.c_void_p) for n in ("x", "f_true", "cmd", "kind", "hold", "trace", "sat")]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -263,6 +269,15 @@ FSM_EXPORTS = ["frp_nmpc_fsm_goal", "frp_nmpc_fsm_force", "frp_nmpc_fsm_mpc", "f
 FSM_INIT, FSM_WAIT_TARGET, FSM_INIT_YAW, FSM_GEN_NEW_TRAJ, FSM_REPLAN_TRAJ, FSM_EXEC_TRAJ = range(6)  # FRP_FSM_*: enum FSM_EXEC_STATE, in its order
 FSM_EXT_NOISE_BOUND = 0.5  # nmpc/ext_noise_bound (nmpc_manage.cpp:13)
 FSM_EXEC_PERIOD = 0.01     # the period of exec_timer_ (nmpc_manage.cpp:44) = that of the command timer
+
+# the vehicle (include/frp_nmpc_vehicle.h)
+VEHICLE_EXPORTS = ["frp_nmpc_vehicle_step", "frp_nmpc_vehicle_reset", "frp_nmpc_vehicle_message", "frp_nmpc_vehicle_odometry"]
+VEHICLE_STATE, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_MAX_SUB = 9, 8, 13, 16  # FRP_VEHICLE_*
+ODOM_WORLD, ODOM_BODY = 1, 2  # FRP_ODOM_*: odometryCallback, odometryTransCallback
+VEHICLE_SAT_THRUST_LO, VEHICLE_SAT_THRUST_HI, VEHICLE_SAT_ROLL, VEHICLE_SAT_PITCH, VEHICLE_SAT_RATE0, VEHICLE_SAT_ZERO_ACC, VEHICLE_SAT_YAW_WRAP = 1, 2, 4, 8, 16, 128, 256
+# the controller's gains (no reference counterpart: the reference flies RotorS' controller) and what it is told; mass and g are the
+# plant's own (csrc/frp_model.hpp), dt_cmd the command timer's period
+VEHICLE_DEFAULTS = dict(kp=(6.0, 6.0, 8.0), kv=(4.0, 4.0, 5.0), ka=(10.0, 10.0, 4.0), mass=0.745319, g=9.81, dt_cmd=FSM_EXEC_PERIOD, n_sub=4)
 
 
 def goal_search_table():
@@ -417,7 +432,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS + FSM_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS + FSM_EXPORTS + VEHICLE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -462,6 +477,10 @@ def lib():
         l.frp_nmpc_fsm_safety.argtypes = [pf, vp, vp, vp]
         l.frp_nmpc_fsm_exec_begin.argtypes = [pf, ctypes.POINTER(FsmExecIn), vp]
         l.frp_nmpc_fsm_exec_end.argtypes = [pf, vp, vp, vp, vp]
+        l.frp_nmpc_vehicle_step.argtypes = [ctypes.POINTER(VehicleArgs), vp]
+        l.frp_nmpc_vehicle_reset.argtypes = [ci, vp, vp, vp, vp, vp]
+        l.frp_nmpc_vehicle_message.argtypes = [ci, ci, vp, vp, vp]
+        l.frp_nmpc_vehicle_odometry.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]
         _lib = l
     return _lib
 
@@ -1977,11 +1996,91 @@ class DeviceFleet:
         return command_batch_device(self.pre_plan, self.have_traj, t_cur, status, pub_end, end_pt, odom, init_yaw, t_yaw, out, Ts, mass, g, stream)
 
 
+class Vehicle:
+    """The vehicle of every planner of a DeviceFleet, on the device (include/frp_nmpc_vehicle.h): a tracking plant that flies the command
+    timer's samples and the reference's odometry callbacks, so that FleetFSM.period(..., vehicle=...) closes the loop without the host.
+    Owns, all float64 device tensors unless noted: x [B,9] the plant state (position, world velocity, roll pitch yaw), hold [B,8] the last
+    published position and yaw, f_true [B,3] the TRUE mass-normalised external force (the caller writes it; what the planner is told stays
+    the caller's `force` / `force_fresh` of period()), msg [B,13] the last odometry message, state [B,9] what the callbacks made of it (the
+    `state` of period(), exec_step() and full_tick()), state_prev [B,9], fresh [B] int32 (ones: every planner hears every message), and
+    with trace=True trace [B,S,9] / sat [B,S] int32 of the last step().
+    kp, kv, ka, n_sub, mass, g, dt_cmd: VEHICLE_DEFAULTS -- the controller has no reference counterpart, the plant is the planner's own
+    model (csrc/frp_model.hpp).  odom_type: ODOM_BODY (odometryTransCallback: the RotorS message, body-frame twist) or ODOM_WORLD."""
+
+    def __init__(self, fleet, kp=None, kv=None, ka=None, n_sub=None, odom_type=ODOM_BODY, mass=None, g=None, dt_cmd=None, trace=False, S=5):
+        t = fleet.torch
+        dev = fleet.solver.device
+        self.torch, self.fleet, self.B, self.S = t, fleet, fleet.B, int(S)
+        k = dict(VEHICLE_DEFAULTS)
+        k.update({n: v for n, v in (("kp", kp), ("kv", kv), ("ka", ka), ("n_sub", n_sub), ("mass", mass), ("g", g), ("dt_cmd", dt_cmd)) if v is not None})
+        self.kp, self.kv, self.ka = (tuple(float(v) for v in k[n]) for n in ("kp", "kv", "ka"))
+        assert len(self.kp) == len(self.kv) == len(self.ka) == 3
+        self.n_sub, self.mass, self.g, self.dt_cmd = int(k["n_sub"]), float(k["mass"]), float(k["g"]), float(k["dt_cmd"])
+        if odom_type not in (ODOM_WORLD, ODOM_BODY):
+            raise ValueError("odom_type is ODOM_WORLD or ODOM_BODY")
+        self.odom_type = int(odom_type)
+        f64 = dict(dtype=t.float64, device=dev)
+        self.x, self.state, self.state_prev = (t.zeros((self.B, VEHICLE_STATE), **f64) for _ in range(3))
+        self.hold = t.zeros((self.B, VEHICLE_HOLD_STRIDE), **f64)
+        self.f_true = t.zeros((self.B, 3), **f64)
+        self.msg = t.zeros((self.B, VEHICLE_MSG_STRIDE), **f64)
+        self.fresh = t.ones((self.B,), dtype=t.int32, device=dev)
+        self.trace = t.zeros((self.B, self.S, VEHICLE_STATE), **f64) if trace else None
+        self.sat = t.zeros((self.B, self.S), dtype=t.int32, device=dev) if trace else None
+
+    def _stream(self, stream):
+        return ctypes.c_void_p((stream if stream is not None else self.torch.cuda.current_stream(self.x.device)).cuda_stream)
+
+    def _arg(self, a, dtype, shape):
+        assert self.torch.is_tensor(a) and a.dtype == dtype and tuple(a.shape) == shape and a.is_contiguous() and a.device == self.x.device, \
+            (tuple(a.shape), shape, a.dtype)
+        return ctypes.c_void_p(a.data_ptr())
+
+    def reset(self, x0, mask=None, stream=None):
+        """frp_nmpc_vehicle_reset: where mask [B] int32 != 0 (None: everywhere) x <- x0 [B,9] and hold <- its position and yaw: the
+        vehicle hovers there until something is published.  `state` is the callbacks': call odometry(fsm) to publish the new pose."""
+        t = self.torch
+        m = self._arg(mask, t.int32, (self.B,)) if mask is not None else None
+        _check(lib().frp_nmpc_vehicle_reset(self.B, self._arg(x0, t.float64, (self.B, VEHICLE_STATE)), m, ctypes.c_void_p(self.x.data_ptr()),
+                                            ctypes.c_void_p(self.hold.data_ptr()), self._stream(stream)), "frp_nmpc_vehicle_reset")
+
+    def step(self, commands, stream=None):
+        """frp_nmpc_vehicle_step: the S samples of a Commands object (cmd [B,S,16], kind [B,S]) flown in order under f_true; x and hold
+        in place, trace / sat where the object was made with trace=True (S is then the constructor's)."""
+        t = self.torch
+        S = int(commands.cmd.shape[1])
+        if self.trace is not None and S != self.S:
+            raise ValueError(f"this Vehicle traces S = {self.S} samples per call, the commands hold {S}")
+        v = VehicleArgs(self.B, S, self.n_sub, self.mass, self.g, self.dt_cmd, (ctypes.c_double * 3)(*self.kp), (ctypes.c_double * 3)(*self.kv),
+                        (ctypes.c_double * 3)(*self.ka), self.x.data_ptr(), self.f_true.data_ptr(),
+                        self._arg(commands.cmd, t.float64, (self.B, S, COMMAND_STRIDE)).value, self._arg(commands.kind, t.int32, (self.B, S)).value,
+                        self.hold.data_ptr(), self.trace.data_ptr() if self.trace is not None else None, self.sat.data_ptr() if self.sat is not None else None)
+        _check(lib().frp_nmpc_vehicle_step(ctypes.byref(v), self._stream(stream)), "frp_nmpc_vehicle_step")
+
+    def message(self, stream=None):
+        """frp_nmpc_vehicle_message: msg <- the odometry message of x for this object's odom_type."""
+        _check(lib().frp_nmpc_vehicle_message(self.B, self.odom_type, ctypes.c_void_p(self.x.data_ptr()), ctypes.c_void_p(self.msg.data_ptr()),
+                                              self._stream(stream)), "frp_nmpc_vehicle_message")
+
+    def odometry(self, fsm, msg=None, fresh=None, stream=None):
+        """odometryCallback / odometryTransCallback (nmpc_manage.cpp:421-478) into state, state_prev and fsm.have_odom.  msg None (a
+        simulated fleet): the message is produced from the plant first, message(); msg [B,13] (a real fleet): the callback alone.
+        fresh [B] int32: who got a message (None: everybody)."""
+        t = self.torch
+        if msg is None:
+            self.message(stream)
+            msg = self.msg
+        fresh = self.fresh if fresh is None else fresh
+        _check(lib().frp_nmpc_vehicle_odometry(self.B, self.odom_type, self._arg(msg, t.float64, (self.B, VEHICLE_MSG_STRIDE)), self._arg(fresh, t.int32, (self.B,)),
+                                               ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(self.state_prev.data_ptr()),
+                                               self._arg(fsm.have_odom, t.int32, (self.B,)), self._stream(stream)), "frp_nmpc_vehicle_odometry")
+
+
 class FleetFSM:
     """NMPCManage (plan_manage/src/nmpc_manage.cpp) for the B planners of a DeviceFleet, on the device (include/frp_nmpc_fsm.h): a fleet goes
     goal -> yaw alignment -> plan -> execute -> replan on force / collision / failure -> goal reached -> next goal without the host reading
-    anything back.  Owns the state tensors, [B] int32 unless noted: state (FSM_*, INIT at first), have_odom (the CALLER sets it: the
-    odometry callbacks are not restated), have_target, have_traj (NMPCManage's have_traj_, not fleet.have_traj = have_mpc_traj_), trigger,
+    anything back.  Owns the state tensors, [B] int32 unless noted: state (FSM_*, INIT at first), have_odom (the CALLER sets it, or a
+    Vehicle's odometry callbacks do), have_target, have_traj (NMPCManage's have_traj_, not fleet.have_traj = have_mpc_traj_), trigger,
     call_init_yaw, consider_force, replan_force_surpass, surpass_count, plan_fail_count; end_pt, external_acc, last_external_acc [B,3] f64,
     init_yaw [B] f64, yaw_odom [B,9] f64, change_yaw_time / kino_start_time [B] f64 on the caller's clock, all zero at first (the reference
     leaves the doubles uninitialised); search [B], the mask of the last exec_step; mpc_start [B] f64, pre_mpc_start_time_ as period() keeps it.
@@ -2124,7 +2223,7 @@ class FleetFSM:
         return t.sub((now + ramp)[None, :], self.change_yaw_time[:, None], out=out)
 
     def period(self, planner, occmap, state, clock, cloud=None, *, goal=None, goal_fresh=None, force=None, force_fresh=None, fsm_steps=1,
-               local_box=None, end_vel=None, stream=None, **tick_args):
+               local_box=None, end_vel=None, stream=None, vehicle=None, **tick_args):
         """One 50 ms period of the fleet, everything enqueued on `stream` (torch's current stream when None), nothing read back, in this
         fixed order:
           1. goal(goal, goal_fresh) and force(force, force_fresh), each where given;
@@ -2138,8 +2237,15 @@ class FleetFSM:
              yaw inputs this object's; tick.reset_output <- the returned reset_output.
         clock: [fsm_steps + 2] f64 device tensor on the caller's clock (clock_for() fills the reference's timer periods in).  state [B,9]
         f64 odometry.  cloud and tick_args (grid, cut, view, cloud_count, tube_consts, corridor_consts, Ts) are full_tick's.  A
-        captured period replays with new contents of goal / goal_fresh / force / force_fresh / state / clock.  Returns the Commands."""
+        captured period replays with new contents of goal / goal_fresh / force / force_fresh / state / clock.  Returns the Commands.
+        vehicle: a Vehicle, or None.  With one, three more launches follow step 6 --
+          7. vehicle.step(commands) under vehicle.f_true, vehicle.odometry(self): message, then the callback into vehicle.state and have_odom
+        -- and `state` is vehicle.state (pass it, or None): the next period plans from what the vehicle flew, so K periods are one graph
+        with no host in the loop.  The force estimator stays the caller's: force / force_fresh.  With None the launches are steps 1-6."""
         t = self.torch
+        if vehicle is not None:
+            assert vehicle.B == self.B and (state is None or state is vehicle.state), "with a vehicle the odometry is vehicle.state"
+            state = vehicle.state
         assert 1 <= int(fsm_steps) <= self.MAX_STEPS and tuple(clock.shape) == (int(fsm_steps) + 2,) and clock.dtype == t.float64
         fl, tk = self.fleet, self.tick
         s = self._stream(stream)
@@ -2167,6 +2273,9 @@ class FleetFSM:
             self.commands_out = fl.commands(self.t_cmd, self.cmd_status, self.pub_end, tk.cmd_end_pt, odom=self.yaw_odom, init_yaw=self.init_yaw,
                                             t_yaw=self.t_rot, out=self.commands_out, stream=s, Ts=tick_args.get("Ts"))
             tk.reset_output = self.commands_out.reset_output
+        if vehicle is not None:
+            vehicle.step(self.commands_out, s)
+            vehicle.odometry(self, stream=s)
         return self.commands_out
 
     @staticmethod

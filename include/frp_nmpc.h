@@ -605,6 +605,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * its own, part of this ABI version. */
 #include "frp_nmpc_fsm.h"
 
+/* ---- (12) the vehicle: a tracking plant for the command samples, and the odometry callbacks that close the loop ---- */
+/* S command samples flown by a controller and the planner's own dynamics, and NMPCManage's odometryCallback / odometryTransCallback
+ * (plan_manage/src/nmpc_manage.cpp:421-478) with a message producer, one launch each.  A header of its own, part of this ABI version. */
+#include "frp_nmpc_vehicle.h"
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 
