@@ -410,14 +410,21 @@ typedef struct frp_nmpc_reference {
 } frp_nmpc_reference;
 
 /* NMPCSolver::getCurTraj (nmpc_solver.cpp:109-142) + calculate_yaw (:834-862) for all stages of B planners.
- * Asynchronous on `stream`. */
+ * kino_size is clamped to [1, K].  A stage whose quotient (i Ts + time_offset) / Ts is <= -1, >= 2^31 - 1 or not finite (where the
+ * reference's unsigned index reads outside the path) gets the end of the path, for position and look-ahead; offsets in (-Ts, 0)
+ * truncate to sample 0 with a negative weight, as in the reference.  FRP_ERR_ARG before anything is launched for B <= 0, N outside
+ * [1, 64], K < 1, a NULL array other than kino_size / replan, a Ts that is not > 0 or a pi that is not > 3.  Asynchronous on `stream`. */
 int frp_nmpc_reference_batch(const frp_nmpc_reference *p, void *stream);
 
 /* The mode switch at the end of NMPCSolver::solveNMPC (nmpc_solver.cpp:436-447) for B planners: a planner whose
  * horizon runs past its kinodynamic path ((int)((N Ts + time_offset) / Ts) >= kino_size) or whose plan's last stage
  * is within `radius` (1.0 m) of the goal end_pt switches to the final solver -- mode[b] = FRP_MODEL_FINAL -- and stays
  * there until the caller resets it (a new path, :218).  kino_size: [1] or [B] (size_per_planner), end_pt: [3] or [B][3]
- * (end_per_planner).  mode feeds frp_nmpc_pack.mode and frp_nmpc_batch.model_per_problem.  Asynchronous on `stream`. */
+ * (end_per_planner).  mode feeds frp_nmpc_pack.mode and frp_nmpc_batch.model_per_problem.  Asynchronous on `stream`.
+ * A quotient outside int range: the conversion is the device's V_CVT_I32_F64 (here and in frp_nmpc_tick_end), which saturates: a
+ * quotient >= 2^31 (+inf included) gives INT_MAX, so the planner switches; a quotient <= -2^31 (-inf included) gives INT_MIN, so it
+ * does not switch by the index; NaN gives 0, so it switches by the index only for kino_size <= 0.  (The reference's x86 gives
+ * INT_MIN in all three cases.)  FRP_ERR_ARG before anything is launched for B <= 0, N < 1, a NULL array, or a Ts that is not > 0. */
 int frp_nmpc_mode_batch(int B, int N, const double *mpc_output, const double *time_offset, const int *kino_size,
                         int size_per_planner, const double *end_pt, int end_per_planner, double Ts, double radius,
                         int *mode, void *stream);

@@ -385,6 +385,18 @@ def test_widened_entry_points_reject_bad_arguments_before_touching_a_device():
     assert l.frp_nmpc_reference_batch(ctypes.byref(rf), None) == ERR           # no path
     rf.kino_path = 8; rf.Ts = 0.0
     assert l.frp_nmpc_reference_batch(ctypes.byref(rf), None) == ERR
+    rf.Ts = 0.05
+    for field, bad in (("Ts", 0.0), ("Ts", -0.05), ("Ts", float("nan")), ("pi", 3.0), ("pi", 2.9), ("pi", float("nan")), ("N", 0), ("N", 65), ("K", 0),
+                       ("B", 0), ("time_offset", None), ("mpc_output", None), ("ref_pos", None), ("ref_yaw", None)):
+        keep = getattr(rf, field)
+        setattr(rf, field, bad)
+        assert l.frp_nmpc_reference_batch(ctypes.byref(rf), None) == ERR, (field, bad)
+        setattr(rf, field, keep)
+    assert l.frp_nmpc_reference_batch(None, None) == ERR
+    mode_args = [4, 20, one, one, one, 0, one, 0, 0.05, 1.0, one, None]   # B, N, plan, time_offset, kino_size, per, end_pt, per, Ts, radius, mode, stream
+    for at, bad in ((8, 0.0), (8, -0.05), (8, float("nan")), (0, 0), (1, 0), (2, None), (3, None), (4, None), (6, None), (10, None)):
+        a = list(mode_args); a[at] = bad
+        assert l.frp_nmpc_mode_batch(*a) == ERR, (at, bad)
     assert l.frp_nmpc_coldstart_batch(4, 20, None, None, 7.3, None, None) == ERR
     d3, i3 = (ctypes.c_double * 3)(0, 0, 0), (ctypes.c_int * 3)(1 << 11, 1 << 11, 2)   # 2^23 cells > FRP_CORRIDOR_MAX_CELLS
     assert l.frp_nmpc_cloud_grid_build(one, 10, d3, 0.5, i3, one, one, one, one, None) == ERR
