@@ -15,6 +15,8 @@
 //     stay.  sqrt and the divisions are IEEE; asin, atan2 and ceil are ocml's.
 //   * Every index is b < B and s < S as the entry point checked them (B * S fits an int; offsets are formed in size_t).
 //   * Every store is a plain C++ store from a vector lane; no inline assembly.
+//   * frp_nmpc_vehicle_step_observed (frp_nmpc_estimator.h) is the same step kernel instantiated with one more store per sample, the
+//     clamped thrust; the instantiation frp_nmpc_vehicle_step launches is the kernel as it was (profiles/estimator_step_identity.txt).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
@@ -61,7 +63,10 @@ __device__ inline void rotation(const Quat &q, double R[9])
     R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
 }
 
-__global__ __launch_bounds__(THREADS) void step_kernel(frp_nmpc_vehicle c)
+// OBSERVED: frp_nmpc_vehicle_step_observed's instantiation (frp_nmpc_estimator.h) also stores the clamped thrust of every sample;
+// frp_nmpc_vehicle_step launches <false>, whose code has no such store (`thrust` is then not read).
+template <bool OBSERVED>
+__global__ __launch_bounds__(THREADS) void step_kernel(frp_nmpc_vehicle c, double *thrust)
 {
     const int b = blockIdx.x * THREADS + threadIdx.x;
     if (b >= c.B) return;
@@ -166,6 +171,7 @@ __global__ __launch_bounds__(THREADS) void step_kernel(frp_nmpc_vehicle c)
             for (int i = 0; i < NXV; i++) c.trace[((size_t)b * S + s) * NXV + i] = x[i];
         }
         if (c.sat) c.sat[(size_t)b * S + s] = sat;
+        if (OBSERVED) thrust[(size_t)b * S + s] = T;
     }
 #pragma unroll
     for (int i = 0; i < NXV; i++) c.x[(size_t)b * NXV + i] = x[i];
@@ -266,7 +272,8 @@ static unsigned blocks_for(int B) { return (unsigned)(((long long)B + THREADS - 
 
 extern "C" {
 
-int frp_nmpc_vehicle_step(const frp_nmpc_vehicle *v, void *stream)
+// the argument rules of frp_nmpc_vehicle_step and of frp_nmpc_vehicle_step_observed
+static int step_args(const frp_nmpc_vehicle *v)
 {
     using namespace frp::vehicle;
     if (!v || v->B < 1 || v->S < 1 || (long long)v->B * v->S > 0x7fffffffLL || v->n_sub < 1 || v->n_sub > FRP_VEHICLE_MAX_SUB) return FRP_ERR_ARG;
@@ -274,8 +281,25 @@ int frp_nmpc_vehicle_step(const frp_nmpc_vehicle *v, void *stream)
     for (int i = 0; i < 3; i++)
         if (!gain(v->kp[i]) || !gain(v->kv[i]) || !gain(v->ka[i])) return FRP_ERR_ARG;
     if (!v->x || !v->f_true || !v->cmd || !v->kind || !v->hold) return FRP_ERR_ARG;
+    return FRP_OK;
+}
+
+int frp_nmpc_vehicle_step(const frp_nmpc_vehicle *v, void *stream)
+{
+    using namespace frp::vehicle;
+    if (step_args(v) != FRP_OK) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(step_kernel, dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v);
+    hipLaunchKernelGGL(step_kernel<false>, dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, static_cast<double *>(nullptr));
+    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+}
+
+// frp_nmpc_estimator.h
+int frp_nmpc_vehicle_step_observed(const frp_nmpc_vehicle *v, double *thrust, void *stream)
+{
+    using namespace frp::vehicle;
+    if (step_args(v) != FRP_OK || !thrust) return FRP_ERR_ARG;
+    if (!device_ok()) return FRP_ERR_NO_DEVICE;
+    hipLaunchKernelGGL(step_kernel<true>, dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, thrust);
     return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
 }
 

@@ -196,6 +196,11 @@ class VehicleArgs(ctypes.Structure):  # frp_nmpc_vehicle (include/frp_nmpc_vehic
                [(n, ctypes.c_void_p) for n in ("x", "f_true", "cmd", "kind", "hold", "trace", "sat")]
 
 
+class EstimatorArgs(ctypes.Structure):  # frp_nmpc_estimator (include/frp_nmpc_estimator.h)
+    _fields_ = [("B", ctypes.c_int), ("S", ctypes.c_int), ("min_samples", ctypes.c_int), ("dt", ctypes.c_double), ("alpha", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("meas", "thrust", "f_hat", "y_prev", "count", "force", "fresh", "residual", "status")]
+
+
 class OccMapBody(ctypes.Structure):  # frp_nmpc_occmap_body (include/frp_nmpc_occmap_check.h)
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -278,6 +283,14 @@ VEHICLE_SAT_THRUST_LO, VEHICLE_SAT_THRUST_HI, VEHICLE_SAT_ROLL, VEHICLE_SAT_PITC
 # the controller's gains (no reference counterpart: the reference flies RotorS' controller) and what it is told; mass and g are the
 # plant's own (csrc/frp_model.hpp), dt_cmd the command timer's period
 VEHICLE_DEFAULTS = dict(kp=(6.0, 6.0, 8.0), kv=(4.0, 4.0, 5.0), ka=(10.0, 10.0, 4.0), mass=0.745319, g=9.81, dt_cmd=FSM_EXEC_PERIOD, n_sub=4)
+
+# the force estimator (include/frp_nmpc_estimator.h)
+ESTIMATOR_EXPORTS = ["frp_nmpc_vehicle_step_observed", "frp_nmpc_estimator_update", "frp_nmpc_estimator_reset"]
+EST_SKIPPED, EST_FIRST, EST_ABSORBED = 0, 1, 2  # FRP_EST_*: status[b][s]
+# CHOSEN, not derived (the reference has no estimator: its wrench comes from another node): a filter time constant of 0.1 s -- two of the
+# planner's 50 ms periods, alpha = 1 - exp(-0.01 / 0.1) = 0.095 per 100 Hz sample, a step of 1 m/s^2 passes ext_noise_bound = 0.5 after
+# 7 samples --, and an estimate that counts as fresh once 10 residuals (two periods) went into it
+ESTIMATOR_DEFAULTS = dict(tau=0.1, min_samples=10)
 
 
 def goal_search_table():
@@ -432,7 +445,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS + FSM_EXPORTS + VEHICLE_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS + FSM_EXPORTS + VEHICLE_EXPORTS + ESTIMATOR_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -481,6 +494,9 @@ def lib():
         l.frp_nmpc_vehicle_reset.argtypes = [ci, vp, vp, vp, vp, vp]
         l.frp_nmpc_vehicle_message.argtypes = [ci, ci, vp, vp, vp]
         l.frp_nmpc_vehicle_odometry.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]
+        l.frp_nmpc_vehicle_step_observed.argtypes = [ctypes.POINTER(VehicleArgs), vp, vp]
+        l.frp_nmpc_estimator_update.argtypes = [ctypes.POINTER(EstimatorArgs), vp]
+        l.frp_nmpc_estimator_reset.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp]
         _lib = l
     return _lib
 
@@ -2000,8 +2016,8 @@ class Vehicle:
     """The vehicle of every planner of a DeviceFleet, on the device (include/frp_nmpc_vehicle.h): a tracking plant that flies the command
     timer's samples and the reference's odometry callbacks, so that FleetFSM.period(..., vehicle=...) closes the loop without the host.
     Owns, all float64 device tensors unless noted: x [B,9] the plant state (position, world velocity, roll pitch yaw), hold [B,8] the last
-    published position and yaw, f_true [B,3] the TRUE mass-normalised external force (the caller writes it; what the planner is told stays
-    the caller's `force` / `force_fresh` of period()), msg [B,13] the last odometry message, state [B,9] what the callbacks made of it (the
+    published position and yaw, f_true [B,3] the TRUE mass-normalised external force (the caller writes it; what the planner is told is
+    the `force` / `force_fresh` of period(): the caller's own, or a ForceEstimator's), msg [B,13] the last odometry message, state [B,9] what the callbacks made of it (the
     `state` of period(), exec_step() and full_tick()), state_prev [B,9], fresh [B] int32 (ones: every planner hears every message), and
     with trace=True trace [B,S,9] / sat [B,S] int32 of the last step().
     kp, kv, ka, n_sub, mass, g, dt_cmd: VEHICLE_DEFAULTS -- the controller has no reference counterpart, the plant is the planner's own
@@ -2027,6 +2043,7 @@ class Vehicle:
         self.fresh = t.ones((self.B,), dtype=t.int32, device=dev)
         self.trace = t.zeros((self.B, self.S, VEHICLE_STATE), **f64) if trace else None
         self.sat = t.zeros((self.B, self.S), dtype=t.int32, device=dev) if trace else None
+        self.estimator = None   # a ForceEstimator attaches itself here: step() and reset() then feed and reset it
 
     def _stream(self, stream):
         return ctypes.c_void_p((stream if stream is not None else self.torch.cuda.current_stream(self.x.device)).cuda_stream)
@@ -2043,19 +2060,31 @@ class Vehicle:
         m = self._arg(mask, t.int32, (self.B,)) if mask is not None else None
         _check(lib().frp_nmpc_vehicle_reset(self.B, self._arg(x0, t.float64, (self.B, VEHICLE_STATE)), m, ctypes.c_void_p(self.x.data_ptr()),
                                             ctypes.c_void_p(self.hold.data_ptr()), self._stream(stream)), "frp_nmpc_vehicle_reset")
+        if self.estimator is not None:
+            self.estimator.reset(mask, stream)
 
     def step(self, commands, stream=None):
         """frp_nmpc_vehicle_step: the S samples of a Commands object (cmd [B,S,16], kind [B,S]) flown in order under f_true; x and hold
-        in place, trace / sat where the object was made with trace=True (S is then the constructor's)."""
+        in place, trace / sat where the object was made with trace=True (S is then the constructor's).
+        With a ForceEstimator attached (self.estimator): frp_nmpc_vehicle_step_observed instead -- the same flight, and the thrust of every
+        sample into the estimator's `thrust`, the trace into this object's own trace or else the estimator's `meas` --, then its update()."""
         t = self.torch
         S = int(commands.cmd.shape[1])
         if self.trace is not None and S != self.S:
             raise ValueError(f"this Vehicle traces S = {self.S} samples per call, the commands hold {S}")
+        est = self.estimator
+        if est is not None and S != est.S:
+            raise ValueError(f"the attached ForceEstimator takes S = {est.S} samples per call, the commands hold {S}")
+        trace = self.trace if self.trace is not None else est.meas if est is not None else None
         v = VehicleArgs(self.B, S, self.n_sub, self.mass, self.g, self.dt_cmd, (ctypes.c_double * 3)(*self.kp), (ctypes.c_double * 3)(*self.kv),
                         (ctypes.c_double * 3)(*self.ka), self.x.data_ptr(), self.f_true.data_ptr(),
                         self._arg(commands.cmd, t.float64, (self.B, S, COMMAND_STRIDE)).value, self._arg(commands.kind, t.int32, (self.B, S)).value,
-                        self.hold.data_ptr(), self.trace.data_ptr() if self.trace is not None else None, self.sat.data_ptr() if self.sat is not None else None)
-        _check(lib().frp_nmpc_vehicle_step(ctypes.byref(v), self._stream(stream)), "frp_nmpc_vehicle_step")
+                        self.hold.data_ptr(), trace.data_ptr() if trace is not None else None, self.sat.data_ptr() if self.sat is not None else None)
+        if est is None:
+            _check(lib().frp_nmpc_vehicle_step(ctypes.byref(v), self._stream(stream)), "frp_nmpc_vehicle_step")
+            return
+        _check(lib().frp_nmpc_vehicle_step_observed(ctypes.byref(v), ctypes.c_void_p(est.thrust.data_ptr()), self._stream(stream)), "frp_nmpc_vehicle_step_observed")
+        est.update(meas=trace, stream=stream)
 
     def message(self, stream=None):
         """frp_nmpc_vehicle_message: msg <- the odometry message of x for this object's odom_type."""
@@ -2074,6 +2103,64 @@ class Vehicle:
         _check(lib().frp_nmpc_vehicle_odometry(self.B, self.odom_type, self._arg(msg, t.float64, (self.B, VEHICLE_MSG_STRIDE)), self._arg(fresh, t.int32, (self.B,)),
                                                ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(self.state_prev.data_ptr()),
                                                self._arg(fsm.have_odom, t.int32, (self.B,)), self._stream(stream)), "frp_nmpc_vehicle_odometry")
+
+
+class ForceEstimator:
+    """The force estimator of every vehicle of a Vehicle, on the device (include/frp_nmpc_estimator.h): a velocity-residual observer on the
+    planner's own model that turns the thrust and the states of the samples a vehicle flew into the `force` / `force_fresh` pair of
+    FleetFSM.period -- what the planner is TOLD, where vehicle.f_true is what acts.  It has no reference counterpart (the reference
+    subscribes to a wrench another node publishes), and its measurements are the TRUE plant states of the vehicle's trace: noise is the
+    caller's to add (update(meas=...) takes any [B,S,9] tensor).
+    Attaches itself as vehicle.estimator: Vehicle.step then launches frp_nmpc_vehicle_step_observed and update(), Vehicle.reset resets
+    it under the same mask.  The loop closes through arguments period() already has:
+        fsm.period(planner, occmap, None, clock, force=est.force, force_fresh=est.fresh, vehicle=veh)
+    -- the force callback of period p hears the estimate the end of period p - 1 left.
+    Owns, float64 device tensors unless noted: meas [B,S,9] (the vehicle's trace where it keeps none of its own), thrust [B,S], f_hat [B,3],
+    y_prev [B,9], count [B] int32 (-1: no previous measurement), force [B,3], fresh [B] int32 and, with residual=True, residual [B,S,3] /
+    status [B,S] int32 (EST_*) of the last update().
+    tau, min_samples: ESTIMATOR_DEFAULTS -- CHOSEN, not derived, as VEHICLE_DEFAULTS' gains are: a first-order filter of time constant tau
+    on the residual, alpha = -expm1(-dt / tau) per sample with dt the vehicle's dt_cmd, computed here on the host; the estimate counts
+    as fresh after min_samples residuals."""
+
+    def __init__(self, vehicle, tau=None, min_samples=None, residual=False):
+        import math
+        t = vehicle.torch
+        dev = vehicle.x.device
+        k = dict(ESTIMATOR_DEFAULTS)
+        k.update({n: v for n, v in (("tau", tau), ("min_samples", min_samples)) if v is not None})
+        self.torch, self.vehicle, self.B, self.S = t, vehicle, vehicle.B, vehicle.S
+        self.tau, self.min_samples, self.dt = float(k["tau"]), int(k["min_samples"]), float(vehicle.dt_cmd)
+        if not (self.tau > 0.0 and math.isfinite(self.tau)) or self.min_samples < 1:
+            raise ValueError("ForceEstimator: tau finite and > 0, min_samples >= 1")
+        self.alpha = -math.expm1(-self.dt / self.tau)
+        f64 = dict(dtype=t.float64, device=dev)
+        i32 = dict(dtype=t.int32, device=dev)
+        self.meas, self.thrust = t.zeros((self.B, self.S, VEHICLE_STATE), **f64), t.zeros((self.B, self.S), **f64)
+        self.f_hat, self.y_prev, self.force = t.zeros((self.B, 3), **f64), t.zeros((self.B, VEHICLE_STATE), **f64), t.zeros((self.B, 3), **f64)
+        self.count, self.fresh = t.full((self.B,), -1, **i32), t.zeros((self.B,), **i32)
+        self.residual = t.zeros((self.B, self.S, 3), **f64) if residual else None
+        self.status = t.zeros((self.B, self.S), **i32) if residual else None
+        vehicle.estimator = self
+
+    def update(self, meas=None, thrust=None, stream=None):
+        """frp_nmpc_estimator_update: the S samples of meas [B,S,9] / thrust [B,S] (None: this object's own) absorbed in order; f_hat,
+        y_prev and count in place, force and fresh written."""
+        t, v = self.torch, self.vehicle
+        meas = self.meas if meas is None else meas
+        thrust = self.thrust if thrust is None else thrust
+        p = lambda a: a.data_ptr() if a is not None else None
+        e = EstimatorArgs(self.B, self.S, self.min_samples, self.dt, self.alpha, v._arg(meas, t.float64, (self.B, self.S, VEHICLE_STATE)).value,
+                          v._arg(thrust, t.float64, (self.B, self.S)).value, p(self.f_hat), p(self.y_prev), p(self.count), p(self.force), p(self.fresh),
+                          p(self.residual), p(self.status))
+        _check(lib().frp_nmpc_estimator_update(ctypes.byref(e), v._stream(stream)), "frp_nmpc_estimator_update")
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_estimator_reset: where mask [B] int32 != 0 (None: everywhere) f_hat <- 0, count <- -1, force <- 0, fresh <- 0."""
+        t, v = self.torch, self.vehicle
+        m = v._arg(mask, t.int32, (self.B,)) if mask is not None else None
+        vp = lambda a: ctypes.c_void_p(a.data_ptr())
+        _check(lib().frp_nmpc_estimator_reset(self.B, m, vp(self.f_hat), vp(self.y_prev), vp(self.count), vp(self.force), vp(self.fresh), v._stream(stream)),
+               "frp_nmpc_estimator_reset")
 
 
 class FleetFSM:

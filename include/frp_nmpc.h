@@ -617,6 +617,12 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * (plan_manage/src/nmpc_manage.cpp:421-478) with a message producer, one launch each.  A header of its own, part of this ABI version. */
 #include "frp_nmpc_vehicle.h"
 
+/* ---- (13) the force estimator: what the planner is told about the external force, from what the vehicle flew ---- */
+/* A velocity-residual observer on the planner's own dynamics, fed by the thrust and the states of the vehicle's samples, writing the
+ * force / fresh pair of frp_nmpc_fsm_force; no counterpart in the reference (its wrench comes from another node).  One launch each.  A
+ * header of its own, part of this ABI version. */
+#include "frp_nmpc_estimator.h"
+
 const char *frp_nmpc_version(void);
 int frp_nmpc_device_count(void);
 
