@@ -256,6 +256,14 @@ CHECK_EXPORTS = ["frp_nmpc_occmap_check_surround", "frp_nmpc_occmap_check_paths"
 OCCMAP_BODY = (0.27, 0.0425)  # occ_map/ego_r, ego_h of the reference's launch file
 SAFETY_INFLATE_CHECK, SAFETY_INFLATE_SEARCH = 1.2, 1.5  # checkReplanCallback's two ratios (nmpc_manage.cpp:291, :308, :333)
 
+# section (8)'s distance header (include/frp_nmpc_occmap_distance.h): the truncated distance field and the clearance queries, checked at
+# load time like EXPORTS.  No reference counterpart: the reference's map keeps no distance
+DISTANCE_EXPORTS = ["frp_nmpc_occmap_distance_scratch_bytes", "frp_nmpc_occmap_distance_update", "frp_nmpc_occmap_clearance",
+                    "frp_nmpc_occmap_clearance_trace", "frp_nmpc_occmap_clearance_reset"]
+OCCMAP_DIST_FAR, OCCMAP_DIST_MAX_R = 65535, 64  # FRP_OCCMAP_DIST_FAR, FRP_OCCMAP_DIST_MAX_R
+# CHOSEN, not derived: a radius of 20 voxels is 2 m at the reference's 0.1 m resolution -- beyond it a clearance reads +inf
+OCCMAP_DIST_DEFAULT_R = 20
+
 
 # the command timer (include/frp_nmpc_command.h)
 COMMAND_EXPORTS = ["frp_nmpc_command_snapshot", "frp_nmpc_command_batch"]
@@ -445,7 +453,7 @@ def lib():
         l.frp_nmpc_astar_workspace_bytes.restype = ctypes.c_size_t
         l.frp_nmpc_astar_workspace_bytes.argtypes = [ctypes.POINTER(Astar)]
         l.frp_nmpc_astar_batch.argtypes = [ctypes.POINTER(Astar), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS + FSM_EXPORTS + VEHICLE_EXPORTS + ESTIMATOR_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
+        for name in EXPORTS + FUSE_EXPORTS + FUSE_BATCH_EXPORTS + FUSE_POINTS_EXPORTS + CHECK_EXPORTS + DISTANCE_EXPORTS + RENDER_EXPORTS + RENDER_SCAN_EXPORTS + VIEW_EXPORTS + LARGE_EXPORTS + COMMAND_EXPORTS + OUTCOME_EXPORTS + FSM_EXPORTS + VEHICLE_EXPORTS + ESTIMATOR_EXPORTS:  # a library without one of them is not this header's library: no call is ever skipped for a missing kernel
             if not hasattr(l, name):
                 raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
         pm, vp, sz = ctypes.POINTER(OccMap), ctypes.c_void_p, ctypes.c_size_t
@@ -479,6 +487,12 @@ def lib():
         l.frp_nmpc_occmap_check_surround.argtypes = [pm, pb, cd, ci, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_paths.argtypes = [pm, pb, cd, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]
         l.frp_nmpc_occmap_check_goals.argtypes = [pm, pb, cd, cd, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, sz, vp]
+        l.frp_nmpc_occmap_distance_scratch_bytes.restype = ctypes.c_size_t
+        l.frp_nmpc_occmap_distance_scratch_bytes.argtypes = [pm, ci]
+        l.frp_nmpc_occmap_distance_update.argtypes = [pm, ci, ci, vp, vp, sz, vp, sz, vp]
+        l.frp_nmpc_occmap_clearance.argtypes = [pm, vp, ci, ci, vp, vp, vp, vp]
+        l.frp_nmpc_occmap_clearance_trace.argtypes = [pm, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        l.frp_nmpc_occmap_clearance_reset.argtypes = [ci, vp, vp, vp, vp, vp]
         l.frp_nmpc_command_snapshot.argtypes = [ci, ci, vp, vp, vp, vp, vp]
         l.frp_nmpc_command_batch.argtypes = [ctypes.POINTER(Command), vp]
         l.frp_nmpc_tick_begin.argtypes = [ctypes.POINTER(Tick), vp, vp]
@@ -1474,6 +1488,108 @@ class OccupancyMap:
                 if a is not None:
                     a.record_stream(stream)
         return out
+
+    def distance_field(self, R=OCCMAP_DIST_DEFAULT_R, border=True):
+        """A DistanceField of this map (include/frp_nmpc_occmap_distance.h), built once from the bit plane as it is now.  R: the radius in
+        voxels, 1 ... OCCMAP_DIST_MAX_R; the default of 20 is 2 m at the reference's 0.1 m resolution -- CHOSEN, not derived.  border:
+        voxels outside the map count as occupied (checkPosSurround's reading)."""
+        return DistanceField(self, R, border)
+
+
+class DistanceField:
+    """The truncated distance field of an OccupancyMap, on the device (include/frp_nmpc_occmap_distance.h): field [gx, gy, gz] uint16, the
+    exact integer squared distance in voxels from each voxel to the nearest occupied one where that is <= R * R, else OCCMAP_DIST_FAR;
+    with border=True the voxels outside the map count as occupied.  It has no reference counterpart (the reference's map keeps no
+    distance).  Owns `field` and the scratch of the three passes; update() rebuilds from the map's CURRENT bit plane -- the field does
+    not follow the map by itself.  clearance(pos) is resolution * sqrt(field) at the positions' voxels: a distance between voxel
+    CENTRES (the header says what that bounds), +inf beyond R, 0.0 inside an occupied voxel, outside the map or for a position that is
+    not finite."""
+
+    def __init__(self, occmap, R=OCCMAP_DIST_DEFAULT_R, border=True):
+        t = occmap.torch
+        self.torch, self.occmap, self.R, self.border = t, occmap, int(R), bool(border)
+        if not 1 <= self.R <= OCCMAP_DIST_MAX_R:
+            raise ValueError(f"DistanceField: R is 1 ... {OCCMAP_DIST_MAX_R} voxels")
+        m = occmap._map()
+        self.scratch_bytes = int(lib().frp_nmpc_occmap_distance_scratch_bytes(ctypes.byref(m), self.R))
+        if self.scratch_bytes == 0:
+            raise ValueError("frp_nmpc_occmap_distance refuses this map description")
+        self.field = t.empty(occmap.grid, dtype=t.uint16, device=occmap.device)
+        self.scratch = t.empty((self.scratch_bytes,), dtype=t.uint8, device=occmap.device)
+        self.update()
+
+    def _stream(self, stream):
+        return ctypes.c_void_p((stream if stream is not None else self.torch.cuda.current_stream(self.field.device)).cuda_stream)
+
+    def update(self, stream=None):
+        """frp_nmpc_occmap_distance_update: field <- the definition on the map's bit plane as the stream finds it (three launches)."""
+        o = self.occmap
+        m = o._map()
+        _check(lib().frp_nmpc_occmap_distance_update(ctypes.byref(m), self.R, int(self.border), ctypes.c_void_p(self.field.data_ptr()),
+                                                     ctypes.c_void_p(self.scratch.data_ptr()), self.scratch_bytes, ctypes.c_void_p(o.ws.data_ptr()), o.ws_bytes,
+                                                     self._stream(stream)), "frp_nmpc_occmap_distance_update")
+
+    def clearance(self, pos, d2=False, stream=None):
+        """frp_nmpc_occmap_clearance of pos [Q,3] (float64 device tensor, or an array that is uploaded): float64 [Q] device tensor; with
+        d2=True (clear, d2) with d2 int32 [Q]: the field's integer, OCCMAP_DIST_FAR included, -1 outside the map."""
+        t, o = self.torch, self.occmap
+        q = o._dev(pos, t.float64)
+        Q = int(q.shape[0])
+        assert tuple(q.shape) == (Q, 3)
+        clear = t.zeros((Q,), dtype=t.float64, device=o.device)
+        sq = t.zeros((Q,), dtype=t.int32, device=o.device) if d2 else None
+        m = o._map()
+        _check(lib().frp_nmpc_occmap_clearance(ctypes.byref(m), ctypes.c_void_p(self.field.data_ptr()), self.R, Q, q.data_ptr() if Q else None,
+                                               clear.data_ptr() if Q else None, sq.data_ptr() if d2 and Q else None, self._stream(stream)),
+               "frp_nmpc_occmap_clearance")
+        o._record(stream, q, clear, sq)
+        return (clear, sq) if d2 else clear
+
+
+class FlightClearance:
+    """How close every vehicle of a Vehicle came to an obstacle, on the device (frp_nmpc_occmap_clearance_trace): min_clear [B] float64
+    (+inf until something nearer than the field's radius was seen), hits [B] int32 (samples with clearance 0.0: inside an occupied
+    voxel, outside the map or not finite) and samples [B] int32.  It hooks into nothing: the caller launches update() after
+    Vehicle.step / FleetFSM.period(..., vehicle=...), inside the same captured graph if they wish.  The positions are the TRUE plant
+    states of the vehicle's trace, and the numbers are distances between voxel centres (include/frp_nmpc_occmap_distance.h); the
+    body's radius is the caller's to subtract.  Tracking error and the rest of a flight record are not kept."""
+
+    def __init__(self, vehicle, field):
+        t = vehicle.torch
+        dev = vehicle.x.device
+        if field.field.device != dev:
+            raise ValueError("FlightClearance: the vehicle and the distance field are on different devices")
+        self.torch, self.vehicle, self.field, self.B = t, vehicle, field, vehicle.B
+        self.min_clear = t.full((self.B,), float("inf"), dtype=t.float64, device=dev)
+        self.hits, self.samples = t.zeros((self.B,), dtype=t.int32, device=dev), t.zeros((self.B,), dtype=t.int32, device=dev)
+
+    def update(self, trace=None, active=None, stream=None):
+        """The S samples of trace [B,S,stride >= 3] (float64; None: vehicle.trace, or else the attached estimator's meas -- the fallback
+        Vehicle.step writes to) taken in order into min_clear, hits and samples; active [B] int32 or None: where it is 0 nothing of
+        that vehicle changes."""
+        t, v = self.torch, self.vehicle
+        if trace is None:
+            trace = v.trace if v.trace is not None else v.estimator.meas if v.estimator is not None else None
+            if trace is None:
+                raise ValueError("FlightClearance.update: this Vehicle keeps no trace (trace=True) and has no ForceEstimator attached; pass trace=")
+        assert t.is_tensor(trace) and trace.dim() == 3, "trace is a [B, S, stride] tensor"
+        S, stride = int(trace.shape[1]), int(trace.shape[2])
+        if S < 1 or stride < 3:
+            raise ValueError("FlightClearance.update: trace is [B, S >= 1, stride >= 3]")
+        a = v._arg(active, t.int32, (self.B,)) if active is not None else None
+        f = self.field
+        m = f.occmap._map()
+        _check(lib().frp_nmpc_occmap_clearance_trace(ctypes.byref(m), ctypes.c_void_p(f.field.data_ptr()), f.R, self.B, S, stride,
+                                                     v._arg(trace, t.float64, (self.B, S, stride)), a, ctypes.c_void_p(self.min_clear.data_ptr()),
+                                                     ctypes.c_void_p(self.hits.data_ptr()), ctypes.c_void_p(self.samples.data_ptr()), v._stream(stream)),
+               "frp_nmpc_occmap_clearance_trace")
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_occmap_clearance_reset: where mask [B] int32 != 0 (None: everywhere) min_clear <- +inf, hits <- 0, samples <- 0."""
+        t, v = self.torch, self.vehicle
+        m = v._arg(mask, t.int32, (self.B,)) if mask is not None else None
+        _check(lib().frp_nmpc_occmap_clearance_reset(self.B, m, ctypes.c_void_p(self.min_clear.data_ptr()), ctypes.c_void_p(self.hits.data_ptr()),
+                                                     ctypes.c_void_p(self.samples.data_ptr()), v._stream(stream)), "frp_nmpc_occmap_clearance_reset")
 
 
 class AstarPlanner:

@@ -597,6 +597,11 @@ int frp_nmpc_occmap_query(const frp_nmpc_occmap *map, int Q, const double *pos, 
  * points, beside the entries above, which keep their limit.  A header of its own, part of this section and of this ABI version. */
 #include "frp_nmpc_corridor_large.h"
 
+/* The truncated distance field of the bit plane (exact integer squared distances to the nearest occupied voxel within a radius) and
+ * the clearance of positions and of vehicle traces on it.  No counterpart in the reference (its map keeps no distance).  A header of
+ * its own, part of this section and of this ABI version. */
+#include "frp_nmpc_occmap_distance.h"
+
 /* ---- (9) the command timer: every planner's 100 Hz setpoints from its last accepted plan ---- */
 /* NMPCSolver::cmdTrajCallback (plan_manage/src/nmpc_solver.cpp:865-987) for S consecutive callbacks of B planners in one launch, and
  * the snapshot pre_mpc_output_ = mpc_output_ (:527-528) it samples.  A header of its own, part of this ABI version. */
