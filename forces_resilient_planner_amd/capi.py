@@ -1,0 +1,411 @@
+"""The C-ABI of include/*.h (libfrp_nmpc_amd.so), declared once: the ctypes mirrors of its structs (C_TYPES names each one's C type and
+header), the mirrored macros (MACROS), every function's signature (SIGNATURES), the loader and the helpers that turn tensors and streams
+into the pointers the calls take.  Nothing here knows what a call is for; tests/test_capi_table_cpu.py holds all of it to the headers.
+"""
+import ctypes
+import os
+
+_PKG = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("FRP_LIB") or os.path.join(_PKG, "libfrp_nmpc_amd.so")  # FRP_LIB: an experiment build (tools/build_variant.sh)
+
+c_double_p = ctypes.POINTER(ctypes.c_double)
+c_int_p = ctypes.POINTER(ctypes.c_int)
+
+
+class Options(ctypes.Structure):
+    _fields_ = [("maxit", ctypes.c_int), ("tol_stat", ctypes.c_double), ("tol_eq", ctypes.c_double),
+                ("tol_ineq", ctypes.c_double), ("tol_comp", ctypes.c_double), ("mu0", ctypes.c_double),
+                ("ftb", ctypes.c_double), ("hessian", ctypes.c_int), ("diverge_mu", ctypes.c_double), ("twist", ctypes.c_int),
+                ("timeout", ctypes.c_double)]  # seconds of wall clock per scope, 0 = no budget (frp_nmpc_options.timeout)
+
+
+class Batch(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("M", ctypes.c_int), ("MF", ctypes.c_int),
+                ("model", ctypes.c_int),
+                ("xinit", ctypes.c_void_p), ("x0", ctypes.c_void_p), ("params", ctypes.c_void_p),
+                ("nfaces", ctypes.c_void_p), ("z", ctypes.c_void_p), ("exitflag", ctypes.c_void_p),
+                ("iters", ctypes.c_void_p), ("info", ctypes.c_void_p), ("model_per_problem", ctypes.c_void_p),
+                ("order_hint", ctypes.c_void_p)]
+
+
+class Pack(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("M", ctypes.c_int), ("NPOLY", ctypes.c_int), ("F", ctypes.c_int),
+                ("external_acc_per_stage", ctypes.c_int), ("mpc_output", ctypes.c_void_p), ("external_acc", ctypes.c_void_p), ("ref_pos", ctypes.c_void_p),
+                ("ref_yaw", ctypes.c_void_p), ("ellipsoid", ctypes.c_void_p), ("poly_A", ctypes.c_void_p),
+                ("poly_b", ctypes.c_void_p), ("poly_nfaces", ctypes.c_void_p), ("poly_index", ctypes.c_void_p),
+                ("w_stage_wp", ctypes.c_double), ("w_stage_input", ctypes.c_double), ("w_input_rate", ctypes.c_double),
+                ("w_terminal_wp", ctypes.c_double), ("w_terminal_input", ctypes.c_double),
+                ("xinit", ctypes.c_void_p), ("x0", ctypes.c_void_p), ("params", ctypes.c_void_p), ("nfaces", ctypes.c_void_p),
+                ("mode", ctypes.c_void_p), ("wf_stage_wp", ctypes.c_double), ("wf_stage_input", ctypes.c_double),
+                ("wf_input_rate", ctypes.c_double), ("wf_terminal_wp", ctypes.c_double), ("wf_terminal_input", ctypes.c_double),
+                ("padded_rows_are_zero", ctypes.c_int)]
+
+
+class Tube(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("mpc_output", ctypes.c_void_p),
+                ("mass", ctypes.c_double), ("drag", ctypes.c_double), ("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double),
+                ("noise", ctypes.c_double * 3), ("epsilon", ctypes.c_double), ("Ts", ctypes.c_double),
+                ("ellipsoid", ctypes.c_void_p)]
+
+
+class Corridor(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("F", ctypes.c_int), ("P", ctypes.c_int),
+                ("cloud", ctypes.c_void_p), ("cloud_per_planner", ctypes.c_int), ("cloud_count", ctypes.c_void_p),
+                ("ref_pos", ctypes.c_void_p), ("ref_yaw", ctypes.c_void_p), ("ellipsoid", ctypes.c_void_p),
+                ("bbox", ctypes.c_double * 3), ("seed_len", ctypes.c_double), ("inflation", ctypes.c_double),
+                ("offset_x", ctypes.c_double),
+                ("poly_A", ctypes.c_void_p), ("poly_b", ctypes.c_void_p), ("poly_nfaces", ctypes.c_void_p),
+                ("poly_index", ctypes.c_void_p), ("poly_count", ctypes.c_void_p),
+                ("grid_origin", ctypes.c_double * 3), ("grid_cell", ctypes.c_double), ("grid_dims", ctypes.c_int * 3),
+                ("grid_points", ctypes.c_void_p), ("grid_index", ctypes.c_void_p), ("grid_start", ctypes.c_void_p)]
+
+
+class CorridorCut(ctypes.Structure):  # the tensor behind .box is kept alive on ._box
+    _fields_ = [("box", ctypes.c_void_p), ("origin", ctypes.c_double * 3), ("resolution", ctypes.c_double)]
+
+
+class Reference(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("kino_path", ctypes.c_void_p),
+                ("path_per_planner", ctypes.c_int), ("kino_size", ctypes.c_void_p), ("time_offset", ctypes.c_void_p),
+                ("mpc_output", ctypes.c_void_p), ("Ts", ctypes.c_double), ("pi", ctypes.c_double),
+                ("ref_pos", ctypes.c_void_p), ("ref_yaw", ctypes.c_void_p), ("replan", ctypes.c_void_p)]
+
+
+class Astar(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("occ", ctypes.c_void_p), ("grid", ctypes.c_int * 3), ("origin", ctypes.c_double * 3),
+                ("map_size", ctypes.c_double * 3), ("resolution", ctypes.c_double), ("local_box", ctypes.c_void_p),
+                ("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double),
+                ("max_tau", ctypes.c_double), ("init_max_tau", ctypes.c_double), ("max_vel", ctypes.c_double), ("max_acc", ctypes.c_double),
+                ("w_time", ctypes.c_double), ("horizon", ctypes.c_double), ("lambda_heu", ctypes.c_double), ("tie_breaker", ctypes.c_double),
+                ("allocate_num", ctypes.c_int), ("check_num", ctypes.c_int),
+                ("start_pt", ctypes.c_void_p), ("start_vel", ctypes.c_void_p), ("start_acc", ctypes.c_void_p), ("end_pt", ctypes.c_void_p),
+                ("end_vel", ctypes.c_void_p), ("external_acc", ctypes.c_void_p), ("active", ctypes.c_void_p), ("init_search", ctypes.c_int),
+                ("Ts", ctypes.c_double), ("K", ctypes.c_int),
+                ("kino_path", ctypes.c_void_p), ("kino_size", ctypes.c_void_p), ("status", ctypes.c_void_p), ("stats", ctypes.c_void_p),
+                ("path_nodes", ctypes.c_void_p), ("retry_pt", ctypes.c_void_p), ("retry_vel", ctypes.c_void_p)]
+
+
+class OccMap(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_double * 3), ("map_size", ctypes.c_double * 3), ("resolution", ctypes.c_double), ("grid", ctypes.c_int * 3),
+                ("clamp_min_log", ctypes.c_double), ("clamp_max_log", ctypes.c_double), ("min_occupancy_log", ctypes.c_double),
+                ("local_radius", ctypes.c_double * 3), ("log_odds", ctypes.c_void_p), ("occ", ctypes.c_void_p)]
+
+
+class OccMapView(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("centre", ctypes.c_void_p), ("P", ctypes.c_int), ("local_box", ctypes.c_void_p),
+                ("cloud", ctypes.c_void_p), ("cloud_count", ctypes.c_void_p)]
+
+
+class OccMapFuse(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int), ("cols", ctypes.c_int), ("depth", ctypes.c_void_p), ("last_depth", ctypes.c_void_p),
+                ("last_T_wc", ctypes.c_double * 16), ("K", ctypes.c_double * 9), ("T_wc", ctypes.c_double * 16),
+                ("depth_scale", ctypes.c_double), ("depth_filter_mindist", ctypes.c_double), ("depth_filter_tolerance", ctypes.c_double),
+                ("depth_filter_margin", ctypes.c_int), ("skip_pixel", ctypes.c_int),
+                ("prob_hit_log", ctypes.c_double), ("prob_miss_log", ctypes.c_double),
+                ("min_ray_length", ctypes.c_double), ("max_ray_length", ctypes.c_double),
+                ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
+
+
+class OccMapFuseBatch(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int), ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("depth", ctypes.c_void_p), ("last_depth", ctypes.c_void_p),
+                ("T_wc", ctypes.c_void_p), ("last_T_wc", ctypes.c_void_p), ("active", ctypes.c_void_p), ("K", ctypes.c_double * 9),
+                ("depth_scale", ctypes.c_double), ("depth_filter_mindist", ctypes.c_double), ("depth_filter_tolerance", ctypes.c_double),
+                ("depth_filter_margin", ctypes.c_int), ("skip_pixel", ctypes.c_int),
+                ("prob_hit_log", ctypes.c_double), ("prob_miss_log", ctypes.c_double),
+                ("min_ray_length", ctypes.c_double), ("max_ray_length", ctypes.c_double),
+                ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
+
+
+class OccMapFusePoints(ctypes.Structure):
+    _fields_ = [("scans", ctypes.c_int), ("P", ctypes.c_int), ("points", ctypes.c_void_p), ("points_f32", ctypes.c_void_p),
+                ("count", ctypes.c_void_p), ("origin", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("prob_hit_log", ctypes.c_double), ("prob_miss_log", ctypes.c_double),
+                ("min_ray_length", ctypes.c_double), ("max_ray_length", ctypes.c_double),
+                ("max_rounds", ctypes.c_int), ("status", ctypes.c_void_p)]
+
+
+class OccMapRender(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int), ("rows", ctypes.c_int), ("cols", ctypes.c_int), ("T_wc", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("K", ctypes.c_double * 9), ("depth_scale", ctypes.c_double), ("max_range", ctypes.c_double),
+                ("depth", ctypes.c_void_p), ("voxel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class OccMapRenderScan(ctypes.Structure):
+    _fields_ = [("scans", ctypes.c_int), ("P", ctypes.c_int), ("beams", ctypes.c_void_p), ("T_ws", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("min_range", ctypes.c_double), ("max_range", ctypes.c_double), ("far_range", ctypes.c_double),
+                ("points", ctypes.c_void_p), ("points_f32", ctypes.c_void_p), ("origin", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("range", ctypes.c_void_p), ("voxel", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class OccMapSharedView(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_int), ("cell", ctypes.c_double), ("dims", ctypes.c_int * 3),
+                ("cloud", ctypes.c_void_p), ("count", ctypes.c_void_p), ("total", ctypes.c_void_p),
+                ("grid_points", ctypes.c_void_p), ("grid_index", ctypes.c_void_p), ("grid_start", ctypes.c_void_p),
+                ("cursor", ctypes.c_void_p), ("group_sums", ctypes.c_void_p)]
+
+
+class CorridorLarge(ctypes.Structure):
+    _fields_ = [("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("overflow", ctypes.c_void_p)]
+
+
+class Command(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("S", ctypes.c_int), ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("g", ctypes.c_double),
+                ("pre_plan", ctypes.c_void_p), ("t_cur", ctypes.c_void_p), ("status", ctypes.c_void_p), ("have_traj", ctypes.c_void_p),
+                ("pub_end", ctypes.c_void_p), ("end_pt", ctypes.c_void_p), ("odom", ctypes.c_void_p), ("init_yaw", ctypes.c_void_p),
+                ("t_yaw", ctypes.c_void_p), ("cmd", ctypes.c_void_p), ("kind", ctypes.c_void_p), ("finish", ctypes.c_void_p),
+                ("reset_output", ctypes.c_void_p)]
+
+
+class Tick(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in ("fail_count", "replan_count", "kino_replan", "exit_code", "initialized", "cmd_status",
+                                                                        "pub_end", "cmd_end_pt", "exec_mpc", "gate", "keep", "accept", "result", "replan")]
+
+
+class TickIn(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int), ("K", ctypes.c_int), ("Ts", ctypes.c_double), ("z", ctypes.c_void_p), ("exitflag", ctypes.c_void_p),
+                ("mpc_output", ctypes.c_void_p), ("state", ctypes.c_void_p), ("end_pt", ctypes.c_void_p), ("end_per_planner", ctypes.c_int),
+                ("kino_path", ctypes.c_void_p), ("path_per_planner", ctypes.c_int), ("kino_size", ctypes.c_void_p), ("size_per_planner", ctypes.c_int),
+                ("time_offset", ctypes.c_void_p), ("ref_replan", ctypes.c_void_p), ("mode", ctypes.c_void_p)]
+
+
+class Fsm(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in ("state", "have_odom", "have_target", "have_traj", "trigger", "call_init_yaw",
+                                                                        "consider_force", "replan_force_surpass", "surpass_count", "plan_fail_count",
+                                                                        "exec_mpc", "cmd_status", "pub_end", "end_pt", "external_acc", "last_external_acc",
+                                                                        "init_yaw", "yaw_odom", "change_yaw_time", "kino_start_time", "mode")]
+
+
+class FsmExecIn(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int), ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("g", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("state", "pre_plan", "exit_code", "t_cur", "now", "search", "start_pt", "start_vel", "start_acc",
+                                               "retry_pt", "retry_vel")]
+
+
+class VehicleArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("S", ctypes.c_int), ("n_sub", ctypes.c_int), ("mass", ctypes.c_double), ("g", ctypes.c_double), ("dt_cmd", ctypes.c_double),
+                ("kp", ctypes.c_double * 3), ("kv", ctypes.c_double * 3), ("ka", ctypes.c_double * 3)] + \
+               [(n, ctypes.c_void_p) for n in ("x", "f_true", "cmd", "kind", "hold", "trace", "sat")]
+
+
+class EstimatorArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("S", ctypes.c_int), ("min_samples", ctypes.c_int), ("dt", ctypes.c_double), ("alpha", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("meas", "thrust", "f_hat", "y_prev", "count", "force", "fresh", "residual", "status")]
+
+
+class OccMapBody(ctypes.Structure):
+    _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
+
+
+class ForcesParams(ctypes.Structure):
+    _fields_ = [("xinit", ctypes.c_double * 9), ("x0", ctypes.c_double * 340),
+                ("all_parameters", ctypes.c_double * 2600), ("num_of_threads", ctypes.c_uint)]
+
+
+class ForcesOutput(ctypes.Structure):
+    _fields_ = [("x", (ctypes.c_double * 17) * 20)]
+
+
+class ForcesInfo(ctypes.Structure):
+    _fields_ = [("it", ctypes.c_int), ("it2opt", ctypes.c_int)] + \
+               [(n, ctypes.c_double) for n in "res_eq res_ineq rsnorm rcompnorm pobj dobj dgap rdgap mu mu_aff sigma".split()] + \
+               [("lsit_aff", ctypes.c_int), ("lsit_cc", ctypes.c_int)] + \
+               [(n, ctypes.c_double) for n in "step_aff step_cc solvetime fevalstime".split()]
+
+
+EXTFUNC = ctypes.CFUNCTYPE(None, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                           c_double_p, c_double_p, c_double_p, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int)
+
+# every mirror above, by the header that defines it: its C type
+C_TYPES = {cls: (ctype, header) for header, group in {
+    "frp_nmpc.h": {Options: "frp_nmpc_options", Batch: "frp_nmpc_batch", Pack: "frp_nmpc_pack", Tube: "frp_nmpc_tube", Corridor: "frp_nmpc_corridor",
+                   CorridorCut: "frp_nmpc_corridor_cut", Reference: "frp_nmpc_reference", Astar: "frp_nmpc_astar", OccMap: "frp_nmpc_occmap",
+                   OccMapView: "frp_nmpc_occmap_view", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
+    "frp_nmpc_occmap_fuse.h": {OccMapFuse: "frp_nmpc_occmap_fuse"}, "frp_nmpc_occmap_fuse_batch.h": {OccMapFuseBatch: "frp_nmpc_occmap_fuse_batch"},
+    "frp_nmpc_occmap_fuse_points.h": {OccMapFusePoints: "frp_nmpc_occmap_fuse_points"}, "frp_nmpc_occmap_check.h": {OccMapBody: "frp_nmpc_occmap_body"},
+    "frp_nmpc_occmap_render.h": {OccMapRender: "frp_nmpc_occmap_render"}, "frp_nmpc_occmap_render_scan.h": {OccMapRenderScan: "frp_nmpc_occmap_render_scan"},
+    "frp_nmpc_occmap_view.h": {OccMapSharedView: "frp_nmpc_occmap_shared_view"}, "frp_nmpc_corridor_large.h": {CorridorLarge: "frp_nmpc_corridor_large"},
+    "frp_nmpc_command.h": {Command: "frp_nmpc_command"}, "frp_nmpc_outcome.h": {Tick: "frp_nmpc_tick", TickIn: "frp_nmpc_tick_in"},
+    "frp_nmpc_fsm.h": {Fsm: "frp_nmpc_fsm", FsmExecIn: "frp_nmpc_fsm_exec_in"}, "frp_nmpc_vehicle.h": {VehicleArgs: "frp_nmpc_vehicle"},
+    "frp_nmpc_estimator.h": {EstimatorArgs: "frp_nmpc_estimator"}}.items() for cls, ctype in group.items()}
+
+# ---- the mirrored macros, and nothing else down to MACROS: it takes every integer constant the module holds at that line ----
+INFO_STRIDE, ABI_VERSION = 12, 7
+FRP_ERR_NO_DEVICE, FRP_ERR_ARG = -1001, -1003
+ASTAR_MAX_PATH, ASTAR_REACH_HORIZON, ASTAR_REACH_END, ASTAR_NO_PATH, ASTAR_REACH_END_BUT_SHOT_FAILS = 256, 1, 2, 3, 4
+CORRIDOR_MAX_F, CORRIDOR_MAX_POINTS, CORRIDOR_MAX_CELLS = 64, 65536, 1 << 22
+OCCMAP_FUSE_DEFAULT_ROUNDS, OCCMAP_FUSE_MAX_FRAMES, OCCMAP_FUSE_POINTS_MAX_SCANS = 128, 64, 64
+OCCMAP_FUSE_REFUSED = -256      # status[f][0] of a frame whose pose the device refuses
+OCCMAP_VIEW_MAX_GROUPS, OCCMAP_VIEW_LAUNCHES = 1024, 5
+CORRIDOR_LARGE_MAX_POINTS, CORRIDOR_LARGE_LIST, CORRIDOR_LARGE_GROUPS = 1 << 22, 65536, 512
+OCCMAP_DIST_FAR, OCCMAP_DIST_MAX_R = 65535, 64
+CMD_INIT_POSITION, CMD_ROTATE_YAW, CMD_PUB_END, CMD_PUB_TRAJ, CMD_WAIT = range(5)  # enum CMD_STATUS (nmpc_utils.h:115-122)
+COMMAND_NONE, COMMAND_TRAJ, COMMAND_END, COMMAND_YAW, COMMAND_NO_YAW_INPUT = 0, 1, 2, 3, -1  # kind[b][s]
+COMMAND_STRIDE = 16  # position 0-2, quaternion x y z w 3-6, linear velocity 7-9, body rates 10-12, linear acceleration 13-15
+TICK_RUN, TICK_IDLE, TICK_AT_END, TICK_ENDING = range(4)  # gate[b]
+TICK_RESULT_IDLE = -4  # result[b] of a planner whose mpcCallback returned before solveNMPC
+FSM_INIT, FSM_WAIT_TARGET, FSM_INIT_YAW, FSM_GEN_NEW_TRAJ, FSM_REPLAN_TRAJ, FSM_EXEC_TRAJ = range(6)  # enum FSM_EXEC_STATE, in its order
+VEHICLE_STATE, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_MAX_SUB = 9, 8, 13, 16
+ODOM_WORLD, ODOM_BODY = 1, 2  # odometryCallback, odometryTransCallback
+VEHICLE_SAT_THRUST_LO, VEHICLE_SAT_THRUST_HI, VEHICLE_SAT_ROLL, VEHICLE_SAT_PITCH, VEHICLE_SAT_RATE0, VEHICLE_SAT_ZERO_ACC, VEHICLE_SAT_YAW_WRAP = 1, 2, 4, 8, 16, 128, 256
+EST_SKIPPED, EST_FIRST, EST_ABSORBED = 0, 1, 2  # status[b][s]
+
+# name here -> macro in include/*.h, for every integer above (one defined below this line is not checked): FRP_<name>, but for three
+MACROS = {n: n if n.startswith("FRP_") else "FRP_" + n for n, v in list(globals().items()) if n.isupper() and type(v) is int}
+MACROS["ABI_VERSION"] = "FRP_NMPC_ABI_VERSION"
+
+# ---- every function the headers declare, by header, in its declaration order: name -> (restype, argtypes) ----
+# Raw addresses are c_void_p whatever the C pointee: callers hand over data_ptr() integers, c_void_p objects, byref()s or None.
+_i, _d, _z, _v = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
+_P = ctypes.POINTER
+_batch, _map, _cor, _cut, _fsm, _body = [_P(Batch), _P(Options)], _P(OccMap), _P(Corridor), _P(CorridorCut), _P(Fsm), _P(OccMapBody)
+_forces = (_i, [_P(ForcesParams), _P(ForcesOutput), _P(ForcesInfo), _v, _v])  # (FILE *, extfunc: an EXTFUNC or None, which only c_void_p takes)
+_BY_HEADER = {
+    "frp_nmpc.h": {"frp_nmpc_abi_version": (_i, []),
+        "frp_nmpc_abi_check": (_i, [_i, _z, _z, _i]),
+        "frp_nmpc_default_options": (None, [_P(Options)]),
+        "frp_nmpc_workspace_bytes": (_z, [_i, _i, _i]),
+        "frp_nmpc_solve_batch": (_i, _batch + [_v, _z, _v]),
+        "frp_nmpc_solve_batch_host": (_i, _batch),
+        "frp_nmpc_host_register": (_i, [_v, _z]),
+        "frp_nmpc_host_unregister": (_i, [_v]),
+        "frp_nmpc_host_registered": (_i, [_v, _z]),
+        "frp_nmpc_host_unregister_all": (_i, []),
+        "frp_nmpc_solve_batch_host_begin": (_i, _batch + [c_int_p]),
+        "frp_nmpc_solve_batch_host_wait": (_i, [_i]),
+        "frp_nmpc_stage_eval": (_i, [_i] * 4 + [_v] * 8),
+        "frp_nmpc_stage_eval_host": (_i, [_i] * 4 + [_v] * 7),
+        "frp_nmpc_time_solve": (_i, _batch + [_v, _z, _v, _i, _P(ctypes.c_float)]),
+        "frp_nmpc_kernel_timing_begin": (_i, [_i, _i]),
+        "frp_nmpc_kernel_timing_end": (_i, [_P(ctypes.c_float), c_int_p]),
+        "frp_nmpc_set_q4_min_batch": (_i, [_i]),
+        "frp_nmpc_solver_variant": (_i, _batch + [ctypes.c_char_p, _z]),
+        "frp_nmpc_pack_batch": (_i, [_P(Pack), _v]),
+        "frp_nmpc_update_batch": (_i, [_i, _i, _v, _v, _v, _v]),
+        "frp_nmpc_tube_batch": (_i, [_P(Tube), _v]),
+        "frp_nmpc_cloud_grid_build": (_i, [_v, _i, _v, _d, _v, _v, _v, _v, _v, _v]),
+        "frp_nmpc_corridor_batch": (_i, [_cor, _v]),
+        "frp_nmpc_corridor_batch_cut": (_i, [_cor, _cut, _v]),
+        "frp_nmpc_reference_batch": (_i, [_P(Reference), _v]),
+        "frp_nmpc_mode_batch": (_i, [_i, _i, _v, _v, _v, _i, _v, _i, _d, _d, _v, _v]),
+        "frp_nmpc_coldstart_batch": (_i, [_i, _i, _v, _v, _d, _v, _v]),
+        "frp_nmpc_astar_workspace_bytes": (_z, [_P(Astar)]),
+        "frp_nmpc_astar_batch": (_i, [_P(Astar), _v, _z, _v]),
+        "frp_nmpc_occmap_workspace_bytes": (_z, [_map]),
+        "frp_nmpc_occmap_reset": (_i, [_map, _v, _z, _v]),
+        "frp_nmpc_occmap_clear_box": (_i, [_map, c_double_p, c_double_p, _v, _z, _v]),
+        "frp_nmpc_occmap_insert_cloud": (_i, [_map, _v, _i, _v, _z, _v]),
+        "frp_nmpc_occmap_refresh": (_i, [_map, _v, _z, _v]),
+        "frp_nmpc_occmap_local_view": (_i, [_map, _P(OccMapView), _v, _z, _v]),
+        "frp_nmpc_occmap_query": (_i, [_map, _i, _v, _v, _v, _v, _v, _z, _v]),
+        "frp_nmpc_version": (ctypes.c_char_p, []),
+        "frp_nmpc_device_count": (_i, []),
+        "FORCESNLPsolver_normal_solve": _forces,
+        "FORCESNLPsolver_final_solve": _forces},
+    "frp_nmpc_occmap_fuse.h": {"frp_nmpc_occmap_fuse_workspace_bytes": (_z, [_map, _P(OccMapFuse)]),
+        "frp_nmpc_occmap_fuse_depth": (_i, [_map, _P(OccMapFuse), _v, _z, _v, _z, _v])},
+    "frp_nmpc_occmap_fuse_batch.h": {"frp_nmpc_occmap_fuse_batch_workspace_bytes": (_z, [_map, _P(OccMapFuseBatch)]),
+        "frp_nmpc_occmap_fuse_depth_batch": (_i, [_map, _P(OccMapFuseBatch), _v, _z, _v, _z, _v])},
+    "frp_nmpc_occmap_fuse_points.h": {"frp_nmpc_occmap_fuse_points_workspace_bytes": (_z, [_map, _P(OccMapFusePoints)]),
+        "frp_nmpc_occmap_fuse_points_batch": (_i, [_map, _P(OccMapFusePoints), _v, _z, _v, _z, _v])},
+    "frp_nmpc_occmap_check.h": {"frp_nmpc_occmap_check_surround": (_i, [_map, _body, _d, _i, _v, _v, _v, _v, _v, _z, _v]),
+        "frp_nmpc_occmap_check_paths": (_i, [_map, _body, _d, _i, _i, _i, _v, _v, _v, _v, _v, _v, _z, _v]),
+        "frp_nmpc_occmap_check_goals": (_i, [_map, _body, _d, _d, _i, _v, _v, _v, _i, _i, _v, _v, _v, _v, _z, _v])},
+    "frp_nmpc_occmap_distance.h": {"frp_nmpc_occmap_distance_scratch_bytes": (_z, [_map, _i]),
+        "frp_nmpc_occmap_distance_update": (_i, [_map, _i, _i, _v, _v, _z, _v, _z, _v]),
+        "frp_nmpc_occmap_clearance": (_i, [_map, _v, _i, _i, _v, _v, _v, _v]),
+        "frp_nmpc_occmap_clearance_trace": (_i, [_map, _v, _i, _i, _i, _i, _v, _v, _v, _v, _v, _v]),
+        "frp_nmpc_occmap_clearance_reset": (_i, [_i, _v, _v, _v, _v, _v])},
+    "frp_nmpc_occmap_render.h": {"frp_nmpc_occmap_render_depth": (_i, [_map, _P(OccMapRender), _v, _z, _v]),
+        "frp_nmpc_occmap_camera_poses": (_i, [_i, _v, c_double_p, _v, _v])},
+    "frp_nmpc_occmap_render_scan.h": {"frp_nmpc_occmap_render_scan_batch": (_i, [_map, _P(OccMapRenderScan), _v, _z, _v])},
+    "frp_nmpc_occmap_view.h": {"frp_nmpc_occmap_shared_view_dims": (_i, [_map, _d, _P(_i * 3)]),
+        "frp_nmpc_occmap_shared_view_update": (_i, [_map, _P(OccMapSharedView), _v, _z, _v]),
+        "frp_nmpc_corridor_batch_view": (_i, [_cor, _cut, _v])},
+    "frp_nmpc_corridor_large.h": {"frp_nmpc_corridor_large_workspace_bytes": (_z, [_i]),
+        "frp_nmpc_corridor_batch_large": (_i, [_cor, _cut, _P(CorridorLarge), _v]),
+        "frp_nmpc_occmap_shared_view_update_large": (_i, [_map, _P(OccMapSharedView), _v, _z, _v])},
+    "frp_nmpc_command.h": {"frp_nmpc_command_snapshot": (_i, [_i, _i, _v, _v, _v, _v, _v]),
+        "frp_nmpc_command_batch": (_i, [_P(Command), _v])},
+    "frp_nmpc_outcome.h": {"frp_nmpc_tick_begin": (_i, [_P(Tick), _v, _v]),
+        "frp_nmpc_tick_end": (_i, [_P(Tick), _P(TickIn), _v])},
+    "frp_nmpc_fsm.h": {"frp_nmpc_fsm_goal": (_i, [_fsm, _v, _v, _v]),
+        "frp_nmpc_fsm_force": (_i, [_fsm, _v, _v, _d, _v]),
+        "frp_nmpc_fsm_mpc": (_i, [_fsm, _v, _v]),
+        "frp_nmpc_fsm_safety": (_i, [_fsm, _v, _v, _v]),
+        "frp_nmpc_fsm_exec_begin": (_i, [_fsm, _P(FsmExecIn), _v]),
+        "frp_nmpc_fsm_exec_end": (_i, [_fsm, _v, _v, _v, _v])},
+    "frp_nmpc_vehicle.h": {"frp_nmpc_vehicle_step": (_i, [_P(VehicleArgs), _v]),
+        "frp_nmpc_vehicle_reset": (_i, [_i, _v, _v, _v, _v, _v]),
+        "frp_nmpc_vehicle_message": (_i, [_i, _i, _v, _v, _v]),
+        "frp_nmpc_vehicle_odometry": (_i, [_i, _i, _v, _v, _v, _v, _v, _v])},
+    "frp_nmpc_estimator.h": {"frp_nmpc_vehicle_step_observed": (_i, [_P(VehicleArgs), _v, _v]),
+        "frp_nmpc_estimator_update": (_i, [_P(EstimatorArgs), _v]),
+        "frp_nmpc_estimator_reset": (_i, [_i, _v, _v, _v, _v, _v, _v, _v])}}
+SIGNATURES = {name: sig for group in _BY_HEADER.values() for name, sig in group.items()}
+
+# each header's exports, in its order
+EXPORTS, FUSE_EXPORTS, FUSE_BATCH_EXPORTS, FUSE_POINTS_EXPORTS, CHECK_EXPORTS, DISTANCE_EXPORTS, RENDER_EXPORTS, RENDER_SCAN_EXPORTS, VIEW_EXPORTS, \
+    LARGE_EXPORTS, COMMAND_EXPORTS, OUTCOME_EXPORTS, FSM_EXPORTS, VEHICLE_EXPORTS, ESTIMATOR_EXPORTS = (list(group) for group in _BY_HEADER.values())
+
+
+_lib = None  # the loaded library, once lib() ran (solver._lib is this name as it was at import: None)
+
+
+def lib():
+    """Load libfrp_nmpc_amd.so (built in-tree by forces_resilient_planner_amd.build)."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f"{LIB_PATH} missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        # PyTorch ships its own HIP runtime; the library links the system one.  Both coexist in one process as long
+        # as torch's is initialised first (the reverse order leaves torch with "No HIP GPUs are available"), and
+        # DeviceSolver / DeviceFleet hand torch-owned HBM to the library, so initialise torch here if it has a GPU.
+        try:
+            import torch
+            if torch.cuda.is_available():
+                torch.cuda.init()
+        except ImportError:
+            pass
+        l = ctypes.CDLL(LIB_PATH)
+        # the ctypes mirrors below against the library that was actually loaded (include/frp_nmpc.h: FRP_NMPC_ABI_CHECK): a stale
+        # library would write another info stride into our arrays / read short option structs
+        if not hasattr(l, "frp_nmpc_abi_check"):
+            raise RuntimeError(f"{LIB_PATH} predates the ABI check (frp_nmpc.h ABI {ABI_VERSION}): rebuild it")
+        l.frp_nmpc_abi_check.argtypes = SIGNATURES["frp_nmpc_abi_check"][1]
+        if l.frp_nmpc_abi_check(ABI_VERSION, ctypes.sizeof(Options), ctypes.sizeof(Batch), INFO_STRIDE) != 0:
+            raise RuntimeError(f"{LIB_PATH} was built from another include/frp_nmpc.h than these bindings (ABI {ABI_VERSION}, "
+                               f"options {ctypes.sizeof(Options)} B, batch {ctypes.sizeof(Batch)} B, info stride {INFO_STRIDE})")
+        for name, (restype, argtypes) in SIGNATURES.items():  # a library without one of them is not these headers' library: no call is ever skipped for a missing kernel
+            if not hasattr(l, name):
+                raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it")
+            f = getattr(l, name)
+            f.restype, f.argtypes = restype, argtypes
+        _lib = l
+    return _lib
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed with frp error {rc} (no HIP device / HIP error / bad argument; "
+                           "this library has no CPU path)")
+
+
+def tensor_ptr(a):
+    """The address of a device tensor as the c_void_p a call or a struct field takes; None stays None (an absent argument)."""
+    return ctypes.c_void_p(a.data_ptr()) if a is not None else None
+
+
+def stream_ptr(stream, where):
+    """A torch stream as the c_void_p a call takes; None: torch's current stream of the device `where`, or of the tensor `where`."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(getattr(where, "device", where))
+    return ctypes.c_void_p(stream.cuda_stream)
+
+
+def checked_ptr(like, a, dtype, shape):
+    """tensor_ptr of an argument that has to be a contiguous tensor of that dtype and shape on the device of the tensor `like`."""
+    import torch
+    assert torch.is_tensor(a) and a.dtype == dtype and tuple(a.shape) == shape and a.is_contiguous() and a.device == like.device, \
+        (tuple(a.shape), shape, a.dtype)
+    return ctypes.c_void_p(a.data_ptr())

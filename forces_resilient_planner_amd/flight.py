@@ -1,0 +1,362 @@
+"""A fleet in flight, on the device: the state machine that drives the planners (FleetFSM), the vehicle that flies their commands
+(Vehicle) and the estimator that tells them what it felt (ForceEstimator) (frp_nmpc_fsm_*, _vehicle_*, _estimator_*)."""
+import ctypes
+
+from . import layout as L
+from .capi import (COMMAND_STRIDE, FSM_INIT, ODOM_BODY, ODOM_WORLD, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs,
+                   Fsm, FsmExecIn, VehicleArgs, _check, checked_ptr, lib, stream_ptr, tensor_ptr)
+from .fleet import TickState
+from .occmap import SafetyCheck
+from .planning import COMMAND_DEFAULTS
+
+FSM_EXT_NOISE_BOUND = 0.5  # nmpc/ext_noise_bound (nmpc_manage.cpp:13)
+FSM_EXEC_PERIOD = 0.01     # the period of exec_timer_ (nmpc_manage.cpp:44) = that of the command timer
+
+# the controller's gains (no reference counterpart: the reference flies RotorS' controller) and what it is told; mass and g are the
+# plant's own (csrc/frp_model.hpp), dt_cmd the command timer's period
+VEHICLE_DEFAULTS = dict(kp=(6.0, 6.0, 8.0), kv=(4.0, 4.0, 5.0), ka=(10.0, 10.0, 4.0), mass=0.745319, g=9.81, dt_cmd=FSM_EXEC_PERIOD, n_sub=4)
+
+# CHOSEN, not derived (the reference has no estimator: its wrench comes from another node): a filter time constant of 0.1 s -- two of the
+# planner's 50 ms periods, alpha = 1 - exp(-0.01 / 0.1) = 0.095 per 100 Hz sample, a step of 1 m/s^2 passes ext_noise_bound = 0.5 after
+# 7 samples --, and an estimate that counts as fresh once 10 residuals (two periods) went into it
+ESTIMATOR_DEFAULTS = dict(tau=0.1, min_samples=10)
+
+
+class Vehicle:
+    """The vehicle of every planner of a DeviceFleet, on the device (include/frp_nmpc_vehicle.h): a tracking plant that flies the command
+    timer's samples and the reference's odometry callbacks, so that FleetFSM.period(..., vehicle=...) closes the loop without the host.
+    Owns, all float64 device tensors unless noted: x [B,9] the plant state (position, world velocity, roll pitch yaw), hold [B,8] the last
+    published position and yaw, f_true [B,3] the TRUE mass-normalised external force (the caller writes it; what the planner is told is
+    the `force` / `force_fresh` of period(): the caller's own, or a ForceEstimator's), msg [B,13] the last odometry message, state [B,9] what the callbacks made of it (the
+    `state` of period(), exec_step() and full_tick()), state_prev [B,9], fresh [B] int32 (ones: every planner hears every message), and
+    with trace=True trace [B,S,9] / sat [B,S] int32 of the last step().
+    kp, kv, ka, n_sub, mass, g, dt_cmd: VEHICLE_DEFAULTS -- the controller has no reference counterpart, the plant is the planner's own
+    model (csrc/frp_model.hpp).  odom_type: ODOM_BODY (odometryTransCallback: the RotorS message, body-frame twist) or ODOM_WORLD."""
+
+    def __init__(self, fleet, kp=None, kv=None, ka=None, n_sub=None, odom_type=ODOM_BODY, mass=None, g=None, dt_cmd=None, trace=False, S=5):
+        t = fleet.torch
+        dev = fleet.solver.device
+        self.torch, self.fleet, self.B, self.S = t, fleet, fleet.B, int(S)
+        k = dict(VEHICLE_DEFAULTS)
+        k.update({n: v for n, v in (("kp", kp), ("kv", kv), ("ka", ka), ("n_sub", n_sub), ("mass", mass), ("g", g), ("dt_cmd", dt_cmd)) if v is not None})
+        self.kp, self.kv, self.ka = (tuple(float(v) for v in k[n]) for n in ("kp", "kv", "ka"))
+        assert len(self.kp) == len(self.kv) == len(self.ka) == 3
+        self.n_sub, self.mass, self.g, self.dt_cmd = int(k["n_sub"]), float(k["mass"]), float(k["g"]), float(k["dt_cmd"])
+        if odom_type not in (ODOM_WORLD, ODOM_BODY):
+            raise ValueError("odom_type is ODOM_WORLD or ODOM_BODY")
+        self.odom_type = int(odom_type)
+        f64 = dict(dtype=t.float64, device=dev)
+        self.x, self.state, self.state_prev = (t.zeros((self.B, VEHICLE_STATE), **f64) for _ in range(3))
+        self.hold = t.zeros((self.B, VEHICLE_HOLD_STRIDE), **f64)
+        self.f_true = t.zeros((self.B, 3), **f64)
+        self.msg = t.zeros((self.B, VEHICLE_MSG_STRIDE), **f64)
+        self.fresh = t.ones((self.B,), dtype=t.int32, device=dev)
+        self.trace = t.zeros((self.B, self.S, VEHICLE_STATE), **f64) if trace else None
+        self.sat = t.zeros((self.B, self.S), dtype=t.int32, device=dev) if trace else None
+        self.estimator = None   # a ForceEstimator attaches itself here: step() and reset() then feed and reset it
+
+    def reset(self, x0, mask=None, stream=None):
+        """frp_nmpc_vehicle_reset: where mask [B] int32 != 0 (None: everywhere) x <- x0 [B,9] and hold <- its position and yaw: the
+        vehicle hovers there until something is published.  `state` is the callbacks': call odometry(fsm) to publish the new pose."""
+        t = self.torch
+        m = checked_ptr(self.x, mask, t.int32, (self.B,)) if mask is not None else None
+        _check(lib().frp_nmpc_vehicle_reset(self.B, checked_ptr(self.x, x0, t.float64, (self.B, VEHICLE_STATE)), m, tensor_ptr(self.x),
+                                            tensor_ptr(self.hold), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_reset")
+        if self.estimator is not None:
+            self.estimator.reset(mask, stream)
+
+    def step(self, commands, stream=None):
+        """frp_nmpc_vehicle_step: the S samples of a Commands object (cmd [B,S,16], kind [B,S]) flown in order under f_true; x and hold
+        in place, trace / sat where the object was made with trace=True (S is then the constructor's).
+        With a ForceEstimator attached (self.estimator): frp_nmpc_vehicle_step_observed instead -- the same flight, and the thrust of every
+        sample into the estimator's `thrust`, the trace into this object's own trace or else the estimator's `meas` --, then its update()."""
+        t = self.torch
+        S = int(commands.cmd.shape[1])
+        if self.trace is not None and S != self.S:
+            raise ValueError(f"this Vehicle traces S = {self.S} samples per call, the commands hold {S}")
+        est = self.estimator
+        if est is not None and S != est.S:
+            raise ValueError(f"the attached ForceEstimator takes S = {est.S} samples per call, the commands hold {S}")
+        trace = self.trace if self.trace is not None else est.meas if est is not None else None
+        v = VehicleArgs(self.B, S, self.n_sub, self.mass, self.g, self.dt_cmd, (ctypes.c_double * 3)(*self.kp), (ctypes.c_double * 3)(*self.kv),
+                        (ctypes.c_double * 3)(*self.ka), self.x.data_ptr(), self.f_true.data_ptr(),
+                        checked_ptr(self.x, commands.cmd, t.float64, (self.B, S, COMMAND_STRIDE)), checked_ptr(self.x, commands.kind, t.int32, (self.B, S)),
+                        self.hold.data_ptr(), trace.data_ptr() if trace is not None else None, self.sat.data_ptr() if self.sat is not None else None)
+        if est is None:
+            _check(lib().frp_nmpc_vehicle_step(ctypes.byref(v), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step")
+            return
+        _check(lib().frp_nmpc_vehicle_step_observed(ctypes.byref(v), tensor_ptr(est.thrust), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step_observed")
+        est.update(meas=trace, stream=stream)
+
+    def message(self, stream=None):
+        """frp_nmpc_vehicle_message: msg <- the odometry message of x for this object's odom_type."""
+        _check(lib().frp_nmpc_vehicle_message(self.B, self.odom_type, tensor_ptr(self.x), tensor_ptr(self.msg), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_message")
+
+    def odometry(self, fsm, msg=None, fresh=None, stream=None):
+        """odometryCallback / odometryTransCallback (nmpc_manage.cpp:421-478) into state, state_prev and fsm.have_odom.  msg None (a
+        simulated fleet): the message is produced from the plant first, message(); msg [B,13] (a real fleet): the callback alone.
+        fresh [B] int32: who got a message (None: everybody)."""
+        t = self.torch
+        if msg is None:
+            self.message(stream)
+            msg = self.msg
+        fresh = self.fresh if fresh is None else fresh
+        _check(lib().frp_nmpc_vehicle_odometry(self.B, self.odom_type, checked_ptr(self.x, msg, t.float64, (self.B, VEHICLE_MSG_STRIDE)),
+                                               checked_ptr(self.x, fresh, t.int32, (self.B,)), tensor_ptr(self.state), tensor_ptr(self.state_prev),
+                                               checked_ptr(self.x, fsm.have_odom, t.int32, (self.B,)), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_odometry")
+
+
+class ForceEstimator:
+    """The force estimator of every vehicle of a Vehicle, on the device (include/frp_nmpc_estimator.h): a velocity-residual observer on the
+    planner's own model that turns the thrust and the states of the samples a vehicle flew into the `force` / `force_fresh` pair of
+    FleetFSM.period -- what the planner is TOLD, where vehicle.f_true is what acts.  It has no reference counterpart (the reference
+    subscribes to a wrench another node publishes), and its measurements are the TRUE plant states of the vehicle's trace: noise is the
+    caller's to add (update(meas=...) takes any [B,S,9] tensor).
+    Attaches itself as vehicle.estimator: Vehicle.step then launches frp_nmpc_vehicle_step_observed and update(), Vehicle.reset resets
+    it under the same mask.  The loop closes through arguments period() already has:
+        fsm.period(planner, occmap, None, clock, force=est.force, force_fresh=est.fresh, vehicle=veh)
+    -- the force callback of period p hears the estimate the end of period p - 1 left.
+    Owns, float64 device tensors unless noted: meas [B,S,9] (the vehicle's trace where it keeps none of its own), thrust [B,S], f_hat [B,3],
+    y_prev [B,9], count [B] int32 (-1: no previous measurement), force [B,3], fresh [B] int32 and, with residual=True, residual [B,S,3] /
+    status [B,S] int32 (EST_*) of the last update().
+    tau, min_samples: ESTIMATOR_DEFAULTS -- CHOSEN, not derived, as VEHICLE_DEFAULTS' gains are: a first-order filter of time constant tau
+    on the residual, alpha = -expm1(-dt / tau) per sample with dt the vehicle's dt_cmd, computed here on the host; the estimate counts
+    as fresh after min_samples residuals."""
+
+    def __init__(self, vehicle, tau=None, min_samples=None, residual=False):
+        import math
+        t = vehicle.torch
+        dev = vehicle.x.device
+        k = dict(ESTIMATOR_DEFAULTS)
+        k.update({n: v for n, v in (("tau", tau), ("min_samples", min_samples)) if v is not None})
+        self.torch, self.vehicle, self.B, self.S = t, vehicle, vehicle.B, vehicle.S
+        self.tau, self.min_samples, self.dt = float(k["tau"]), int(k["min_samples"]), float(vehicle.dt_cmd)
+        if not (self.tau > 0.0 and math.isfinite(self.tau)) or self.min_samples < 1:
+            raise ValueError("ForceEstimator: tau finite and > 0, min_samples >= 1")
+        self.alpha = -math.expm1(-self.dt / self.tau)
+        f64 = dict(dtype=t.float64, device=dev)
+        i32 = dict(dtype=t.int32, device=dev)
+        self.meas, self.thrust = t.zeros((self.B, self.S, VEHICLE_STATE), **f64), t.zeros((self.B, self.S), **f64)
+        self.f_hat, self.y_prev, self.force = t.zeros((self.B, 3), **f64), t.zeros((self.B, VEHICLE_STATE), **f64), t.zeros((self.B, 3), **f64)
+        self.count, self.fresh = t.full((self.B,), -1, **i32), t.zeros((self.B,), **i32)
+        self.residual = t.zeros((self.B, self.S, 3), **f64) if residual else None
+        self.status = t.zeros((self.B, self.S), **i32) if residual else None
+        vehicle.estimator = self
+
+    def update(self, meas=None, thrust=None, stream=None):
+        """frp_nmpc_estimator_update: the S samples of meas [B,S,9] / thrust [B,S] (None: this object's own) absorbed in order; f_hat,
+        y_prev and count in place, force and fresh written."""
+        t, v = self.torch, self.vehicle
+        meas = self.meas if meas is None else meas
+        thrust = self.thrust if thrust is None else thrust
+        e = EstimatorArgs(self.B, self.S, self.min_samples, self.dt, self.alpha, checked_ptr(v.x, meas, t.float64, (self.B, self.S, VEHICLE_STATE)),
+                          checked_ptr(v.x, thrust, t.float64, (self.B, self.S)),
+                          *map(tensor_ptr, (self.f_hat, self.y_prev, self.count, self.force, self.fresh, self.residual, self.status)))
+        _check(lib().frp_nmpc_estimator_update(ctypes.byref(e), stream_ptr(stream, v.x)), "frp_nmpc_estimator_update")
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_estimator_reset: where mask [B] int32 != 0 (None: everywhere) f_hat <- 0, count <- -1, force <- 0, fresh <- 0."""
+        t, v = self.torch, self.vehicle
+        m = checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None
+        state = map(tensor_ptr, (self.f_hat, self.y_prev, self.count, self.force, self.fresh))
+        _check(lib().frp_nmpc_estimator_reset(self.B, m, *state, stream_ptr(stream, v.x)), "frp_nmpc_estimator_reset")
+
+
+class FleetFSM:
+    """NMPCManage (plan_manage/src/nmpc_manage.cpp) for the B planners of a DeviceFleet, on the device (include/frp_nmpc_fsm.h): a fleet goes
+    goal -> yaw alignment -> plan -> execute -> replan on force / collision / failure -> goal reached -> next goal without the host reading
+    anything back.  Owns the state tensors, [B] int32 unless noted: state (FSM_*, INIT at first), have_odom (the CALLER sets it, or a
+    Vehicle's odometry callbacks do), have_target, have_traj (NMPCManage's have_traj_, not fleet.have_traj = have_mpc_traj_), trigger,
+    call_init_yaw, consider_force, replan_force_surpass, surpass_count, plan_fail_count; end_pt, external_acc, last_external_acc [B,3] f64,
+    init_yaw [B] f64, yaw_odom [B,9] f64, change_yaw_time / kino_start_time [B] f64 on the caller's clock, all zero at first (the reference
+    leaves the doubles uninitialised); search [B], the mask of the last exec_step; mpc_start [B] f64, pre_mpc_start_time_ as period() keeps it.
+    Shares exec_mpc, cmd_status and pub_end with `tick` (a TickState, made here when None) and mode with the fleet; exec_mpc is ZEROED
+    here: under the state machine a planner solves only after its first successful search (the reference's exec_mpc_ = false).
+    The command timer's yaw inputs are this object's: DeviceFleet.commands(..., odom=fsm.yaw_odom, init_yaw=fsm.init_yaw, t_yaw=fsm.t_yaw(...)).
+    This layer is structurally unpinned: the reference has no test vectors for it; tests/fsm_oracle.py is the restatement it is held to."""
+
+    INT_FIELDS = ("state", "have_odom", "have_target", "have_traj", "trigger", "call_init_yaw", "consider_force", "replan_force_surpass",
+                  "surpass_count", "plan_fail_count")
+    F64_FIELDS = (("end_pt", 3), ("external_acc", 3), ("last_external_acc", 3), ("init_yaw", 0), ("yaw_odom", 9), ("change_yaw_time", 0),
+                  ("kino_start_time", 0))
+    MAX_STEPS = 5   # exec steps per period: exec_timer_ runs at 100 Hz, the tick at 20 Hz
+    S = 5           # command callbacks per period
+
+    def __init__(self, fleet, tick=None, ext_noise_bound=FSM_EXT_NOISE_BOUND):
+        t = fleet.torch
+        dev = fleet.solver.device
+        self.torch, self.fleet, self.B = t, fleet, fleet.B
+        self.tick = tick if tick is not None else TickState(fleet)
+        assert self.tick.B == self.B
+        self.ext_noise_bound = float(ext_noise_bound)
+        for n in self.INT_FIELDS + ("search",):
+            setattr(self, n, t.zeros((self.B,), dtype=t.int32, device=dev))
+        self.state.fill_(FSM_INIT)
+        for n, w in self.F64_FIELDS:
+            setattr(self, n, t.zeros((self.B, w) if w else (self.B,), dtype=t.float64, device=dev))
+        self.exec_mpc, self.cmd_status, self.pub_end, self.mode = self.tick.exec_mpc, self.tick.cmd_status, self.tick.pub_end, fleet.mode
+        self.exec_mpc.zero_()
+        f64 = dict(dtype=t.float64, device=dev)
+        self.mpc_start = t.zeros((self.B,), **f64)
+        # period()'s own buffers: a capture of it allocates nothing of the caller's
+        z = lambda: t.zeros((self.B,), dtype=t.int32, device=dev)
+        self.safety_out = SafetyCheck(z(), z(), z(), z())
+        self.ref_pos, self.ref_yaw = t.zeros((self.B, fleet.N, 3), **f64), t.zeros((self.B, fleet.N), **f64)
+        self.t_step, self.toff = t.zeros((self.B,), **f64), t.zeros((self.B,), **f64)
+        self.t_cmd, self.t_rot = t.zeros((self.B, self.S), **f64), t.zeros((self.B, self.S), **f64)
+        self._ramp = t.arange(self.S, **f64) * FSM_EXEC_PERIOD
+        self._ran = t.zeros((self.B,), dtype=t.bool, device=dev)
+        self.commands_out = None
+
+    def struct(self):
+        p = lambda n: getattr(self, n).data_ptr() if getattr(self, n) is not None else None
+        return Fsm(self.B, *[p(n) for n, _ in Fsm._fields_[1:]])
+
+    def arrays(self):
+        """Every state array on the host (a synchronising read-back: tests and logs)."""
+        names = self.INT_FIELDS + ("exec_mpc", "cmd_status", "pub_end", "search") + tuple(n for n, _ in self.F64_FIELDS)
+        return {n: getattr(self, n).cpu().numpy() for n in names}
+
+    def goal(self, goal, fresh, stream=None):
+        """goalCallback (nmpc_manage.cpp:481-493): goal [B,3] f64, fresh [B] int32 (non-zero: a message for this planner)."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_goal(ctypes.byref(f), checked_ptr(self.state, goal, t.float64, (self.B, 3)), checked_ptr(self.state, fresh, t.int32, (self.B,)),
+                                       stream_ptr(stream, self.state)), "frp_nmpc_fsm_goal")
+
+    def force(self, force, fresh, stream=None):
+        """extforceCallback (nmpc_manage.cpp:366-418): force [B,3] f64 (mass-normalised), fresh [B] int32."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_force(ctypes.byref(f), checked_ptr(self.state, force, t.float64, (self.B, 3)), checked_ptr(self.state, fresh, t.int32, (self.B,)),
+                                        self.ext_noise_bound, stream_ptr(stream, self.state)), "frp_nmpc_fsm_force")
+
+    def mpc_result(self, result=None, stream=None):
+        """The switch of mpcCallback (nmpc_manage.cpp:60-97) on result [B] int32 (None: tick.result, as full_tick(tick=...) left it)."""
+        f = self.struct()
+        result = self.tick.result if result is None else result
+        _check(lib().frp_nmpc_fsm_mpc(ctypes.byref(f), checked_ptr(self.state, result, self.torch.int32, (self.B,)), stream_ptr(stream, self.state)),
+               "frp_nmpc_fsm_mpc")
+
+    def safety_verdict(self, goal_blocked, first_hit, stream=None):
+        """The transitions of checkReplanCallback (nmpc_manage.cpp:318-325, :333-338) for verdicts [B] int32 the caller holds."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_safety(ctypes.byref(f), checked_ptr(self.state, goal_blocked, t.int32, (self.B,)),
+                                         checked_ptr(self.state, first_hit, t.int32, (self.B,)), stream_ptr(stream, self.state)), "frp_nmpc_fsm_safety")
+
+    def safety(self, occmap, planner, local_box=None, stride=5, stream=None, out=None):
+        """One checkReplanCallback (nmpc_manage.cpp:285-341): OccupancyMap.safety_check on this object's end_pt (moved in place where the
+        search finds a free goal) / have_target / have_traj and the planner's kino_path / kino_size, then the transitions.  Returns the
+        SafetyCheck (out, or this object's own safety_out)."""
+        out = out if out is not None else self.safety_out
+        occmap.safety_check(self.end_pt, planner.kino_path, planner.kino_size, have_target=self.have_target, have_traj=self.have_traj,
+                            local_box=local_box, stride=stride, stream=stream, out=out)
+        self.safety_verdict(out.goal_blocked, out.first_hit, stream)
+        return out
+
+    def bind(self, planner):
+        """Makes the planner's retry buffers exist (an allocation: period() and exec_step() call it; call it once before a capture)."""
+        assert planner.B == self.B and planner.device == self.state.device
+        if planner._retry is None:
+            planner._retry = [self.torch.zeros_like(planner._q[0]), self.torch.zeros_like(planner._q[0])]
+
+    def exec_step(self, planner, state, t_cur, now, local_box=None, end_vel=None, stream=None, Ts=None, mass=None, g=None):
+        """One execFSMCallback (nmpc_manage.cpp:109-260) for every planner: frp_nmpc_fsm_exec_begin writes self.search and, for the planners
+        that search, the start / retry state straight into the AstarPlanner's own buffers; planner.plan(active=self.search) with this
+        object's end_pt and external_acc; frp_nmpc_fsm_exec_end applies the verdict (planner.status).  state [B,9] f64 odometry, t_cur [B]
+        f64 seconds since pre_mpc_start_time_, now [1] f64; end_vel [B,3] or None: the planner's uploaded one (zeros at first).
+        Ts / mass / g: COMMAND_DEFAULTS.  Planners that do not search keep their A* rows and their path."""
+        self.bind(planner)
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.state.device)
+        self.exec_begin(state, t_cur, now, planner._q[0], planner._q[1], planner._q[2], planner._retry[0], planner._retry[1], s, Ts, mass, g)
+        planner.plan(init=True, local_box=local_box, stream=s, active=self.search, end_pt=self.end_pt, end_vel=end_vel, external_acc=self.external_acc)
+        self.exec_end(planner.status, now, s)
+
+    def exec_begin(self, state, t_cur, now, start_pt, start_vel, start_acc, retry_pt, retry_vel, stream=None, Ts=None, mass=None, g=None):
+        """frp_nmpc_fsm_exec_begin: the first half of exec_step, for a caller with its own search.  Writes self.search and, for the
+        planners that search alone, the five [B,3] f64 start / retry tensors; reads the fleet's pre_plan and the tick's exit_code."""
+        t = self.torch
+        k = dict(COMMAND_DEFAULTS)
+        k.update({n: float(v) for n, v in (("Ts", Ts), ("mass", mass), ("g", g)) if v is not None})
+        fl, B = self.fleet, self.B
+        f = self.struct()
+        v = lambda a, shape=(B, 3), dtype=t.float64: checked_ptr(self.state, a, dtype, shape)
+        i = FsmExecIn(fl.N, k["Ts"], k["mass"], k["g"], v(state, (B, 9)), v(fl.pre_plan, (B, fl.N, L.NZ)), v(self.tick.exit_code, (B,), t.int32),
+                      v(t_cur, (B,)), v(now, (1,)), self.search.data_ptr(), v(start_pt), v(start_vel), v(start_acc), v(retry_pt), v(retry_vel))
+        _check(lib().frp_nmpc_fsm_exec_begin(ctypes.byref(f), ctypes.byref(i), stream_ptr(stream, self.state)), "frp_nmpc_fsm_exec_begin")
+
+    def exec_end(self, astar_status, now, stream=None):
+        """frp_nmpc_fsm_exec_end: the second half of exec_step, on self.search and astar_status [B] int32 (AstarPlanner.status)."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_fsm_exec_end(ctypes.byref(f), tensor_ptr(self.search), checked_ptr(self.state, astar_status, t.int32, (self.B,)),
+                                           checked_ptr(self.state, now, t.float64, (1,)), stream_ptr(stream, self.state)), "frp_nmpc_fsm_exec_end")
+
+    def time_offset(self, mpc_start, out=None):
+        """(mpc_start_time_ - kino_start_time_).toSec() (nmpc_solver.cpp:436) on the device: mpc_start [1] or [B] f64 -> [B]."""
+        return self.torch.sub(mpc_start, self.kino_start_time, out=out)
+
+    def t_yaw(self, now, S, out=None):
+        """(now - change_yaw_time_).toSec() (nmpc_solver.cpp:885) of S command callbacks at now, now + 0.01, ...: now [1] f64 -> [B,S]."""
+        t = self.torch
+        ramp = self._ramp if S == self.S else t.arange(S, dtype=t.float64, device=now.device) * FSM_EXEC_PERIOD
+        return t.sub((now + ramp)[None, :], self.change_yaw_time[:, None], out=out)
+
+    def period(self, planner, occmap, state, clock, cloud=None, *, goal=None, goal_fresh=None, force=None, force_fresh=None, fsm_steps=1,
+               local_box=None, end_vel=None, stream=None, vehicle=None, **tick_args):
+        """One 50 ms period of the fleet, everything enqueued on `stream` (torch's current stream when None), nothing read back, in this
+        fixed order:
+          1. goal(goal, goal_fresh) and force(force, force_fresh), each where given;
+          2. safety(occmap, planner, local_box);
+          3. fsm_steps (1 ... 5) exec_step()s, step k at clock[k] with t_cur = clock[k] - mpc_start;
+          4. fleet.full_tick(external_acc, planner.kino_path, time_offset, cloud, ..., kino_size=planner.kino_size, state=state, tick=self.tick,
+             end_pt=self.end_pt, **tick_args) at clock[fsm_steps], with time_offset = clock[fsm_steps] - kino_start_time; mpc_start <- that
+             time for the planners that got past solveNMPC's gates (tick.gate == TICK_RUN; nmpc_solver.cpp:358-359);
+          5. mpc_result();
+          6. fleet.commands with S = 5 callbacks at clock[fsm_steps + 1], + 0.01, ...: t_cur from mpc_start, t_yaw from change_yaw_time, the
+             yaw inputs this object's; tick.reset_output <- the returned reset_output.
+        clock: [fsm_steps + 2] f64 device tensor on the caller's clock (clock_for() fills the reference's timer periods in).  state [B,9]
+        f64 odometry.  cloud and tick_args (grid, cut, view, cloud_count, tube_consts, corridor_consts, Ts) are full_tick's.  A
+        captured period replays with new contents of goal / goal_fresh / force / force_fresh / state / clock.  Returns the Commands.
+        vehicle: a Vehicle, or None.  With one, three more launches follow step 6 --
+          7. vehicle.step(commands) under vehicle.f_true, vehicle.odometry(self): message, then the callback into vehicle.state and have_odom
+        -- and `state` is vehicle.state (pass it, or None): the next period plans from what the vehicle flew, so K periods are one graph
+        with no host in the loop.  The force estimator stays the caller's: force / force_fresh.  With None the launches are steps 1-6."""
+        t = self.torch
+        if vehicle is not None:
+            assert vehicle.B == self.B and (state is None or state is vehicle.state), "with a vehicle the odometry is vehicle.state"
+            state = vehicle.state
+        assert 1 <= int(fsm_steps) <= self.MAX_STEPS and tuple(clock.shape) == (int(fsm_steps) + 2,) and clock.dtype == t.float64
+        fl, tk = self.fleet, self.tick
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.state.device)
+        self.bind(planner)
+        if goal is not None:
+            self.goal(goal, goal_fresh, s)
+        if force is not None:
+            self.force(force, force_fresh, s)
+        self.safety(occmap, planner, local_box=local_box, stream=s)
+        with t.cuda.stream(s):
+            for k in range(int(fsm_steps)):
+                now = clock[k:k + 1]
+                t.sub(now, self.mpc_start, out=self.t_step)
+                self.exec_step(planner, state, self.t_step, now, local_box=local_box, end_vel=end_vel, stream=s, Ts=tick_args.get("Ts"))
+            now = clock[fsm_steps:fsm_steps + 1]
+            self.time_offset(now, out=self.toff)
+            fl.full_tick(self.external_acc, planner.kino_path, self.toff, cloud, self.ref_pos, self.ref_yaw, stream=s, kino_size=planner.kino_size,
+                         state=state, tick=tk, end_pt=self.end_pt, **tick_args)
+            t.eq(tk.gate, TICK_RUN, out=self._ran)
+            t.where(self._ran, now, self.mpc_start, out=self.mpc_start)
+            self.mpc_result(stream=s)
+            first = clock[fsm_steps + 1:fsm_steps + 2]
+            t.sub((first + self._ramp)[None, :], self.mpc_start[:, None], out=self.t_cmd)
+            self.t_yaw(first, self.S, out=self.t_rot)
+            self.commands_out = fl.commands(self.t_cmd, self.cmd_status, self.pub_end, tk.cmd_end_pt, odom=self.yaw_odom, init_yaw=self.init_yaw,
+                                            t_yaw=self.t_rot, out=self.commands_out, stream=s, Ts=tick_args.get("Ts"))
+            tk.reset_output = self.commands_out.reset_output
+        if vehicle is not None:
+            vehicle.step(self.commands_out, s)
+            vehicle.odometry(self, stream=s)
+        return self.commands_out
+
+    @staticmethod
+    def clock_for(t0, fsm_steps):
+        """The reference's timers for a period starting at t0 (host floats): exec steps at t0, t0 + 0.01, ..., the tick and the first
+        command callback one exec period after the last step and after the tick."""
+        return [t0 + FSM_EXEC_PERIOD * k for k in range(int(fsm_steps) + 2)]

@@ -1,0 +1,285 @@
+"""What a planner computes around its solve, on device tensors: the tube, the stage references, the corridor, the kinodynamic A* and the
+100 Hz command sampling (frp_nmpc_tube_batch, _reference_batch, _corridor_batch*, _astar_batch, _command_*)."""
+import ctypes
+
+import numpy as np
+
+from . import layout as L
+from .capi import (ASTAR_MAX_PATH, COMMAND_STRIDE, CORRIDOR_MAX_F, CORRIDOR_MAX_POINTS, Astar, Command, Corridor, Reference, Tube, _check, lib, stream_ptr,
+                   tensor_ptr)
+from .occmap import CloudGrid, OccupancyMap
+
+REFERENCE_PI = 3.1415926  # nmpc_solver.cpp:3
+
+# getSikangConst's constants (nmpc_solver.cpp:302, :318, :323)
+CORRIDOR_DEFAULTS = dict(bbox=(2.0, 2.0, 1.0), seed_len=0.1, inflation=1.1, offset_x=0.0)
+
+# ROS parameter defaults of the tube model (nmpc_solver.cpp:68-74, nmpc_utils.h:188-189)
+TUBE_DEFAULTS = dict(mass=0.74, drag=0.33, ego_r=0.27, ego_h=0.0425, noise=(0.5, 0.5, 0.5), epsilon=0.06, Ts=0.05)
+
+COMMAND_DEFAULTS = dict(Ts=0.05, mass=0.74, g=9.81)  # nmpc_utils.h:189, nmpc/mass, the g of nmpc_solver.cpp
+
+
+def tube_batch_device(mpc_output, ellipsoid, consts=None, stream=None):
+    """frp_nmpc_tube_batch on device tensors: mpc_output [B,N+1,17] f64 -> ellipsoid [B,N,3,3] f64 (in place)."""
+    import torch
+    c = dict(TUBE_DEFAULTS)
+    c.update(consts or {})
+    B, rows, nz = mpc_output.shape
+    assert nz == L.NZ and mpc_output.is_contiguous() and ellipsoid.is_contiguous() and mpc_output.dtype == torch.float64
+    assert tuple(ellipsoid.shape) == (B, rows - 1, 3, 3) and ellipsoid.dtype == torch.float64
+    tb = Tube(B, rows - 1, mpc_output.data_ptr(), c["mass"], c["drag"], c["ego_r"], c["ego_h"],
+              (ctypes.c_double * 3)(*c["noise"]), c["epsilon"], c["Ts"], ellipsoid.data_ptr())
+    _check(lib().frp_nmpc_tube_batch(ctypes.byref(tb), stream_ptr(stream, mpc_output.device)), "frp_nmpc_tube_batch")
+
+
+def reference_batch_device(kino_path, time_offset, mpc_output, ref_pos, ref_yaw, replan=None, kino_size=None, Ts=0.05,
+                           stream=None):
+    """frp_nmpc_reference_batch on device tensors: kino_path [K,3] (shared) or [B,K,3]; time_offset [B];
+    mpc_output [B,N+1,17] -> ref_pos [B,N,3], ref_yaw [B,N], replan [B] int32."""
+    import torch
+    B, N, _ = ref_pos.shape
+    per = 1 if kino_path.dim() == 3 else 0
+    K = kino_path.shape[-2]
+    for t in (kino_path, time_offset, mpc_output, ref_pos, ref_yaw):
+        assert t.is_contiguous() and t.dtype == torch.float64
+    assert tuple(mpc_output.shape) == (B, N + 1, L.NZ) and tuple(ref_yaw.shape) == (B, N) and tuple(time_offset.shape) == (B,)
+    rf = Reference(B, N, K, kino_path.data_ptr(), per, kino_size.data_ptr() if kino_size is not None else None,
+                   time_offset.data_ptr(), mpc_output.data_ptr(), Ts, REFERENCE_PI, ref_pos.data_ptr(), ref_yaw.data_ptr(),
+                   replan.data_ptr() if replan is not None else None)
+    _check(lib().frp_nmpc_reference_batch(ctypes.byref(rf), stream_ptr(stream, ref_pos.device)), "frp_nmpc_reference_batch")
+
+
+def reference_batch_host(kino_path, time_offset, mpc_output, kino_size=None, Ts=0.05, device="cuda:0"):
+    """Host convenience: numpy in, (ref_pos [B,N,3], ref_yaw [B,N], replan [B]) out."""
+    import torch
+    lib()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+    B, rows, _ = mpc_output.shape
+    N = rows - 1
+    rp = torch.zeros((B, N, 3), dtype=torch.float64, device=device); ry = torch.zeros((B, N), dtype=torch.float64, device=device)
+    fl = torch.zeros((B,), dtype=torch.int32, device=device)
+    ks = None if kino_size is None else torch.from_numpy(np.ascontiguousarray(kino_size, dtype=np.int32)).to(device)
+    reference_batch_device(dev(kino_path), dev(time_offset), dev(mpc_output), rp, ry, fl, ks, Ts)
+    torch.cuda.synchronize(device)
+    return rp.cpu().numpy(), ry.cpu().numpy(), fl.cpu().numpy()
+
+
+class Commands:
+    """What command_batch_device / DeviceFleet.commands return (device tensors): cmd [B,S,16] f64 (position 0-2, quaternion x y z w 3-6,
+    linear velocity 7-9, body rates 10-12, linear acceleration 13-15), kind [B,S] int32 (COMMAND_*), finish [B] int32 (finish_mpc_cmd_; written
+    only where a callback touched it), reset_output [B] int32 (1 where PUB_END ran: cold-start that planner; written nowhere else) and
+    status [B] int32, the caller's own tensor updated in place.  Pass the object back as `out` to reuse its buffers: finish and
+    reset_output then carry over from call to call, as the reference's members do."""
+
+    def __init__(self, cmd, kind, finish, reset_output, status):
+        self.cmd, self.kind, self.finish, self.reset_output, self.status = cmd, kind, finish, reset_output, status
+
+
+def command_snapshot_device(z, accept, pre_plan, have_traj, stream=None):
+    """frp_nmpc_command_snapshot on device tensors: where accept [B] int32 != 0, pre_plan [B,N,17] <- z [B,N,17] (pre_mpc_output_ =
+    mpc_output_, nmpc_solver.cpp:527, the solver's rows before the yaw wrap of :531-543) and have_traj [B] int32 <- 1."""
+    import torch
+    B, N, nz = z.shape
+    assert nz == L.NZ and tuple(pre_plan.shape) == (B, N, L.NZ) and tuple(accept.shape) == (B,) and tuple(have_traj.shape) == (B,)
+    assert z.dtype == pre_plan.dtype == torch.float64 and accept.dtype == have_traj.dtype == torch.int32
+    assert z.is_contiguous() and pre_plan.is_contiguous() and accept.is_contiguous() and have_traj.is_contiguous()
+    _check(lib().frp_nmpc_command_snapshot(B, N, tensor_ptr(z), tensor_ptr(accept), tensor_ptr(pre_plan), tensor_ptr(have_traj),
+                                           stream_ptr(stream, z.device)), "frp_nmpc_command_snapshot")
+
+
+def command_batch_device(pre_plan, have_traj, t_cur, status, pub_end, end_pt, odom=None, init_yaw=None, t_yaw=None, out=None, Ts=None,
+                         mass=None, g=None, stream=None):
+    """frp_nmpc_command_batch on device tensors: S consecutive callbacks of NMPCSolver::cmdTrajCallback (nmpc_solver.cpp:865-987) for
+    each of B planners in one launch.  pre_plan [B,N,17] f64 + have_traj [B] int32 (command_snapshot_device), t_cur [B,S] f64 seconds
+    since pre_mpc_start_time_, status [B] int32 CMD_* (updated IN PLACE), pub_end [B] int32, end_pt [B,3] f64; the yaw rotation's odom
+    [B,9] f64, init_yaw [B] f64 and t_yaw [B,S] f64 seconds since change_yaw_time_: all three or none -- with none a planner in
+    CMD_ROTATE_YAW gets kind COMMAND_NO_YAW_INPUT and zeros.  Ts, mass, g: COMMAND_DEFAULTS.  Returns a Commands object (out, when
+    given: nothing is allocated then, so the call can be captured)."""
+    import torch
+    B, N, nz = pre_plan.shape
+    assert nz == L.NZ and t_cur.dim() == 2 and t_cur.shape[0] == B
+    S = t_cur.shape[1]
+    yaw_in = (odom, init_yaw, t_yaw)
+    if any(a is None for a in yaw_in) and not all(a is None for a in yaw_in):
+        raise ValueError("odom, init_yaw and t_yaw go together: all three or none (frp_nmpc_command.odom)")
+    f64 = [(pre_plan, (B, N, L.NZ)), (t_cur, (B, S)), (end_pt, (B, 3))] + ([(odom, (B, 9)), (init_yaw, (B,)), (t_yaw, (B, S))] if odom is not None else [])
+    i32 = [(status, (B,)), (have_traj, (B,)), (pub_end, (B,))]
+    dev = pre_plan.device
+    if out is None:
+        out = Commands(torch.zeros((B, S, COMMAND_STRIDE), dtype=torch.float64, device=dev), torch.zeros((B, S), dtype=torch.int32, device=dev),
+                       torch.zeros((B,), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev), status)
+    out.status = status
+    f64.append((out.cmd, (B, S, COMMAND_STRIDE)))
+    i32 += [(out.kind, (B, S)), (out.finish, (B,)), (out.reset_output, (B,))]
+    for t, shape in f64:
+        assert t.dtype == torch.float64 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (tuple(t.shape), shape, t.dtype)
+    for t, shape in i32:
+        assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (tuple(t.shape), shape, t.dtype)
+    k = dict(COMMAND_DEFAULTS)
+    k.update({n: float(v) for n, v in (("Ts", Ts), ("mass", mass), ("g", g)) if v is not None})
+    c = Command(B, N, S, k["Ts"], k["mass"], k["g"], pre_plan.data_ptr(), t_cur.data_ptr(), status.data_ptr(), have_traj.data_ptr(),
+                pub_end.data_ptr(), end_pt.data_ptr(), tensor_ptr(odom), tensor_ptr(init_yaw), tensor_ptr(t_yaw), out.cmd.data_ptr(), out.kind.data_ptr(),
+                out.finish.data_ptr(), out.reset_output.data_ptr())
+    _check(lib().frp_nmpc_command_batch(ctypes.byref(c), stream_ptr(stream, dev)), "frp_nmpc_command_batch")
+    return out
+
+
+class AstarPlanner:
+    """SURVEY 8f row f-4 (second half): the kinodynamic A* of NMPCSolver::getKinoPath for B planners on the device
+    (frp_nmpc_astar_batch).  `world`: occupancy grid occ[x][y][z] (uint8) + the map / search constants of the reference's launch
+    files (forces_resilient_planner_amd.workloads.astar_world), or an OccupancyMap: the planner then searches the map's own occ
+    buffer (no copy: later inserts are seen) -- pass the local_box of the map's local view to plan().  Outputs stay in HBM: kino_path [B,K,3] / kino_size [B] are what
+    DeviceFleet.references() takes as a per-planner path."""
+
+    def __init__(self, world, B, K=1024, Ts=0.05, device="cuda:0", want_path_nodes=False, allocate_num=None):
+        import torch
+        lib()
+        self.torch = torch
+        self.B, self.K, self.Ts = B, K, Ts
+        self.device = torch.device(device)
+        self.map = world if isinstance(world, OccupancyMap) else None
+        if self.map is not None:
+            assert self.map.device == self.device
+            world = self.map.astar_world()
+        self.world = world
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.occ = self.map.occ if self.map is not None else torch.from_numpy(np.ascontiguousarray(world["occ"], dtype=np.uint8)).to(self.device)
+        self.kino_path = torch.zeros((B, K, 3), **f64)
+        self.kino_size = torch.zeros((B,), **i32)
+        self.status = torch.zeros((B,), **i32)
+        self.stats = torch.zeros((B, 4), **i32)
+        self.path_nodes = torch.zeros((B, ASTAR_MAX_PATH, 11), **f64) if want_path_nodes else None
+        self.allocate_num = int(allocate_num or world["allocate_num"])
+        self._q = [torch.zeros((B, 3), **f64) for _ in range(6)]
+        self._retry = None  # (retry_pt, retry_vel): the start of the repeated search, when it differs (upload(..., retry=...))
+        a = self._args()
+        self.ws_bytes = int(lib().frp_nmpc_astar_workspace_bytes(ctypes.byref(a)))
+        self.ws = torch.empty((self.ws_bytes // 8 + 1,), **f64)
+
+    def _args(self, init=True, local_box=None, active=None, end_pt=None, end_vel=None, external_acc=None):
+        w = self.world
+        a = Astar()
+        a.B = self.B; a.occ = self.occ.data_ptr(); a.grid[:] = tuple(self.occ.shape); a.origin[:] = w["origin"]; a.map_size[:] = w["map_size"]
+        a.resolution = w["resolution"]; a.local_box = local_box.data_ptr() if local_box is not None else None
+        a.ego_r = w["ego_r"]; a.ego_h = w["ego_h"]
+        for k in ("max_tau", "init_max_tau", "max_vel", "max_acc", "w_time", "horizon", "lambda_heu", "tie_breaker", "check_num"):
+            setattr(a, k, w[k])
+        a.allocate_num = self.allocate_num
+        a.start_pt, a.start_vel, a.start_acc, a.end_pt, a.end_vel, a.external_acc = (t.data_ptr() for t in self._q)
+        for name, over in (("end_pt", end_pt), ("end_vel", end_vel), ("external_acc", external_acc)):  # a caller's own [B,3] in place of the uploaded one
+            if over is not None:
+                assert over.dtype == self.torch.float64 and tuple(over.shape) == (self.B, 3) and over.is_contiguous() and over.device == self.device
+                setattr(a, name, over.data_ptr())
+        a.active = active.data_ptr() if active is not None else None
+        a.init_search = 1 if init else 0
+        a.Ts = self.Ts; a.K = self.K
+        a.kino_path = self.kino_path.data_ptr(); a.kino_size = self.kino_size.data_ptr(); a.status = self.status.data_ptr()
+        a.stats = self.stats.data_ptr(); a.path_nodes = self.path_nodes.data_ptr() if self.path_nodes is not None else None
+        a.retry_pt = self._retry[0].data_ptr() if self._retry is not None else None
+        a.retry_vel = self._retry[1].data_ptr() if self._retry is not None else None
+        return a
+
+    def upload(self, start_pt, start_v, start_a, end_pt, end_v, f_ext, retry=None):
+        """retry = (pt [B,3], vel [B,3]): the start of the repeated search (getKinoPath retries from the odometry state,
+        nmpc_solver.cpp:190-193); None: the same start."""
+        t = self.torch
+        cp = lambda dst, src: dst.copy_(src if t.is_tensor(src) else t.from_numpy(np.ascontiguousarray(src, dtype=np.float64)))
+        for dst, src in zip(self._q, (start_pt, start_v, start_a, end_pt, end_v, f_ext)):
+            cp(dst, src)
+        if retry is None:
+            self._retry = None
+        else:
+            if self._retry is None:
+                self._retry = [t.zeros_like(self._q[0]), t.zeros_like(self._q[0])]
+            cp(self._retry[0], retry[0]); cp(self._retry[1], retry[1])
+
+    def plan(self, init=True, local_box=None, stream=None, active=None, end_pt=None, end_vel=None, external_acc=None):
+        """Asynchronous on `stream` (or torch's current stream): every planner's search + retry + getKinoTraj.
+        active: int32 [B] device tensor -- only planners with a non-zero entry search (the others keep their path);
+        a planner whose search ends in NO_PATH keeps its previous path as well.
+        end_pt / end_vel / external_acc: [B,3] f64 device tensors read in place of the uploaded ones (FleetFSM hands over its own
+        end_pt and external_acc: no copy)."""
+        a = self._args(init, local_box, active, end_pt, end_vel, external_acc)
+        _check(lib().frp_nmpc_astar_batch(ctypes.byref(a), tensor_ptr(self.ws), self.ws_bytes, stream_ptr(stream, self.device)),
+               "frp_nmpc_astar_batch")
+
+
+def corridor_batch_device(cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b, poly_nfaces, poly_index, poly_count=None,
+                          cloud_count=None, consts=None, stream=None, grid=None, cut=None, view=None):
+    """frp_nmpc_corridor_batch on device tensors.  cloud [P,3] (shared) or [B,P,3]; ref_pos [B,N,3]; ref_yaw [B,N];
+    ellipsoid [B,N,3,3]; outputs poly_A [B,N,F,3], poly_b [B,N,F], poly_nfaces / poly_index [B,N] int32.
+    cut (OccupancyMap.cut, a CorridorCut): frp_nmpc_corridor_batch_cut -- every planner sees only the points of the SHARED cloud
+    inside its own local box.
+    view (a SharedView, with cloud = None and neither grid nor cloud_count): frp_nmpc_corridor_batch_view -- the view's cloud with its
+    device-side count AND its grid; combines with cut.  A large view (view.cap > CORRIDOR_MAX_POINTS) goes to
+    frp_nmpc_corridor_batch_large with the view's workspace; view.overflow[:B] then tells which planners it refused."""
+    import torch
+    if view is not None:
+        assert cloud is None and grid is None and cloud_count is None, "view= brings its own cloud, grid and count"
+        cloud, grid, cloud_count = view.cloud, view.grid, view.count
+    c = dict(CORRIDOR_DEFAULTS)
+    c.update(consts or {})
+    B, N, F, _ = poly_A.shape
+    per = 1 if cloud.dim() == 3 else 0
+    P = cloud.shape[-2]
+    for t in (cloud, ref_pos, ref_yaw, ellipsoid, poly_A, poly_b):
+        assert t.is_contiguous() and t.dtype == torch.float64
+    assert tuple(ref_pos.shape) == (B, N, 3) and tuple(ellipsoid.shape) == (B, N, 3, 3) and tuple(poly_b.shape) == (B, N, F)
+    assert poly_nfaces.dtype == torch.int32 and poly_index.dtype == torch.int32
+    s = stream_ptr(stream, ref_pos.device)
+    cr = Corridor(B, N, F, P, cloud.data_ptr() if P else None, per, cloud_count.data_ptr() if cloud_count is not None else None,
+                  ref_pos.data_ptr(), ref_yaw.data_ptr(), ellipsoid.data_ptr(), (ctypes.c_double * 3)(*c["bbox"]),
+                  c["seed_len"], c["inflation"], c["offset_x"], poly_A.data_ptr(), poly_b.data_ptr(),
+                  poly_nfaces.data_ptr(), poly_index.data_ptr(), poly_count.data_ptr() if poly_count is not None else None)
+    if grid is not None:
+        assert per == 0, "the grid belongs to a shared cloud"
+        cr.grid_origin = (ctypes.c_double * 3)(*grid.origin); cr.grid_cell = grid.cell; cr.grid_dims = (ctypes.c_int * 3)(*grid.dims)
+        cr.grid_points = grid.points.data_ptr(); cr.grid_index = grid.index.data_ptr(); cr.grid_start = grid.start.data_ptr()
+    if cut is not None:
+        assert per == 0, "the cut belongs to a shared cloud"
+        assert getattr(cut, "_box", None) is None or cut._box.shape[0] == B, "one local_box row per planner"
+    if view is not None and view.cap > CORRIDOR_MAX_POINTS:
+        w = view._large_args(B)
+        _check(lib().frp_nmpc_corridor_batch_large(ctypes.byref(cr), ctypes.byref(cut) if cut is not None else None, ctypes.byref(w),
+                                                   s), "frp_nmpc_corridor_batch_large")
+        return
+    if view is not None:
+        _check(lib().frp_nmpc_corridor_batch_view(ctypes.byref(cr), ctypes.byref(cut) if cut is not None else None, s),
+               "frp_nmpc_corridor_batch_view")
+        return
+    if cut is not None:
+        _check(lib().frp_nmpc_corridor_batch_cut(ctypes.byref(cr), ctypes.byref(cut), s), "frp_nmpc_corridor_batch_cut")
+        return
+    _check(lib().frp_nmpc_corridor_batch(ctypes.byref(cr), s), "frp_nmpc_corridor_batch")
+
+
+def corridor_batch_host(cloud, ref_pos, ref_yaw, ellipsoid, F=CORRIDOR_MAX_F, consts=None, device="cuda:0", grid_cell=None):
+    """Host convenience: numpy in, (poly_index [B,N], poly_A [B,N,F,3], poly_b [B,N,F], poly_nfaces [B,N], poly_count [B]) out."""
+    import torch
+    lib()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+    B, N, _ = ref_pos.shape
+    A = torch.zeros((B, N, F, 3), dtype=torch.float64, device=device); b = torch.zeros((B, N, F), dtype=torch.float64, device=device)
+    nf = torch.zeros((B, N), dtype=torch.int32, device=device); pi = torch.zeros((B, N), dtype=torch.int32, device=device)
+    cnt = torch.zeros((B,), dtype=torch.int32, device=device)
+    d_cloud = dev(cloud).reshape(-1, 3)
+    grid = CloudGrid(d_cloud, grid_cell) if grid_cell else None
+    corridor_batch_device(d_cloud, dev(ref_pos), dev(ref_yaw), dev(ellipsoid), A, b, nf, pi, cnt, consts=consts, grid=grid)
+    torch.cuda.synchronize(device)
+    return pi.cpu().numpy(), A.cpu().numpy(), b.cpu().numpy(), nf.cpu().numpy(), cnt.cpu().numpy()
+
+
+def tube_batch_host(plans, consts=None, device="cuda:0"):
+    """Host convenience: plans [B,N,17] (rows 0..N-1 of the plan deque) -> E [B,N,3,3]."""
+    import torch
+    lib()
+    plans = np.ascontiguousarray(plans, dtype=np.float64)
+    B, N, _ = plans.shape
+    mo = torch.zeros((B, N + 1, L.NZ), dtype=torch.float64, device=device)
+    mo[:, :N] = torch.from_numpy(plans).to(device)
+    E = torch.empty((B, N, 3, 3), dtype=torch.float64, device=device)
+    tube_batch_device(mo, E, consts)
+    torch.cuda.synchronize(device)
+    return E.cpu().numpy()

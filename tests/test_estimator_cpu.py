@@ -290,7 +290,7 @@ def _host_vehicle(trace):
 @pytest.mark.parametrize("trace", [False, True])
 def test_vehicle_without_an_estimator_makes_the_calls_it_made_before_and_with_one_feeds_it(monkeypatch, trace):
     rec = _Recorder()
-    monkeypatch.setattr(solver, "lib", lambda: rec)
+    monkeypatch.setattr("forces_resilient_planner_amd.flight.lib", lambda: rec)
     veh, cmds, stream, torch = _host_vehicle(trace)
     assert veh.estimator is None
     x0, mask = torch.zeros((3, 9), dtype=torch.float64), torch.ones((3,), dtype=torch.int32)

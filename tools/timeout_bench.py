@@ -68,12 +68,13 @@ def run(reps=21, tick_budget_ms=0.5):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import full_tick_bench as FT
     base = FT.run(4096, 10, 20000, 0.5, 0)
-    orig = solver.default_options
-    solver.default_options = lambda **kw: orig(**{"timeout": tick_budget_ms * 1e-3, **kw})
+    from forces_resilient_planner_amd import batch  # (DeviceSolver looks default_options up in its own module)
+    orig = batch.default_options
+    batch.default_options = lambda **kw: orig(**{"timeout": tick_budget_ms * 1e-3, **kw})
     try:
         bud = FT.run(4096, 10, 20000, 0.5, 0)
     finally:
-        solver.default_options = orig
+        batch.default_options = orig
     pick = lambda r: {k: r[k] for k in ("ms_per_tick", "converged_frac", "mean_iters")}
     out["full_tick_4096"] = {"no_budget": pick(base), f"budget_{tick_budget_ms}ms": pick(bud)}
     return out
