@@ -11,7 +11,7 @@
  *       plan_manage/solver/final/FORCESNLPsolver_final/include/FORCESNLPsolver_final.h:317-323
  *     called at plan_manage/src/forces_normal.cpp:139 and forces_final.cpp:138.
  *     A caller compiled against the reference's own headers links against this library unchanged
- *     (sizes/offsets are asserted in csrc/frp_capi.hip: params 23600 B, output 2720 B, info 136 B).
+ *     (sizes/offsets are asserted in csrc/frp_capi.hip, the call itself is csrc/frp_dropin.hip: params 23600 B, output 2720 B, info 136 B).
  *
  * (2) A batched, horizon-generic API (not in the reference, needed by BASELINE.json configs[1..4]):
  *     B independent problems, device-resident buffers, per-problem exit flags.

@@ -869,6 +869,60 @@ def test_two_host_batches_in_flight_give_the_plans_of_the_blocking_call():
             solver.host_unregister(*r)
 
 
+def test_host_paths_agree_with_one_device_launch_at_odd_sizes_with_per_problem_models():
+    """The odd corners of a chunk's device block: B = 37 and N = 7 are odd, so the face counts and the per-problem models behind the
+    doubles end off a double boundary, 12 live corridor rows of 15 make every host path pack, and the models ride along with registered
+    buffers.  The reference is ONE frp_nmpc_solve_batch launch on device-resident arrays in the caller's 15-row layout (no chunk, no
+    packing, no gather); the staged call, the staged call cut into chunks of 5, 9 and 23, the blocking call on registered buffers and the
+    pipelined begin / wait give its plans, flags, iteration counts and diagnostics bit for bit."""
+    import torch
+    B, N, M, LIVE = 37, 7, 15, 12
+    w = workloads.config3(B, N=N, M=M)
+    p = w["params"].reshape(B, N, -1).copy()   # rows [10 | A (M x 3) | b (M)]: the rows from LIVE on become padding
+    p[:, :, 10 + 3 * LIVE:10 + 3 * M] = 0.0; p[:, :, 10 + 3 * M + LIVE:] = 0.0
+    w = dict(w, params=p, nfaces=np.minimum(w["nfaces"], LIVE).astype(np.int32), models=np.random.default_rng(37).integers(0, 2, B).astype(np.int32))
+    w = {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in w.items()}
+    assert w["nfaces"].max() == LIVE < M  # (the packing runs)
+    ds = solver.DeviceSolver(B, N, M, LIVE, w["model"])
+    ds.upload(w)
+    ds.models = torch.from_numpy(w["models"]).to(ds.device)
+    ds.solve(); torch.cuda.synchronize()
+    ref = (ds.z.cpu().numpy(), ds.exitflag.cpu().numpy(), ds.iters.cpu().numpy(), ds.info.cpu().numpy())
+    for md in (0, 1):
+        assert np.any(ref[1][w["models"] == md] == 1), md  # (agreement is not agreement on failures)
+
+    def same(got, what):
+        for name, a, b in zip(("z", "exitflag", "iterations", "diagnostics"), ref, got):
+            assert a.shape == b.shape and a.tobytes() == b.tobytes(), (what, name)
+
+    same(solver.solve_batch_host(w), "staged")
+    os.environ["FRP_HOST_SPLIT"] = "5,9"
+    try:
+        same(solver.solve_batch_host(w), "staged in chunks of 5, 9, 23")
+    finally:
+        os.environ.pop("FRP_HOST_SPLIT", None)
+    arena, used = np.zeros(1 << 19, dtype=np.uint8), [0]  # ONE registered range holds every array: arrays this small would share pages
+
+    def pinned(a):
+        lo = used[0]; used[0] = lo + (a.nbytes + 63) // 64 * 64
+        v = arena[lo:lo + a.nbytes].view(a.dtype).reshape(a.shape); v[...] = a
+        return v
+
+    wr = {k: (pinned(v) if isinstance(v, np.ndarray) else v) for k, v in w.items()}
+    out = tuple(pinned(np.full_like(a, -7)) for a in ref)
+    assert used[0] <= arena.nbytes
+    solver.host_register(arena)
+    try:
+        solver.solve_batch_host(wr, out=out)
+        same(out, "registered, blocking")
+        for o in out:
+            o[...] = -7
+        solver.solve_batch_host_wait(solver.solve_batch_host_begin(wr, out))
+        same(out, "registered, begin / wait")
+    finally:
+        solver.host_unregister(arena)
+
+
 def test_host_registrations_are_counted_and_sub_ranges_are_aliases():
     """frp_nmpc_host_register: the same buffer registered twice is unpinned by its second unregistration; a sub-range of a
     registered buffer is an alias that is unregistered by its own pointer and keeps the enclosing range alive; a range that partly overlaps

@@ -20,7 +20,7 @@ __global__ void cp(const T *__restrict__ src, T *__restrict__ dst, size_t n)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 // the gather's pattern: of every 130-double parameter row the ten leading slots + 18 A entries (doubles 0..27) and 6 b entries (100..105)
-// MODE 0: output element -> input element, as frp_capi.hip's gather_inputs_kernel does; 1: lane = (row, slot) with 40 slots per row: the 64-byte
+// MODE 0: output element -> input element, as frp_host_batch.hip's gather_inputs_kernel does; 1: lane = (row, slot) with 40 slots per row: the 64-byte
 // lines that cover the two segments, read whole
 template <int MODE>
 __global__ void gather(const double *__restrict__ src, double *__restrict__ dst, size_t rows)
