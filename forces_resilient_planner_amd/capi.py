@@ -192,6 +192,12 @@ class EstimatorArgs(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("meas", "thrust", "f_hat", "y_prev", "count", "force", "fresh", "residual", "status")]
 
 
+class FlightRecordArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int)] + [(n, ctypes.c_void_p) for n in ("p_prev", "have_prev", "track_max2", "track_sum2", "track_n", "path_len", "speed_max2",
+                                                                        "samples", "flown", "bad", "sat_samples", "sat_bits", "periods", "ticks_run",
+                                                                        "ticks_converged", "result_hist", "state_hist", "first_arrival")]
+
+
 class OccMapBody(ctypes.Structure):
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -219,7 +225,7 @@ EXTFUNC = ctypes.CFUNCTYPE(None, c_double_p, c_double_p, c_double_p, c_double_p,
 C_TYPES = {cls: (ctype, header) for header, group in {
     "frp_nmpc.h": {Options: "frp_nmpc_options", Batch: "frp_nmpc_batch", Pack: "frp_nmpc_pack", Tube: "frp_nmpc_tube", Corridor: "frp_nmpc_corridor",
                    CorridorCut: "frp_nmpc_corridor_cut", Reference: "frp_nmpc_reference", Astar: "frp_nmpc_astar", OccMap: "frp_nmpc_occmap",
-                   OccMapView: "frp_nmpc_occmap_view", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
+                   OccMapView: "frp_nmpc_occmap_view", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
     "frp_nmpc_occmap_fuse.h": {OccMapFuse: "frp_nmpc_occmap_fuse"}, "frp_nmpc_occmap_fuse_batch.h": {OccMapFuseBatch: "frp_nmpc_occmap_fuse_batch"},
     "frp_nmpc_occmap_fuse_points.h": {OccMapFusePoints: "frp_nmpc_occmap_fuse_points"}, "frp_nmpc_occmap_check.h": {OccMapBody: "frp_nmpc_occmap_body"},
     "frp_nmpc_occmap_render.h": {OccMapRender: "frp_nmpc_occmap_render"}, "frp_nmpc_occmap_render_scan.h": {OccMapRenderScan: "frp_nmpc_occmap_render_scan"},
@@ -248,6 +254,11 @@ VEHICLE_STATE, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_MAX_SUB = 9, 8, 
 ODOM_WORLD, ODOM_BODY = 1, 2  # odometryCallback, odometryTransCallback
 VEHICLE_SAT_THRUST_LO, VEHICLE_SAT_THRUST_HI, VEHICLE_SAT_ROLL, VEHICLE_SAT_PITCH, VEHICLE_SAT_RATE0, VEHICLE_SAT_ZERO_ACC, VEHICLE_SAT_YAW_WRAP = 1, 2, 4, 8, 16, 128, 256
 EST_SKIPPED, EST_FIRST, EST_ABSORBED = 0, 1, 2  # status[b][s]
+FLIGHT_GROUP, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_MAX_EDGES, FLIGHT_SAT_MASK, FLIGHT_SUM_INTS, FLIGHT_SUM_F64 = 256, 6, 6, 64, 127, 19, 6
+FLIGHT_I_SELECTED, FLIGHT_I_ARRIVED, FLIGHT_I_WITH_BAD, FLIGHT_I_WITH_HITS, FLIGHT_I_SAMPLES, FLIGHT_I_FLOWN, FLIGHT_I_TRACK_N, FLIGHT_I_BAD, \
+    FLIGHT_I_SAT_SAMPLES, FLIGHT_I_PERIODS, FLIGHT_I_TICKS_RUN, FLIGHT_I_TICKS_CONVERGED, FLIGHT_I_RESULT = range(13)  # out_i of frp_nmpc_flight_summary
+FLIGHT_I_ARRIVAL_SUM = 18  # (FLIGHT_I_RESULT ... + 5 are result_hist's columns)
+FLIGHT_F_TRACK_MAX2, FLIGHT_F_SPEED_MAX2, FLIGHT_F_PATH_MAX, FLIGHT_F_MIN_CLEAR, FLIGHT_F_TRACK_SUM2, FLIGHT_F_PATH_SUM = range(6)  # out_f
 
 # name here -> macro in include/*.h, for every integer above (one defined below this line is not checked): FRP_<name>, but for three
 MACROS = {n: n if n.startswith("FRP_") else "FRP_" + n for n, v in list(globals().items()) if n.isupper() and type(v) is int}
@@ -258,6 +269,7 @@ MACROS["ABI_VERSION"] = "FRP_NMPC_ABI_VERSION"
 _i, _d, _z, _v = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 _P = ctypes.POINTER
 _batch, _map, _cor, _cut, _fsm, _body = [_P(Batch), _P(Options)], _P(OccMap), _P(Corridor), _P(CorridorCut), _P(Fsm), _P(OccMapBody)
+_rec = _P(FlightRecordArgs)
 _forces = (_i, [_P(ForcesParams), _P(ForcesOutput), _P(ForcesInfo), _v, _v])  # (FILE *, extfunc: an EXTFUNC or None, which only c_void_p takes)
 _BY_HEADER = {
     "frp_nmpc.h": {"frp_nmpc_abi_version": (_i, []),
@@ -300,7 +312,12 @@ _BY_HEADER = {
         "frp_nmpc_version": (ctypes.c_char_p, []),
         "frp_nmpc_device_count": (_i, []),
         "FORCESNLPsolver_normal_solve": _forces,
-        "FORCESNLPsolver_final_solve": _forces},
+        "FORCESNLPsolver_final_solve": _forces,
+        "frp_nmpc_flight_record_samples": (_i, [_rec, _i, _v, _i, _v, _v, _v, _v, _v]),
+        "frp_nmpc_flight_record_period": (_i, [_rec, _v, _v, _v, _v, _v, _v]),
+        "frp_nmpc_flight_record_reset": (_i, [_rec, _v, _v, _v]),
+        "frp_nmpc_flight_summary_workspace_bytes": (_z, [_i]),
+        "frp_nmpc_flight_summary": (_i, [_rec, _v, _v, _v, _i, _v, _v, _v, _v, _v, _z, _v])},
     "frp_nmpc_occmap_fuse.h": {"frp_nmpc_occmap_fuse_workspace_bytes": (_z, [_map, _P(OccMapFuse)]),
         "frp_nmpc_occmap_fuse_depth": (_i, [_map, _P(OccMapFuse), _v, _z, _v, _z, _v])},
     "frp_nmpc_occmap_fuse_batch.h": {"frp_nmpc_occmap_fuse_batch_workspace_bytes": (_z, [_map, _P(OccMapFuseBatch)]),

@@ -1,10 +1,13 @@
 """A fleet in flight, on the device: the state machine that drives the planners (FleetFSM), the vehicle that flies their commands
-(Vehicle) and the estimator that tells them what it felt (ForceEstimator) (frp_nmpc_fsm_*, _vehicle_*, _estimator_*)."""
+(Vehicle), the estimator that tells them what it felt (ForceEstimator) and the record of what the fleet did (FlightRecord)
+(frp_nmpc_fsm_*, _vehicle_*, _estimator_*, _flight_*)."""
+import collections
 import ctypes
 
 from . import layout as L
-from .capi import (COMMAND_STRIDE, FSM_INIT, ODOM_BODY, ODOM_WORLD, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs,
-                   Fsm, FsmExecIn, VehicleArgs, _check, checked_ptr, lib, stream_ptr, tensor_ptr)
+from .capi import (COMMAND_STRIDE, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, ODOM_BODY, ODOM_WORLD,
+                   TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
+                   checked_ptr, lib, stream_ptr, tensor_ptr)
 from .fleet import TickState
 from .occmap import SafetyCheck
 from .planning import COMMAND_DEFAULTS
@@ -160,6 +163,129 @@ class ForceEstimator:
         m = checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None
         state = map(tensor_ptr, (self.f_hat, self.y_prev, self.count, self.force, self.fresh))
         _check(lib().frp_nmpc_estimator_reset(self.B, m, *state, stream_ptr(stream, v.x)), "frp_nmpc_estimator_reset")
+
+
+FlightSummary = collections.namedtuple("FlightSummary", "ints floats hist")
+
+
+class FlightRecord:
+    """What every vehicle of a Vehicle did, kept on the device (include/frp_nmpc.h section 14, frp_nmpc_flight_*): how well it tracked, how
+    hard it worked, how often it replanned, arrived or gave up -- and the fleet's figures from those.  It hooks into nothing: the caller
+    launches update_samples() and update_period() after FleetFSM.period(..., vehicle=...), inside the same captured graph if they wish,
+    as with a FlightClearance.  No reference counterpart; tests/flight_record_oracle.py is the statement the device is held to, to the bit.
+    Owns, [B] device tensors unless noted: p_prev [B,3] f64 and have_prev i32 (the position the controller saw when it took the next
+    sample), track_max2 / track_sum2 f64 and track_n i32 (squared tracking errors: p_prev against the sample's setpoint, over samples of
+    kind COMMAND_TRAJ or COMMAND_END), path_len and speed_max2 f64, samples / flown / bad / sat_samples / sat_bits i32, periods / ticks_run /
+    ticks_converged i32, result_hist [B,6] i32 (tick.result 1, 0, -1, -2, -3, other), state_hist [B,6] i32 (FSM_*), first_arrival i32 (-1
+    until tick.result == 0 was seen: the zero-based period).  update_period() sees period ENDS only: with fsm_steps > 1 a state visited
+    and left inside a period is not counted.
+    clearance: a FlightClearance of the same vehicle, or None; summary() folds its min_clear and hits in."""
+
+    I32_FIELDS = ("have_prev", "track_n", "samples", "flown", "bad", "sat_samples", "sat_bits", "periods", "ticks_run", "ticks_converged", "first_arrival")
+    F64_FIELDS = ("track_max2", "track_sum2", "path_len", "speed_max2")
+
+    def __init__(self, vehicle, clearance=None):
+        t = vehicle.torch
+        dev = vehicle.x.device
+        if clearance is not None and (clearance.B != vehicle.B or clearance.min_clear.device != dev):
+            raise ValueError("FlightRecord: the clearance belongs to another fleet or device")
+        self.torch, self.vehicle, self.clearance, self.B = t, vehicle, clearance, vehicle.B
+        f64, i32, i64 = dict(dtype=t.float64, device=dev), dict(dtype=t.int32, device=dev), dict(dtype=t.int64, device=dev)
+        self.p_prev = t.zeros((self.B, 3), **f64)
+        for n in self.F64_FIELDS:
+            setattr(self, n, t.zeros((self.B,), **f64))
+        for n in self.I32_FIELDS:
+            setattr(self, n, t.zeros((self.B,), **i32))
+        self.first_arrival.fill_(-1)
+        self.result_hist, self.state_hist = t.zeros((self.B, FLIGHT_RESULT_BINS), **i32), t.zeros((self.B, FLIGHT_STATE_BINS), **i32)
+        # summary()'s own buffers: a capture of it allocates nothing
+        self.sum_ints, self.sum_floats = t.zeros((FLIGHT_SUM_INTS,), **i64), t.zeros((FLIGHT_SUM_F64,), **f64)
+        self.sum_hist = t.zeros((FLIGHT_MAX_EDGES + 1,), **i64)
+        self._ws_bytes = int(lib().frp_nmpc_flight_summary_workspace_bytes(self.B))
+        self._ws = t.zeros((self._ws_bytes // 8,), **i64)
+
+    def struct(self):
+        return FlightRecordArgs(self.B, *[getattr(self, n).data_ptr() for n, _ in FlightRecordArgs._fields_[1:]])
+
+    def arrays(self):
+        """Every array on the host (a synchronising read-back: tests and logs)."""
+        return {n: getattr(self, n).cpu().numpy() for n, _ in FlightRecordArgs._fields_[1:]}
+
+    def update_samples(self, commands, trace=None, sat=None, active=None, stream=None):
+        """frp_nmpc_flight_record_samples: the S samples of a Commands object (cmd [B,S,16], kind [B,S]) and of trace [B,S,stride >= 6]
+        (float64; None: vehicle.trace, or else the attached estimator's meas -- the fallback Vehicle.step writes to) taken in order.
+        sat [B,S] int32 or None: the saturation words (None with the vehicle's own trace: vehicle.sat; None otherwise: not counted).
+        active [B] int32 or None: where it is 0 nothing of that vehicle changes."""
+        t, v = self.torch, self.vehicle
+        if trace is None:
+            trace = v.trace if v.trace is not None else v.estimator.meas if v.estimator is not None else None
+            if trace is None:
+                raise ValueError("FlightRecord.update_samples: this Vehicle keeps no trace (trace=True) and has no ForceEstimator attached; pass trace=")
+            if sat is None and trace is v.trace:
+                sat = v.sat
+        assert t.is_tensor(trace) and trace.dim() == 3, "trace is a [B, S, stride] tensor"
+        S, stride = int(trace.shape[1]), int(trace.shape[2])
+        if S < 1 or stride < 6:
+            raise ValueError("FlightRecord.update_samples: trace is [B, S >= 1, stride >= 6]")
+        r = self.struct()
+        _check(lib().frp_nmpc_flight_record_samples(ctypes.byref(r), S, checked_ptr(v.x, trace, t.float64, (self.B, S, stride)), stride,
+                                                    checked_ptr(v.x, commands.cmd, t.float64, (self.B, S, COMMAND_STRIDE)),
+                                                    checked_ptr(v.x, commands.kind, t.int32, (self.B, S)),
+                                                    checked_ptr(v.x, sat, t.int32, (self.B, S)) if sat is not None else None,
+                                                    checked_ptr(v.x, active, t.int32, (self.B,)) if active is not None else None,
+                                                    stream_ptr(stream, v.x)), "frp_nmpc_flight_record_samples")
+
+    def update_period(self, fsm, active=None, stream=None):
+        """frp_nmpc_flight_record_period on a FleetFSM as a period left it: fsm.state and its tick's gate, result and exit_code."""
+        t, v, tk = self.torch, self.vehicle, fsm.tick
+        r = self.struct()
+        p = lambda a: checked_ptr(v.x, a, t.int32, (self.B,))
+        _check(lib().frp_nmpc_flight_record_period(ctypes.byref(r), p(fsm.state), p(tk.gate), p(tk.result), p(tk.exit_code),
+                                                   p(active) if active is not None else None, stream_ptr(stream, v.x)), "frp_nmpc_flight_record_period")
+
+    def reset(self, mask=None, x=None, stream=None):
+        """frp_nmpc_flight_record_reset: where mask [B] int32 != 0 (None: everywhere) everything <- 0, first_arrival <- -1 and, with x
+        [B,9] (vehicle.x: where the flight starts), p_prev <- its position, have_prev <- 1; without x have_prev <- 0 and the first sample
+        is not tracked."""
+        t, v = self.torch, self.vehicle
+        r = self.struct()
+        _check(lib().frp_nmpc_flight_record_reset(ctypes.byref(r), checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None,
+                                                  checked_ptr(v.x, x, t.float64, (self.B, VEHICLE_STATE)) if x is not None else None,
+                                                  stream_ptr(stream, v.x)), "frp_nmpc_flight_record_reset")
+
+    def summary(self, mask=None, edges=None, stream=None):
+        """frp_nmpc_flight_summary over the vehicles with mask [B] int32 != 0 (None: all): a FlightSummary of DEVICE tensors, this object's
+        own (the next call overwrites them): ints [19] int64 (FLIGHT_I_*), floats [6] float64 (FLIGHT_F_*) and hist [n_edges + 1] int64,
+        the histogram of the per-vehicle mean squared tracking error over the ascending edges [n_edges <= 64] (a float64 device tensor, or
+        None: one bin).  The sums are added in a fixed order (the header states it): the same bits on every run."""
+        t, v, c = self.torch, self.vehicle, self.clearance
+        n = 0 if edges is None else int(edges.shape[0])
+        if n > FLIGHT_MAX_EDGES:
+            raise ValueError(f"FlightRecord.summary: at most {FLIGHT_MAX_EDGES} edges")
+        r = self.struct()
+        _check(lib().frp_nmpc_flight_summary(ctypes.byref(r), tensor_ptr(c.min_clear) if c is not None else None, tensor_ptr(c.hits) if c is not None else None,
+                                             checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None, n,
+                                             checked_ptr(v.x, edges, t.float64, (n,)) if n else None, tensor_ptr(self.sum_ints), tensor_ptr(self.sum_floats),
+                                             tensor_ptr(self.sum_hist), tensor_ptr(self._ws), self._ws_bytes, stream_ptr(stream, v.x)), "frp_nmpc_flight_summary")
+        return FlightSummary(self.sum_ints, self.sum_floats, self.sum_hist[:n + 1])
+
+    # the square roots are the host's (synchronising read-backs, one value per vehicle)
+    @property
+    def track_rms(self):
+        """sqrt(track_sum2 / track_n) per vehicle, NaN where nothing was tracked."""
+        import numpy as np
+        s, n = self.track_sum2.cpu().numpy(), self.track_n.cpu().numpy()
+        return np.sqrt(np.divide(s, n, out=np.full(self.B, np.nan), where=n > 0))
+
+    @property
+    def track_max(self):
+        import numpy as np
+        return np.sqrt(self.track_max2.cpu().numpy())
+
+    @property
+    def speed_max(self):
+        import numpy as np
+        return np.sqrt(self.speed_max2.cpu().numpy())
 
 
 class FleetFSM:

@@ -701,7 +701,8 @@ class FlightClearance:
     voxel, outside the map or not finite) and samples [B] int32.  It hooks into nothing: the caller launches update() after
     Vehicle.step / FleetFSM.period(..., vehicle=...), inside the same captured graph if they wish.  The positions are the TRUE plant
     states of the vehicle's trace, and the numbers are distances between voxel centres (include/frp_nmpc_occmap_distance.h); the
-    body's radius is the caller's to subtract.  Tracking error and the rest of a flight record are not kept."""
+    body's radius is the caller's to subtract.  Tracking error and the rest of a flight record are flight.FlightRecord's, whose
+    summary() folds this object's min_clear and hits in (FlightRecord(vehicle, clearance=this))."""
 
     def __init__(self, vehicle, field):
         t = vehicle.torch

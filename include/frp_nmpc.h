@@ -662,6 +662,127 @@ int FORCESNLPsolver_normal_solve(frp_forces_params *params, frp_forces_output *o
 int FORCESNLPsolver_final_solve(frp_forces_params *params, frp_forces_output *output, frp_forces_info *info,
                                 FILE *fs, frp_forces_extfunc evalextfunctions);
 
+/* ---- (14) the flight record: tracking error, effort, events and a fleet summary, kept on the device ---- */
+/* What a fleet flown by sections (9)-(13) did, accumulated per vehicle from the arrays those sections leave in device memory, and the
+ * fleet's figures from the per-vehicle ones -- beside frp_nmpc_occmap_clearance_trace (frp_nmpc_occmap_distance.h), which keeps the
+ * clearance.  NO REFERENCE COUNTERPART: the reference logs nothing of the kind.  tests/flight_record_oracle.py is the executable
+ * statement, and the device agrees with it to the bit (csrc/frp_flight_record.hip is built without contraction).
+ * Every call: every pointer is DEVICE memory, asynchronous on `stream`, nothing allocated, nothing read back, capturable into a hipGraph
+ * with the period; no kernel waits on another workgroup.  FRP_ERR_ARG before any launch, FRP_ERR_NO_DEVICE without a device.  Nothing
+ * calls these for the caller: they are launched after a period, as frp_nmpc_occmap_clearance_trace is. */
+#define FRP_FLIGHT_GROUP 256      /* vehicles per workgroup: the unit of the summary's summation order            */
+#define FRP_FLIGHT_RESULT_BINS 6  /* result_hist[b][k]: result 1, 0, -1, -2, -3, anything else                    */
+#define FRP_FLIGHT_STATE_BINS 6   /* state_hist[b][s]: FRP_FSM_* 0 ... 5                                          */
+#define FRP_FLIGHT_MAX_EDGES 64   /* histogram edges of frp_nmpc_flight_summary                                   */
+#define FRP_FLIGHT_SAT_MASK 127   /* THRUST_LO | THRUST_HI | ROLL | PITCH | RATE0 << 0, 1, 2 of FRP_VEHICLE_SAT_* */
+/* out_i of frp_nmpc_flight_summary */
+#define FRP_FLIGHT_SUM_INTS 19
+#define FRP_FLIGHT_I_SELECTED 0        /* vehicles selected                                   */
+#define FRP_FLIGHT_I_ARRIVED 1         /* ... with first_arrival >= 0                         */
+#define FRP_FLIGHT_I_WITH_BAD 2        /* ... with bad > 0                                    */
+#define FRP_FLIGHT_I_WITH_HITS 3       /* ... with hits > 0 (0 without clearance arrays)      */
+#define FRP_FLIGHT_I_SAMPLES 4         /* sums over the selected vehicles, in this order:     */
+#define FRP_FLIGHT_I_FLOWN 5
+#define FRP_FLIGHT_I_TRACK_N 6
+#define FRP_FLIGHT_I_BAD 7
+#define FRP_FLIGHT_I_SAT_SAMPLES 8
+#define FRP_FLIGHT_I_PERIODS 9
+#define FRP_FLIGHT_I_TICKS_RUN 10
+#define FRP_FLIGHT_I_TICKS_CONVERGED 11
+#define FRP_FLIGHT_I_RESULT 12         /* 12 ... 17: the six columns of result_hist           */
+#define FRP_FLIGHT_I_ARRIVAL_SUM 18    /* first_arrival summed over those that arrived        */
+/* out_f of frp_nmpc_flight_summary */
+#define FRP_FLIGHT_SUM_F64 6
+#define FRP_FLIGHT_F_TRACK_MAX2 0      /* max of track_max2                                   */
+#define FRP_FLIGHT_F_SPEED_MAX2 1      /* max of speed_max2                                   */
+#define FRP_FLIGHT_F_PATH_MAX 2        /* max of path_len                                     */
+#define FRP_FLIGHT_F_MIN_CLEAR 3       /* min of min_clear, +inf without clearance arrays     */
+#define FRP_FLIGHT_F_TRACK_SUM2 4      /* sum of track_sum2, in the stated order              */
+#define FRP_FLIGHT_F_PATH_SUM 5        /* sum of path_len, in the stated order                */
+
+typedef struct frp_nmpc_flight_record {
+    int B;                 /* vehicles                                                                                          */
+    /* every array in and out                                                                                                   */
+    double *p_prev;        /* [B][3] the position before the next sample: what the controller saw when it took that sample      */
+    int *have_prev;        /* [B] whether p_prev is valid                                                                       */
+    double *track_max2;    /* [B] largest squared tracking error                                                                */
+    double *track_sum2;    /* [B] sum of squared tracking errors                                                                */
+    int *track_n;          /* [B] tracked samples                                                                               */
+    double *path_len;      /* [B] length of the flown path                                                                      */
+    double *speed_max2;    /* [B] largest squared speed                                                                         */
+    int *samples;          /* [B] samples seen                                                                                  */
+    int *flown;            /* [B] ... of kind FRP_COMMAND_TRAJ or FRP_COMMAND_END                                               */
+    int *bad;              /* [B] ... that were bad (below)                                                                     */
+    int *sat_samples;      /* [B] ... with a bit of FRP_FLIGHT_SAT_MASK in their sat word                                       */
+    int *sat_bits;         /* [B] OR of every sat word seen                                                                     */
+    int *periods;          /* [B] period ends seen                                                                              */
+    int *ticks_run;        /* [B] ... with gate == FRP_TICK_RUN                                                                 */
+    int *ticks_converged;  /* [B] ... and exit_code == 1                                                                        */
+    int *result_hist;      /* [B][FRP_FLIGHT_RESULT_BINS]                                                                       */
+    int *state_hist;       /* [B][FRP_FLIGHT_STATE_BINS]                                                                        */
+    int *first_arrival;    /* [B] the zero-based period of the first result == 0, -1 until then                                 */
+} frp_nmpc_flight_record;
+
+/* S samples of every vehicle taken in order, ONE launch, one thread per vehicle, FRP_FLIGHT_GROUP per workgroup.
+ * trace [B][S][stride >= 6]: position 0-2, velocity 3-5 AFTER each sample (stride 9: frp_nmpc_vehicle.trace, frp_nmpc_estimator.meas);
+ * cmd [B][S][FRP_COMMAND_STRIDE] and kind [B][S]: frp_nmpc_command's; sat [B][S] (frp_nmpc_vehicle.sat) or NULL; active [B] or NULL:
+ * where active[b] == 0 nothing of vehicle b changes and nothing of it is read.
+ * Per sample s, with p0 = p_prev (the state the controller saw), p1 = trace 0-2, v1 = trace 3-5, c = cmd 0-2, and `tracked` standing for
+ * kind == FRP_COMMAND_TRAJ or FRP_COMMAND_END:
+ *   samples += 1;
+ *   with sat:  sat_bits |= sat[b][s];  sat_samples += 1 where sat[b][s] & FRP_FLIGHT_SAT_MASK;
+ *   bad = have_prev and (any of p0, p1, v1 is not finite, or tracked and any of c is not finite)  -- without have_prev no sample is bad;
+ *   bad:       bad += 1, and of the lines below only the last two;
+ *   not bad, have_prev:            d = p1 - p0,  path_len += sqrt((dx dx + dy dy) + dz dz);
+ *   not bad, have_prev, tracked:   e = p0 - c,  e2 = (ex ex + ey ey) + ez ez,  track_sum2 += e2,  track_max2 = e2 > track_max2 ? e2 :
+ *                                  track_max2,  track_n += 1;
+ *   not bad:                       v2 = (vx vx + vy vy) + vz vz,  speed_max2 = v2 > speed_max2 ? v2 : speed_max2  (a NaN never enters);
+ *   tracked, bad or not:           flown += 1;
+ *   always, last:                  p_prev <- p1, have_prev <- 1.
+ * Every product, sum and square root is rounded on its own, in the order written.  The tracking error is the controller's own position
+ * error at the instant of the callback: the state BEFORE the sample against the sample's setpoint.  That is why p_prev is carried; the
+ * state after the sample against the same setpoint would carry a bias of |v| dt_cmd.
+ * FRP_ERR_ARG: rec, an array of it, trace, cmd or kind NULL; B < 0; S < 1; stride < 6; B * S * stride beyond 2^31 - 1.  B == 0 launches
+ * nothing. */
+int frp_nmpc_flight_record_samples(const frp_nmpc_flight_record *rec, int S, const double *trace, int stride, const double *cmd, const int *kind,
+                                   const int *sat, const int *active, void *stream);
+
+/* One period END of every vehicle, one launch: fsm_state (frp_nmpc_fsm.state), gate, result and exit_code (frp_nmpc_tick's), [B] each,
+ * as they stand after the period.  It sees period ends ONLY: with several frp_nmpc_fsm_exec_* steps in a period a state visited and left
+ * inside it is not counted.  Where active (as above) lets it:
+ *   periods += 1;
+ *   gate == FRP_TICK_RUN:  ticks_run += 1, and ticks_converged += 1 where also exit_code == 1;
+ *   result_hist[k] += 1 with k = 0 ... 5 for result 1, 0, -1, -2, -3 and anything else (FRP_TICK_RESULT_IDLE included);
+ *   state_hist[fsm_state] += 1 for fsm_state in 0 ... 5, nothing for another value;
+ *   result == 0 (solveNMPC's "arrived") and first_arrival < 0:  first_arrival <- periods - 1.
+ * FRP_ERR_ARG: rec, an array of it or one of the four arrays NULL; B < 0.  B == 0 launches nothing. */
+int frp_nmpc_flight_record_period(const frp_nmpc_flight_record *rec, const int *fsm_state, const int *gate, const int *result,
+                                  const int *exit_code, const int *active, void *stream);
+
+/* Where mask[b] != 0 (mask == NULL: everywhere): every counter, sum, maximum and histogram <- 0, sat_bits <- 0, first_arrival <- -1, and
+ * with x [B][9] (frp_nmpc_vehicle.x's layout) p_prev <- x 0-2, have_prev <- 1; with x == NULL have_prev <- 0 (p_prev stays, unread).
+ * FRP_ERR_ARG: rec or an array of it NULL; B < 0.  B == 0 launches nothing. */
+int frp_nmpc_flight_record_reset(const frp_nmpc_flight_record *rec, const int *mask, const double *x, void *stream);
+
+/* The fleet's figures over the vehicles with mask[b] != 0 (mask == NULL: all), TWO launches, the same bits on every run.
+ * min_clear [B] f64 and hits [B] i32: frp_nmpc_occmap_clearance_trace's arrays, or both NULL.
+ * out_i [FRP_FLIGHT_SUM_INTS] long long and out_f [FRP_FLIGHT_SUM_F64] double: FRP_FLIGHT_I_* / FRP_FLIGHT_F_* above (the maxima start at
+ * 0, the minimum at +inf, v > max / v < min decide: a NaN never enters).
+ * hist [n_edges + 1] long long: over the selected vehicles with track_n > 0, m = track_sum2 / (double)track_n falls in bin
+ * i = the number of edges with edges[j] <= m, so bin i holds edges[i - 1] <= m < edges[i] for ascending edges [n_edges] (a value on an
+ * edge belongs to the bin above it; an m that is a NaN falls in bin 0).
+ * THE ORDER of the two float sums (FRP_FLIGHT_F_TRACK_SUM2, _PATH_SUM): workgroup g takes vehicles 256 g ... 256 g + 255 as v[0 ... 255],
+ * an unselected or out-of-range lane being +0.0; for stride = 128, 64, ..., 1:  v[i] += v[i + stride] for i < stride; v[0] is the
+ * partial.  The second launch is ONE workgroup; it adds the partials of every figure sequentially from 0.0 (0, +inf for a maximum, the
+ * minimum) in workgroup order.  Integers and bins are exact whatever the order.
+ * workspace: frp_nmpc_flight_summary_workspace_bytes(B) bytes of device memory, written and read by this call alone (0 for B < 0).
+ * FRP_ERR_ARG: rec, an array of it, out_i, out_f, hist or workspace NULL; B < 0; n_edges outside 0 ... FRP_FLIGHT_MAX_EDGES; edges NULL
+ * with n_edges > 0; exactly one of min_clear / hits NULL; workspace_bytes too small.  B == 0 writes the figures of an empty fleet. */
+size_t frp_nmpc_flight_summary_workspace_bytes(int B);
+int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min_clear, const int *hits, const int *mask, int n_edges,
+                            const double *edges, long long *out_i, double *out_f, long long *hist, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

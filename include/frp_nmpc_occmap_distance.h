@@ -6,7 +6,7 @@
  *
  * NO REFERENCE COUNTERPART: the reference's map (occ_grid/src/occ_map.cpp) answers yes / no questions only and keeps no distance
  * information.  tests/occmap_distance_oracle.py is the executable statement, written as brute force.  Tracking error and the rest of a
- * flight record are not part of this header.
+ * flight record are section (14) of frp_nmpc.h (frp_nmpc_flight_*), whose summary takes this header's min_clear and hits.
  *
  * The field.  For a map with grid (gx, gy, gz), a radius R in voxels, 1 <= R <= FRP_OCCMAP_DIST_MAX_R, and a flag `border`:
  *     D2[x][y][z]    = min over "occupied" voxels u of |(x, y, z) - u|^2                       (integers)
