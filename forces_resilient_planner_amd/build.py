@@ -7,8 +7,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfrp_nmpc_amd.so")
-SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_dropin.hip", "frp_host_batch.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_distance.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip", "frp_command.hip", "frp_outcome.hip", "frp_fsm.hip", "frp_vehicle.hip", "frp_estimator.hip", "frp_flight_record.hip"]
-HEADERS = ["frp_kernels.h", "frp_capi_internal.hpp", "frp_copy_pool.hpp", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", "frp_occmap_raywalk.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
+SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_dropin.hip", "frp_host_batch.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_distance.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip", "frp_command.hip", "frp_outcome.hip", "frp_fsm.hip", "frp_vehicle.hip", "frp_estimator.hip", "frp_flight_record.hip", "frp_disturbance.hip"]
+HEADERS = ["frp_kernels.h", "frp_capi_internal.hpp", "frp_copy_pool.hpp", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", "frp_occmap_raywalk.hpp", "frp_disturbance.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_batch.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_points.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_check.h"),
            os.path.join(ROOT, "include", "frp_nmpc_occmap_distance.h"),
@@ -160,7 +160,11 @@ PER_SOURCE_FLAGS = {"frp_ipm_lds.hip": CODEGEN_FLAGS,  # (what else a solver uni
                     "frp_estimator.hip": ["-ffp-contract=off"],
                     # the flight record's squared norms, sums and means are its specification's operations
                     # (tests/flight_record_oracle.py), one rounding each: (dx * dx + dy * dy) + dz * dz is no FMA
-                    "frp_flight_record.hip": ["-ffp-contract=off"]}
+                    "frp_flight_record.hip": ["-ffp-contract=off"],
+                    # the disturbance's time, zone weights and OU step are its specification's operations (tests/disturbance_oracle.py),
+                    # one rounding each: t_epoch + k * dt, acc + w * F and a * g + c * n are no FMAs -- and the vehicle unit, which
+                    # calls the same device function inside its step, is built the same way, so both evaluations round alike
+                    "frp_disturbance.hip": ["-ffp-contract=off"]}
 OBJDIR = os.path.join(PKG, "_build")
 
 

@@ -198,6 +198,12 @@ class FlightRecordArgs(ctypes.Structure):
                                                                         "ticks_converged", "result_hist", "state_hist", "first_arrival")]
 
 
+class DisturbanceArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("Z", ctypes.c_int), ("E", ctypes.c_int), ("t_epoch", ctypes.c_double), ("dt", ctypes.c_double),
+                ("gust_a", ctypes.c_double * 3), ("gust_c", ctypes.c_double * 3), ("seed", ctypes.c_longlong), ("id0", ctypes.c_longlong)] + \
+               [(n, ctypes.c_void_p) for n in ("zone", "event", "gust", "tick")]
+
+
 class OccMapBody(ctypes.Structure):
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -225,7 +231,7 @@ EXTFUNC = ctypes.CFUNCTYPE(None, c_double_p, c_double_p, c_double_p, c_double_p,
 C_TYPES = {cls: (ctype, header) for header, group in {
     "frp_nmpc.h": {Options: "frp_nmpc_options", Batch: "frp_nmpc_batch", Pack: "frp_nmpc_pack", Tube: "frp_nmpc_tube", Corridor: "frp_nmpc_corridor",
                    CorridorCut: "frp_nmpc_corridor_cut", Reference: "frp_nmpc_reference", Astar: "frp_nmpc_astar", OccMap: "frp_nmpc_occmap",
-                   OccMapView: "frp_nmpc_occmap_view", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
+                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
     "frp_nmpc_occmap_fuse.h": {OccMapFuse: "frp_nmpc_occmap_fuse"}, "frp_nmpc_occmap_fuse_batch.h": {OccMapFuseBatch: "frp_nmpc_occmap_fuse_batch"},
     "frp_nmpc_occmap_fuse_points.h": {OccMapFusePoints: "frp_nmpc_occmap_fuse_points"}, "frp_nmpc_occmap_check.h": {OccMapBody: "frp_nmpc_occmap_body"},
     "frp_nmpc_occmap_render.h": {OccMapRender: "frp_nmpc_occmap_render"}, "frp_nmpc_occmap_render_scan.h": {OccMapRenderScan: "frp_nmpc_occmap_render_scan"},
@@ -259,6 +265,7 @@ FLIGHT_I_SELECTED, FLIGHT_I_ARRIVED, FLIGHT_I_WITH_BAD, FLIGHT_I_WITH_HITS, FLIG
     FLIGHT_I_SAT_SAMPLES, FLIGHT_I_PERIODS, FLIGHT_I_TICKS_RUN, FLIGHT_I_TICKS_CONVERGED, FLIGHT_I_RESULT = range(13)  # out_i of frp_nmpc_flight_summary
 FLIGHT_I_ARRIVAL_SUM = 18  # (FLIGHT_I_RESULT ... + 5 are result_hist's columns)
 FLIGHT_F_TRACK_MAX2, FLIGHT_F_SPEED_MAX2, FLIGHT_F_PATH_MAX, FLIGHT_F_MIN_CLEAR, FLIGHT_F_TRACK_SUM2, FLIGHT_F_PATH_SUM = range(6)  # out_f
+DISTURBANCE_MAX_ZONES, DISTURBANCE_MAX_EVENTS, DISTURBANCE_ZONE_STRIDE, DISTURBANCE_EVENT_STRIDE = 16, 8, 12, 5
 
 # name here -> macro in include/*.h, for every integer above (one defined below this line is not checked): FRP_<name>, but for three
 MACROS = {n: n if n.startswith("FRP_") else "FRP_" + n for n, v in list(globals().items()) if n.isupper() and type(v) is int}
@@ -269,7 +276,7 @@ MACROS["ABI_VERSION"] = "FRP_NMPC_ABI_VERSION"
 _i, _d, _z, _v = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 _P = ctypes.POINTER
 _batch, _map, _cor, _cut, _fsm, _body = [_P(Batch), _P(Options)], _P(OccMap), _P(Corridor), _P(CorridorCut), _P(Fsm), _P(OccMapBody)
-_rec = _P(FlightRecordArgs)
+_rec, _dist = _P(FlightRecordArgs), _P(DisturbanceArgs)
 _forces = (_i, [_P(ForcesParams), _P(ForcesOutput), _P(ForcesInfo), _v, _v])  # (FILE *, extfunc: an EXTFUNC or None, which only c_void_p takes)
 _BY_HEADER = {
     "frp_nmpc.h": {"frp_nmpc_abi_version": (_i, []),
@@ -313,6 +320,9 @@ _BY_HEADER = {
         "frp_nmpc_device_count": (_i, []),
         "FORCESNLPsolver_normal_solve": _forces,
         "FORCESNLPsolver_final_solve": _forces,
+        "frp_nmpc_disturbance_eval": (_i, [_dist, _i, _v, _v, _i, _v, _v]),
+        "frp_nmpc_disturbance_reset": (_i, [_dist, _v, _v]),
+        "frp_nmpc_vehicle_step_field": (_i, [_P(VehicleArgs), _dist, _v, _v, _v]),
         "frp_nmpc_flight_record_samples": (_i, [_rec, _i, _v, _i, _v, _v, _v, _v, _v]),
         "frp_nmpc_flight_record_period": (_i, [_rec, _v, _v, _v, _v, _v, _v]),
         "frp_nmpc_flight_record_reset": (_i, [_rec, _v, _v, _v]),

@@ -17,10 +17,16 @@
 //   * Every store is a plain C++ store from a vector lane; no inline assembly.
 //   * frp_nmpc_vehicle_step_observed (frp_nmpc_estimator.h) is the same step kernel instantiated with one more store per sample, the
 //     clamped thrust; the instantiation frp_nmpc_vehicle_step launches is the kernel as it was (profiles/estimator_step_identity.txt).
+//   * frp_nmpc_vehicle_step_field (frp_nmpc.h section 15) is the same step kernel with FIELD set: between a sample's setpoint and its
+//     controller the force is taken from frp_disturbance.hpp's sample_force at the plant's own position, and replaces f for the sample's
+//     Heun steps.  The two instantiations without FIELD are the kernels as they were (profiles/disturbance_step_identity.txt).  The
+//     constant part and the OU state are re-read from memory per sample, not held across the Heun steps: the kernel sits at 230 VGPRs,
+//     and twelve more registers of live state would spill.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
 #include "frp_model.hpp"
+#include "frp_disturbance.hpp"
 
 #pragma clang fp contract(off)
 
@@ -65,8 +71,10 @@ __device__ inline void rotation(const Quat &q, double R[9])
 
 // OBSERVED: frp_nmpc_vehicle_step_observed's instantiation (frp_nmpc_estimator.h) also stores the clamped thrust of every sample;
 // frp_nmpc_vehicle_step launches <false>, whose code has no such store (`thrust` is then not read).
-template <bool OBSERVED>
-__global__ __launch_bounds__(THREADS) void step_kernel(frp_nmpc_vehicle c, double *thrust)
+// FIELD: frp_nmpc_vehicle_step_field's instantiations take every sample's force from the disturbance model d (c.f_true is its constant
+// part) and store it to `force` where asked; without FIELD neither d nor force is read.
+template <bool OBSERVED, bool FIELD>
+__global__ __launch_bounds__(THREADS) void step_kernel(frp_nmpc_vehicle c, double *thrust, frp_nmpc_disturbance d, double *force)
 {
     const int b = blockIdx.x * THREADS + threadIdx.x;
     if (b >= c.B) return;
@@ -112,6 +120,26 @@ __global__ __launch_bounds__(THREADS) void step_kernel(frp_nmpc_vehicle c, doubl
 #pragma unroll
             for (int i = 0; i < 3; i++) p_ref[i] = hp[i];
             yaw = hyaw;
+        }
+        if (FIELD) { // ---- the force this sample flies under: the model at the position before the sample ----
+            double base[3], g[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int i = 0; i < 3; i++) base[i] = c.f_true[(size_t)b * 3 + i];
+            if (d.gust) {
+#pragma unroll
+                for (int i = 0; i < 3; i++) g[i] = d.gust[(size_t)b * 3 + i];
+            }
+            const long long k = d.tick[b];
+            disturbance::sample_force(d, d.zone, d.event, b, k, x, base, g, f);
+            if (d.gust) {
+#pragma unroll
+                for (int i = 0; i < 3; i++) d.gust[(size_t)b * 3 + i] = g[i];
+            }
+            d.tick[b] = (long long)((unsigned long long)k + 1ULL);
+            if (force) {
+#pragma unroll
+                for (int i = 0; i < 3; i++) force[((size_t)b * S + s) * 3 + i] = f[i];
+            }
         }
         // ---- the controller ----
         int sat = 0, which;
@@ -289,7 +317,8 @@ int frp_nmpc_vehicle_step(const frp_nmpc_vehicle *v, void *stream)
     using namespace frp::vehicle;
     if (step_args(v) != FRP_OK) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(step_kernel<false>, dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, static_cast<double *>(nullptr));
+    hipLaunchKernelGGL((step_kernel<false, false>), dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, static_cast<double *>(nullptr),
+                       frp_nmpc_disturbance{}, static_cast<double *>(nullptr));
     return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
 }
 
@@ -299,7 +328,22 @@ int frp_nmpc_vehicle_step_observed(const frp_nmpc_vehicle *v, double *thrust, vo
     using namespace frp::vehicle;
     if (step_args(v) != FRP_OK || !thrust) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(step_kernel<true>, dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, thrust);
+    hipLaunchKernelGGL((step_kernel<true, false>), dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, thrust, frp_nmpc_disturbance{},
+                       static_cast<double *>(nullptr));
+    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+}
+
+// frp_nmpc.h section (15)
+int frp_nmpc_vehicle_step_field(const frp_nmpc_vehicle *v, const frp_nmpc_disturbance *d, double *thrust, double *force, void *stream)
+{
+    using namespace frp::vehicle;
+    if (step_args(v) != FRP_OK || frp::disturbance::check(d) != FRP_OK || d->B != v->B || !(d->dt == v->dt_cmd)) return FRP_ERR_ARG;
+    if (!device_ok()) return FRP_ERR_NO_DEVICE;
+    const dim3 grid(blocks_for(v->B)), block(THREADS);
+    if (thrust)
+        hipLaunchKernelGGL((step_kernel<true, true>), grid, block, 0, static_cast<hipStream_t>(stream), *v, thrust, *d, force);
+    else
+        hipLaunchKernelGGL((step_kernel<false, true>), grid, block, 0, static_cast<hipStream_t>(stream), *v, thrust, *d, force);
     return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
 }
 

@@ -1,11 +1,11 @@
 """A fleet in flight, on the device: the state machine that drives the planners (FleetFSM), the vehicle that flies their commands
-(Vehicle), the estimator that tells them what it felt (ForceEstimator) and the record of what the fleet did (FlightRecord)
-(frp_nmpc_fsm_*, _vehicle_*, _estimator_*, _flight_*)."""
+(Vehicle), the force that acts on it (Disturbance), the estimator that tells them what it felt (ForceEstimator) and the record of what
+the fleet did (FlightRecord) (frp_nmpc_fsm_*, _vehicle_*, _disturbance_*, _estimator_*, _flight_*)."""
 import collections
 import ctypes
 
 from . import layout as L
-from .capi import (COMMAND_STRIDE, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, ODOM_BODY, ODOM_WORLD,
+from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, ODOM_BODY, ODOM_WORLD,
                    TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
                    checked_ptr, lib, stream_ptr, tensor_ptr)
 from .fleet import TickState
@@ -29,9 +29,10 @@ class Vehicle:
     """The vehicle of every planner of a DeviceFleet, on the device (include/frp_nmpc_vehicle.h): a tracking plant that flies the command
     timer's samples and the reference's odometry callbacks, so that FleetFSM.period(..., vehicle=...) closes the loop without the host.
     Owns, all float64 device tensors unless noted: x [B,9] the plant state (position, world velocity, roll pitch yaw), hold [B,8] the last
-    published position and yaw, f_true [B,3] the TRUE mass-normalised external force (the caller writes it; what the planner is told is
-    the `force` / `force_fresh` of period(): the caller's own, or a ForceEstimator's), msg [B,13] the last odometry message, state [B,9] what the callbacks made of it (the
-    `state` of period(), exec_step() and full_tick()), state_prev [B,9], fresh [B] int32 (ones: every planner hears every message), and
+    published position and yaw, f_true [B,3] the TRUE mass-normalised external force (the caller writes it; with a Disturbance attached
+    it is the constant part of that model's force; what the planner is told is the `force` / `force_fresh` of period(): the caller's
+    own, or a ForceEstimator's), msg [B,13] the last odometry message, state [B,9] what the callbacks made of it (the `state` of
+    period(), exec_step() and full_tick()), state_prev [B,9], fresh [B] int32 (ones: every planner hears every message), and
     with trace=True trace [B,S,9] / sat [B,S] int32 of the last step().
     kp, kv, ka, n_sub, mass, g, dt_cmd: VEHICLE_DEFAULTS -- the controller has no reference counterpart, the plant is the planner's own
     model (csrc/frp_model.hpp).  odom_type: ODOM_BODY (odometryTransCallback: the RotorS message, body-frame twist) or ODOM_WORLD."""
@@ -57,6 +58,7 @@ class Vehicle:
         self.trace = t.zeros((self.B, self.S, VEHICLE_STATE), **f64) if trace else None
         self.sat = t.zeros((self.B, self.S), dtype=t.int32, device=dev) if trace else None
         self.estimator = None   # a ForceEstimator attaches itself here: step() and reset() then feed and reset it
+        self.disturbance = None  # a Disturbance attaches itself here: step() then takes every sample's force from it, reset() resets it
 
     def reset(self, x0, mask=None, stream=None):
         """frp_nmpc_vehicle_reset: where mask [B] int32 != 0 (None: everywhere) x <- x0 [B,9] and hold <- its position and yaw: the
@@ -67,12 +69,17 @@ class Vehicle:
                                             tensor_ptr(self.hold), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_reset")
         if self.estimator is not None:
             self.estimator.reset(mask, stream)
+        if self.disturbance is not None:
+            self.disturbance.reset(mask, stream)
 
     def step(self, commands, stream=None):
         """frp_nmpc_vehicle_step: the S samples of a Commands object (cmd [B,S,16], kind [B,S]) flown in order under f_true; x and hold
         in place, trace / sat where the object was made with trace=True (S is then the constructor's).
         With a ForceEstimator attached (self.estimator): frp_nmpc_vehicle_step_observed instead -- the same flight, and the thrust of every
-        sample into the estimator's `thrust`, the trace into this object's own trace or else the estimator's `meas` --, then its update()."""
+        sample into the estimator's `thrust`, the trace into this object's own trace or else the estimator's `meas` --, then its update().
+        With a Disturbance attached (self.disturbance): frp_nmpc_vehicle_step_field instead of either -- f_true is then the constant part
+        of the force, every sample flies under the model's force at the plant's own position (written to the disturbance's `force`), and
+        the estimator, where there is one, is fed as above."""
         t = self.torch
         S = int(commands.cmd.shape[1])
         if self.trace is not None and S != self.S:
@@ -85,11 +92,19 @@ class Vehicle:
                         (ctypes.c_double * 3)(*self.ka), self.x.data_ptr(), self.f_true.data_ptr(),
                         checked_ptr(self.x, commands.cmd, t.float64, (self.B, S, COMMAND_STRIDE)), checked_ptr(self.x, commands.kind, t.int32, (self.B, S)),
                         self.hold.data_ptr(), trace.data_ptr() if trace is not None else None, self.sat.data_ptr() if self.sat is not None else None)
-        if est is None:
+        dist = self.disturbance
+        if dist is not None:
+            if S != dist.S:
+                raise ValueError(f"the attached Disturbance records S = {dist.S} samples per call, the commands hold {S}")
+            d = dist.struct()
+            _check(lib().frp_nmpc_vehicle_step_field(ctypes.byref(v), ctypes.byref(d), tensor_ptr(est.thrust) if est is not None else None,
+                                                     tensor_ptr(dist.force), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step_field")
+        elif est is None:
             _check(lib().frp_nmpc_vehicle_step(ctypes.byref(v), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step")
-            return
-        _check(lib().frp_nmpc_vehicle_step_observed(ctypes.byref(v), tensor_ptr(est.thrust), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step_observed")
-        est.update(meas=trace, stream=stream)
+        else:
+            _check(lib().frp_nmpc_vehicle_step_observed(ctypes.byref(v), tensor_ptr(est.thrust), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step_observed")
+        if est is not None:
+            est.update(meas=trace, stream=stream)
 
     def message(self, stream=None):
         """frp_nmpc_vehicle_message: msg <- the odometry message of x for this object's odom_type."""
@@ -163,6 +178,88 @@ class ForceEstimator:
         m = checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None
         state = map(tensor_ptr, (self.f_hat, self.y_prev, self.count, self.force, self.fresh))
         _check(lib().frp_nmpc_estimator_reset(self.B, m, *state, stream_ptr(stream, v.x)), "frp_nmpc_estimator_reset")
+
+
+class Disturbance:
+    """The TRUE external force of every vehicle of a Vehicle, on the device (include/frp_nmpc.h section 15): wind zones fixed in the world,
+    force events per vehicle and seeded Ornstein-Uhlenbeck gusts, evaluated per command sample at the plant's own position inside the step
+    that flies the sample.  It has no reference counterpart (the reference flies RotorS with a hand-driven wrench);
+    tests/disturbance_oracle.py is the statement.  CHOSEN, not derived: the force is held over a sample (a zero-order hold per dt_cmd),
+    a zone's edge is a linear ramp, the turbulence a first-order process per axis.
+    Attaches itself as vehicle.disturbance: Vehicle.step then launches frp_nmpc_vehicle_step_field -- vehicle.f_true stays the constant
+    part --, Vehicle.reset resets it under the same mask.  FleetFSM.period needs nothing new.
+    zones: [Z <= 16, 12] float64 host rows (lo 0-2, hi 3-5, F 6-8, ramp 9, t_on 10, t_off 11) or None; ramp finite and >= 0 is checked
+    here, on the host array.  events: [B, E <= 8, 5] or [E, 5] (every vehicle's) rows (t_on, t_off, F) or None; an unused slot has
+    t_on = +inf.  gust_sigma / gust_tau: a number or three, per axis (m/s^2, seconds), both or neither; a = exp(-dt / tau) and
+    c = sigma sqrt(1 - a a) are computed here.  seed, id0: vehicle b draws the stream (seed, id0 + b).  t_epoch: the time of sample 0.
+    Owns, device tensors: zone [Z,12], event [B,E,5], gust [B,3] (the OU state; None without gusts), tick [B] int64 (the sample counter),
+    force [B,S,3] (what each sample of the last step flew under)."""
+
+    def __init__(self, vehicle, zones=None, events=None, gust_sigma=None, gust_tau=None, seed=0, id0=0, t_epoch=0.0):
+        import math
+        import numpy as np
+        t = vehicle.torch
+        dev = vehicle.x.device
+        self.torch, self.vehicle, self.B, self.S, self.dt = t, vehicle, vehicle.B, vehicle.S, float(vehicle.dt_cmd)
+        self.seed, self.id0, self.t_epoch = int(seed), int(id0), float(t_epoch)
+        if not (-2 ** 63 <= self.seed < 2 ** 63 and -2 ** 63 <= self.id0 < 2 ** 63) or not math.isfinite(self.t_epoch):
+            raise ValueError("Disturbance: seed and id0 are 64-bit signed integers, t_epoch is finite")
+        f64 = dict(dtype=t.float64, device=dev)
+        self.zone = self.event = self.gust = None
+        self.Z = self.E = 0
+        if zones is not None and len(zones):
+            z = np.ascontiguousarray(zones, dtype=np.float64)
+            if z.ndim != 2 or z.shape[1] != DISTURBANCE_ZONE_STRIDE or z.shape[0] > DISTURBANCE_MAX_ZONES:
+                raise ValueError(f"Disturbance: zones is [Z <= {DISTURBANCE_MAX_ZONES}, {DISTURBANCE_ZONE_STRIDE}]")
+            if not (np.all(np.isfinite(z[:, 9])) and np.all(z[:, 9] >= 0.0)):
+                raise ValueError("Disturbance: a zone's ramp is finite and >= 0")
+            self.Z, self.zone = int(z.shape[0]), t.from_numpy(z).to(dev)
+        if events is not None and np.size(events):
+            e = np.asarray(events, dtype=np.float64)
+            if e.ndim == 2:
+                e = np.broadcast_to(e[None], (self.B,) + e.shape)
+            if e.ndim != 3 or e.shape[0] != self.B or e.shape[2] != DISTURBANCE_EVENT_STRIDE or e.shape[1] > DISTURBANCE_MAX_EVENTS:
+                raise ValueError(f"Disturbance: events is [B, E <= {DISTURBANCE_MAX_EVENTS}, {DISTURBANCE_EVENT_STRIDE}] or [E, {DISTURBANCE_EVENT_STRIDE}]")
+            self.E, self.event = int(e.shape[1]), t.from_numpy(np.ascontiguousarray(e)).to(dev)
+        self.gust_a, self.gust_c = (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)
+        if (gust_sigma is None) != (gust_tau is None):
+            raise ValueError("Disturbance: gust_sigma and gust_tau come together")
+        if gust_sigma is not None:
+            three = lambda v: tuple(float(u) for u in (v if np.ndim(v) else (v, v, v)))
+            sigma, tau = three(gust_sigma), three(gust_tau)
+            if len(sigma) != 3 or len(tau) != 3 or not all(math.isfinite(s) and s >= 0.0 for s in sigma) or not all(math.isfinite(u) and u > 0.0 for u in tau):
+                raise ValueError("Disturbance: gust_sigma finite and >= 0, gust_tau finite and > 0, a number or three each")
+            self.gust_a = tuple(math.exp(-self.dt / u) for u in tau)
+            self.gust_c = tuple(s * math.sqrt(1.0 - a * a) for s, a in zip(sigma, self.gust_a))
+            self.gust = t.zeros((self.B, 3), **f64)
+        self.tick = t.zeros((self.B,), dtype=t.int64, device=dev)
+        self.force = t.zeros((self.B, self.S, 3), **f64)
+        vehicle.disturbance = self
+
+    def struct(self):
+        return DisturbanceArgs(self.B, self.Z, self.E, self.t_epoch, self.dt, (ctypes.c_double * 3)(*self.gust_a), (ctypes.c_double * 3)(*self.gust_c),
+                               self.seed, self.id0, *[a.data_ptr() if a is not None else None for a in (self.zone, self.event, self.gust, self.tick)])
+
+    def eval(self, pos, advance=False, base=None, out=None, stream=None):
+        """frp_nmpc_disturbance_eval: the force [B,S,3] of samples tick ... tick + S - 1 at pos [B,S,3] (any S >= 1), base [B,3] the
+        constant part (None: zero -- not vehicle.f_true).  advance: gust and tick move on by S; otherwise a pure query.  out: a [B,S,3]
+        tensor to write (None: a new one, an allocation)."""
+        t, v = self.torch, self.vehicle
+        assert t.is_tensor(pos) and pos.dim() == 3, "pos is a [B, S, 3] tensor"
+        S = int(pos.shape[1])
+        out = t.empty((self.B, S, 3), dtype=t.float64, device=v.x.device) if out is None else out
+        d = self.struct()
+        _check(lib().frp_nmpc_disturbance_eval(ctypes.byref(d), S, checked_ptr(v.x, pos, t.float64, (self.B, S, 3)),
+                                               checked_ptr(v.x, base, t.float64, (self.B, 3)) if base is not None else None, int(bool(advance)),
+                                               checked_ptr(v.x, out, t.float64, (self.B, S, 3)), stream_ptr(stream, v.x)), "frp_nmpc_disturbance_eval")
+        return out
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_disturbance_reset: where mask [B] int32 != 0 (None: everywhere) tick <- 0 and the OU state <- 0."""
+        t, v = self.torch, self.vehicle
+        d = self.struct()
+        _check(lib().frp_nmpc_disturbance_reset(ctypes.byref(d), checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None,
+                                                stream_ptr(stream, v.x)), "frp_nmpc_disturbance_reset")
 
 
 FlightSummary = collections.namedtuple("FlightSummary", "ints floats hist")

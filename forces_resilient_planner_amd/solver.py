@@ -2,12 +2,13 @@
 
 Every function runs HIP kernels on the MI355X; there is no CPU fallback: a missing library or device raises.  The code lives by concern,
 each module importing only the ones before it: capi (structs, macros, signatures, loader), batch (the solve), occmap (the map), planning
-(tube, references, corridor, A*, commands), fleet (the tick), flight (state machine, vehicle, estimator, flight record).
+(tube, references, corridor, A*, commands), fleet (the tick), flight (state machine, vehicle, disturbance, estimator, flight record).
 """
 from .capi import (ABI_VERSION, ASTAR_MAX_PATH, ASTAR_NO_PATH, ASTAR_REACH_END, ASTAR_REACH_END_BUT_SHOT_FAILS, ASTAR_REACH_HORIZON, CHECK_EXPORTS,
                    CMD_INIT_POSITION, CMD_PUB_END, CMD_PUB_TRAJ, CMD_ROTATE_YAW, CMD_WAIT, COMMAND_END, COMMAND_EXPORTS, COMMAND_NONE,
                    COMMAND_NO_YAW_INPUT, COMMAND_STRIDE, COMMAND_TRAJ, COMMAND_YAW, CORRIDOR_LARGE_GROUPS, CORRIDOR_LARGE_LIST,
-                   CORRIDOR_LARGE_MAX_POINTS, CORRIDOR_MAX_CELLS, CORRIDOR_MAX_F, CORRIDOR_MAX_POINTS, DISTANCE_EXPORTS, EST_ABSORBED, EST_FIRST,
+                   CORRIDOR_LARGE_MAX_POINTS, CORRIDOR_MAX_CELLS, CORRIDOR_MAX_F, CORRIDOR_MAX_POINTS, DISTANCE_EXPORTS, DISTURBANCE_EVENT_STRIDE,
+                   DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, EST_ABSORBED, EST_FIRST,
                    EST_SKIPPED, ESTIMATOR_EXPORTS, EXPORTS, EXTFUNC, FLIGHT_F_MIN_CLEAR, FLIGHT_F_PATH_MAX, FLIGHT_F_PATH_SUM, FLIGHT_F_SPEED_MAX2,
                    FLIGHT_F_TRACK_MAX2, FLIGHT_F_TRACK_SUM2, FLIGHT_GROUP, FLIGHT_I_ARRIVAL_SUM, FLIGHT_I_ARRIVED, FLIGHT_I_BAD, FLIGHT_I_FLOWN,
                    FLIGHT_I_PERIODS, FLIGHT_I_RESULT, FLIGHT_I_SAMPLES, FLIGHT_I_SAT_SAMPLES, FLIGHT_I_SELECTED, FLIGHT_I_TICKS_CONVERGED,
@@ -19,7 +20,7 @@ from .capi import (ABI_VERSION, ASTAR_MAX_PATH, ASTAR_NO_PATH, ASTAR_REACH_END, 
                    OUTCOME_EXPORTS, RENDER_EXPORTS, RENDER_SCAN_EXPORTS, SIGNATURES, TICK_AT_END, TICK_ENDING, TICK_IDLE, TICK_RESULT_IDLE, TICK_RUN,
                    VEHICLE_EXPORTS, VEHICLE_HOLD_STRIDE, VEHICLE_MAX_SUB, VEHICLE_MSG_STRIDE, VEHICLE_SAT_PITCH, VEHICLE_SAT_RATE0, VEHICLE_SAT_ROLL,
                    VEHICLE_SAT_THRUST_HI, VEHICLE_SAT_THRUST_LO, VEHICLE_SAT_YAW_WRAP, VEHICLE_SAT_ZERO_ACC, VEHICLE_STATE, VIEW_EXPORTS, Astar, Batch,
-                   Command, Corridor, CorridorCut, CorridorLarge, EstimatorArgs, FlightRecordArgs, ForcesInfo, ForcesOutput, ForcesParams, Fsm,
+                   Command, Corridor, CorridorCut, CorridorLarge, DisturbanceArgs, EstimatorArgs, FlightRecordArgs, ForcesInfo, ForcesOutput, ForcesParams, Fsm,
                    FsmExecIn, OccMap, OccMapBody, OccMapFuse, OccMapFuseBatch, OccMapFusePoints, OccMapRender, OccMapRenderScan, OccMapSharedView,
                    OccMapView, Options, Pack, Reference, Tick, TickIn, Tube, VehicleArgs, _PKG, _check, _lib, c_double_p, c_int_p, lib)
 from .batch import (DeviceSolver, _registered, default_options, host_register, host_unregister, host_unregister_all, kernel_timing_begin,
@@ -31,5 +32,5 @@ from .planning import (COMMAND_DEFAULTS, CORRIDOR_DEFAULTS, REFERENCE_PI, TUBE_D
                        command_snapshot_device, corridor_batch_device, corridor_batch_host, reference_batch_device, reference_batch_host,
                        tube_batch_device, tube_batch_host)
 from .fleet import DeviceFleet, TickState
-from .flight import (ESTIMATOR_DEFAULTS, FSM_EXEC_PERIOD, FSM_EXT_NOISE_BOUND, VEHICLE_DEFAULTS, FleetFSM, FlightRecord, FlightSummary, ForceEstimator,
+from .flight import (ESTIMATOR_DEFAULTS, FSM_EXEC_PERIOD, FSM_EXT_NOISE_BOUND, VEHICLE_DEFAULTS, Disturbance, FleetFSM, FlightRecord, FlightSummary, ForceEstimator,
                      Vehicle)

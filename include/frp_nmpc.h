@@ -662,6 +662,81 @@ int FORCESNLPsolver_normal_solve(frp_forces_params *params, frp_forces_output *o
 int FORCESNLPsolver_final_solve(frp_forces_params *params, frp_forces_output *output, frp_forces_info *info,
                                 FILE *fs, frp_forces_extfunc evalextfunctions);
 
+/* ---- (15) the disturbance: the TRUE external force as a function of position, time and a seeded stream, on the device ---- */
+/* (Declared ahead of section (14): the flight record's five calls stay the last exports of this header.)
+ * What acts on a vehicle of section (12), evaluated per command sample inside the step that flies the sample: wind zones fixed in the
+ * world, force events per vehicle (the reference's keyboard-injected steps, README.md:111-117) and Ornstein-Uhlenbeck gusts drawn from a
+ * counter-based generator.  With it frp_nmpc_vehicle.f_true is the constant part alone, and a fan the vehicle flies through or a step at
+ * t = 1.3 s needs no host between two periods of a captured loop.  NO REFERENCE COUNTERPART (the reference flies RotorS with a hand-driven
+ * wrench): tests/disturbance_oracle.py is the executable statement, and the device agrees with it to the bit wherever no logarithm or cosine
+ * is involved (csrc/frp_disturbance.hip and csrc/frp_vehicle.hip are built without contraction).  Same ABI version: no existing struct
+ * changed.  CHOSEN, not derived: the force is held over a sample's n_sub Heun steps (a zero-order hold per 10 ms sample), a zone's edge
+ * is a linear ramp, and the turbulence is a first-order (OU) process per axis.
+ *
+ * All forces are mass-normalised (m/s^2), as f_true is.  Vehicle b keeps a 64-bit sample counter tick[b].  For sample k = tick[b]:
+ *   t = t_epoch + (double)k * dt                        one product, one sum
+ *   p = the plant's position BEFORE the sample's Heun steps
+ *   acc = base[b]                                        (frp_nmpc_vehicle.f_true; 0 where base is NULL)
+ *   for z = 0 ... Z - 1:  acc += w_z(p, t) * F_z         every zone, w = 0 included
+ *   for e = 0 ... E - 1:  if t_on <= t < t_off:  acc += F_{b,e}
+ *   with gust:  g <- a o g + c o n(seed, id0 + b, k);   acc += g
+ * Each product and each sum is rounded on its own, per component, in this order.
+ *   zone   row [FRP_DISTURBANCE_ZONE_STRIDE]: lo 0-2, hi 3-5, F 6-8, ramp 9, t_on 10, t_off 11 -- a box fixed in the world, shared by the
+ *          fleet.  w = 0 unless t_on <= t < t_off and all six differences p_i - lo_i (i = 0, 1, 2), hi_i - p_i (i = 0, 1, 2) are >= 0 (a
+ *          NaN fails the test: a non-finite position feels no zone).  Otherwise d = the smallest of the six, taken in that order with
+ *          `<`, and w = d >= ramp ? 1 : d / ramp.  ramp = 0 is a hard edge with closed faces.  ramp finite and >= 0 is the CALLER'S
+ *          contract: the arrays are device memory and are not checked.
+ *   event  row [FRP_DISTURBANCE_EVENT_STRIDE]: t_on, t_off, F 2-4, per vehicle [B][E].  An unused slot has t_on = +inf.
+ *   gust   a = exp(-dt / tau), c = sigma sqrt(1 - a a) per axis, computed by the caller.  n is a standard normal of (seed, id0 + b, k, axis)
+ *          alone: with M(x) the SplitMix64 finaliser (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) *
+ *          0x94D049BB133111EB; x ^ x >> 31, unsigned 64-bit, wrapping),
+ *              h = M(M(M(seed) + id) + k),  r0 = M(h + 2 axis),  r1 = M(h + 2 axis + 1),
+ *              u1 = (double)((r0 >> 11) + 1) / 9007199254740993.0,  u2 = (double)(r1 >> 11) / 9007199254740992.0,
+ *              n = sqrt(-2 log(u1)) * cos(6.283185307179586 * u2).
+ *          (The first divisor is written as 2^53 + 1; the double it denotes is 2^53, so u1 lies in (0, 1] and both quotients are exact.)
+ *          Any sharding of a fleet, any S and any split of a flight into calls draws the same numbers.
+ * Every call: every pointer is DEVICE memory, asynchronous on `stream`, nothing allocated, nothing read back, capturable into a hipGraph
+ * with the period; one launch, one thread per vehicle, 256 per workgroup.  FRP_ERR_ARG before any device call, FRP_ERR_NO_DEVICE without
+ * a device. */
+#define FRP_DISTURBANCE_MAX_ZONES 16
+#define FRP_DISTURBANCE_MAX_EVENTS 8
+#define FRP_DISTURBANCE_ZONE_STRIDE 12
+#define FRP_DISTURBANCE_EVENT_STRIDE 5
+
+typedef struct frp_nmpc_disturbance {
+    int B, Z, E;                  /* vehicles, zones (0 ... FRP_DISTURBANCE_MAX_ZONES), event slots per vehicle (0 ... _MAX_EVENTS)   */
+    double t_epoch, dt;           /* the time of sample 0 (finite) and the sample period (finite and > 0)                            */
+    double gust_a[3], gust_c[3];  /* the OU coefficients per axis, read with gust alone: finite, a in [0, 1], c >= 0                  */
+    long long seed, id0;          /* the stream: vehicle b draws as id0 + b (wrapping)                                                */
+    const double *zone;           /* [Z][FRP_DISTURBANCE_ZONE_STRIDE], NULL iff Z == 0                                                */
+    const double *event;          /* [B][E][FRP_DISTURBANCE_EVENT_STRIDE], NULL iff E == 0                                            */
+    double *gust;                 /* [B][3] in and out: the OU state g; NULL: no gusts, and nothing is drawn                          */
+    long long *tick;              /* [B] in and out: the sample counter                                                               */
+} frp_nmpc_disturbance;
+
+/* The force of samples tick ... tick + S - 1 of every vehicle at the given positions, for callers who fly their own plant (and the
+ * tests): force[b][s] <- the model above at pos[b][s], base [B][3] or NULL.  advance != 0: gust and tick are updated (tick += S);
+ * advance == 0: a pure query, both stay.
+ * FRP_ERR_ARG: d, pos, force or d->tick NULL; B < 1; S < 1; B * S beyond 2^31 - 1; Z or E out of range; zone / event NULL or not against
+ * Z / E; t_epoch not finite; dt not finite and positive; with gust, a coefficient not finite, a outside [0, 1] or c < 0. */
+int frp_nmpc_disturbance_eval(const frp_nmpc_disturbance *d, int S, const double *pos, const double *base, int advance, double *force,
+                              void *stream);
+
+/* Where mask[b] != 0 (mask == NULL: everywhere): tick[b] <- 0 and, with gust, g[b] <- 0.
+ * FRP_ERR_ARG: as above for d. */
+int frp_nmpc_disturbance_reset(const frp_nmpc_disturbance *d, const int *mask, void *stream);
+
+/* frp_nmpc_vehicle_step with the force of every sample taken from the model at the plant's own position before that sample: v->f_true is
+ * `base`, the sample's force replaces it in the plant, and tick advances by S.  x, hold, trace and sat are what S calls of
+ * frp_nmpc_vehicle_step with S = 1 and f_true = that force write, to the bit (the same kernel text; the instantiations that
+ * frp_nmpc_vehicle_step and _step_observed launch are the kernels as they were, profiles/disturbance_step_identity.txt).
+ * thrust [B][S] or NULL: as frp_nmpc_vehicle_step_observed's.  force [B][S][3] or NULL: the force each sample flew under.
+ * FRP_ERR_ARG: whatever frp_nmpc_vehicle_step and frp_nmpc_disturbance_eval refuse of v and d, d->B != v->B, d->dt != v->dt_cmd.
+ * (v is written with its struct tag, as in frp_nmpc_estimator.h: frp_nmpc_vehicle.h may be the file a program includes.) */
+struct frp_nmpc_vehicle;
+int frp_nmpc_vehicle_step_field(const struct frp_nmpc_vehicle *v, const frp_nmpc_disturbance *d, double *thrust, double *force,
+                                void *stream);
+
 /* ---- (14) the flight record: tracking error, effort, events and a fleet summary, kept on the device ---- */
 /* What a fleet flown by sections (9)-(13) did, accumulated per vehicle from the arrays those sections leave in device memory, and the
  * fleet's figures from the per-vehicle ones -- beside frp_nmpc_occmap_clearance_trace (frp_nmpc_occmap_distance.h), which keeps the
@@ -782,6 +857,8 @@ size_t frp_nmpc_flight_summary_workspace_bytes(int B);
 int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min_clear, const int *hits, const int *mask, int n_edges,
                             const double *edges, long long *out_i, double *out_f, long long *hist, void *workspace, size_t workspace_bytes,
                             void *stream);
+
+/* (Section (15), the disturbance, is declared ahead of section (14), above.) */
 
 #ifdef __cplusplus
 }
