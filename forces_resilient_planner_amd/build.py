@@ -8,18 +8,9 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libfrp_nmpc_amd.so")
 SOURCES = ["frp_kernels.hip", "frp_ipm_lds.hip", "frp_ipm_lds_mem.hip", "frp_ipm_lds_q4.hip", "frp_ipm_lds_q30.hip", "frp_ipm_lds_s2.hip", "frp_capi.hip", "frp_dropin.hip", "frp_host_batch.hip", "frp_pack.hip", "frp_tube.hip", "frp_corridor.hip", "frp_corridor_large.hip", "frp_reference.hip", "frp_astar.hip", "frp_occmap.hip", "frp_occmap_fuse.hip", "frp_occmap_fuse_batch.hip", "frp_occmap_fuse_points.hip", "frp_occmap_check.hip", "frp_occmap_distance.hip", "frp_occmap_render.hip", "frp_occmap_render_scan.hip", "frp_occmap_view.hip", "frp_command.hip", "frp_outcome.hip", "frp_fsm.hip", "frp_vehicle.hip", "frp_estimator.hip", "frp_flight_record.hip", "frp_disturbance.hip"]
-HEADERS = ["frp_kernels.h", "frp_capi_internal.hpp", "frp_copy_pool.hpp", "frp_device.hpp", "frp_model.hpp", "frp_adapter.hpp", "frp_tube_math.hpp", "frp_corridor_wave.inc", "frp_corridor_scan.inc", "frp_occmap.hpp", "frp_occmap_fuse.hpp", "frp_occmap_raywalk.hpp", "frp_disturbance.hpp", os.path.join(ROOT, "include", "frp_nmpc.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_batch.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_fuse_points.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_occmap_check.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_occmap_distance.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_occmap_render.h"), os.path.join(ROOT, "include", "frp_nmpc_occmap_render_scan.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_occmap_view.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_corridor_large.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_command.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_outcome.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_fsm.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_vehicle.h"),
-           os.path.join(ROOT, "include", "frp_nmpc_estimator.h")]
+# what a source may include, for the staleness test: every header of csrc/ (by file name) and of include/ (by path)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".h", ".inc"))) + \
+          sorted(os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
 
 
 def hipcc():

@@ -436,3 +436,8 @@ def checked_ptr(like, a, dtype, shape):
     assert torch.is_tensor(a) and a.dtype == dtype and tuple(a.shape) == shape and a.is_contiguous() and a.device == like.device, \
         (tuple(a.shape), shape, a.dtype)
     return ctypes.c_void_p(a.data_ptr())
+
+
+def optional_ptr(like, a, dtype, shape):
+    """checked_ptr of an argument that may be absent: None stays None, anything else is checked as a required one."""
+    return None if a is None else checked_ptr(like, a, dtype, shape)

@@ -8,27 +8,24 @@
 //     after a workgroup barrier: what callback s published depends on kind[b][s] and the inputs alone, never on the status, so the
 //     samples are independent -- two 136-byte plan rows in, 128 bytes out, a handful of sin / cos.  Bandwidth-trivial: the cost is
 //     one launch.
-//   * The index (int)(t / Ts), the fraction fmod(t, Ts) / Ts and row[i] + w * (row[i + 1] - row[i]) are the host's operations, one
-//     rounding each: no contraction in this file (the build passes -ffp-contract=off as well), the division is IEEE, ocml's fmod
-//     is exact.  The interpolated slots are therefore the host's bits; sin / cos are ocml's, within an ulp or two of libm's.
-//   * The quaternion product and Quaternion::toRotationMatrix are Eigen's scalar expressions, term by term.
+//   * The plan test and the sampled row are frp_fleet.hpp's in_plan and plan_row, the host's operations, one rounding each: no
+//     contraction in this file (the build passes -ffp-contract=off as well).  The interpolated slots are therefore the host's bits;
+//     sin / cos are ocml's, within an ulp or two of libm's.
+//   * The quaternion product and the thrust column of Quaternion::toRotationMatrix are that header's too: Eigen's scalar expressions.
 //   * no atomics, no waiting between workgroups, no inline assembly; every store is a plain C++ store from a vector lane.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
+#include "frp_fleet.hpp"
 
 #pragma clang fp contract(off)
 
 namespace frp {
 namespace command {
 
-constexpr double REF_PI = 3.1415926; // the file's own constant (nmpc_solver.cpp:3)
-constexpr int THREADS = 256;
-constexpr int ROW = 17;
+using namespace fleet;
 
-struct Quat {
-    double w, x, y, z;
-};
+constexpr double REF_PI = 3.1415926; // the file's own constant (nmpc_solver.cpp:3)
 
 // Eigen::Quaternion(AngleAxis(angle, unit axis k)) (Geometry/Quaternion.h: ha = 0.5 * angle; w = cos(ha); vec = sin(ha) * axis) -- and
 // eulerToRot's Quaternion(cos(a / 2), .. sin(a / 2) ..) (:558-560): 0.5 * a and a / 2 are the same double, so the two products below
@@ -40,27 +37,10 @@ __device__ inline Quat axis_quat(double c, double s, int k)
     return q;
 }
 
-// a * b (Geometry/Quaternion.h, the scalar quat_product)
-__device__ inline Quat qmul(const Quat &a, const Quat &b)
-{
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
-    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
-    return r;
-}
-
-// eulerToRot(euler) * (0, 0, thrust) (:554-564, :926-927): the third column of Matrix3d(qz * qy * qx) (Quaternion::toRotationMatrix)
-// times the thrust -- the products of the other two columns with the zeros of thrust_b add nothing for finite angles
+// eulerToRot(euler) * (0, 0, thrust) (:554-564, :926-927): Matrix3d(qz * qy * qx) times the body thrust
 __device__ inline void thrust_world(const Quat &qx, const Quat &qy, const Quat &qz, double thrust, double *out)
 {
-    const Quat q = qmul(qmul(qz, qy), qx);
-    const double tx = 2.0 * q.x, ty = 2.0 * q.y, tz = 2.0 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, txx = tx * q.x, txz = tz * q.x, tyy = ty * q.y, tyz = tz * q.y;
-    out[0] = (txz + twy) * thrust;
-    out[1] = (tyz - twx) * thrust;
-    out[2] = (1.0 - (txx + tyy)) * thrust;
+    thrust_column(qmul(qmul(qz, qy), qx), thrust, out);
 }
 
 // sin and cos of a / 2.  Not inlined: ocml's argument reduction holds its constants in scalar registers, and one copy called three times
@@ -75,10 +55,6 @@ __device__ __noinline__ SinCos sincos_half(double a)
     r.s = sin(ha); r.c = cos(ha);
     return r;
 }
-
-// PUB_TRAJ's test (:907-909) on the doubles: for t >= 0 the truncation is a floor and floor(q) < N - 1 <=> q < N - 1; a NaN fails
-// both comparisons, a q beyond int fails the second
-__device__ inline bool in_plan(double t, double Ts, int N) { return t >= 0.0 && t / Ts < (double)(N - 1); }
 
 __global__ __launch_bounds__(THREADS) void command_kernel(frp_nmpc_command c, int planners_per_block)
 {
@@ -128,13 +104,9 @@ __global__ __launch_bounds__(THREADS) void command_kernel(frp_nmpc_command c, in
         for (int j = 0; j < FRP_COMMAND_STRIDE; j++) o[j] = 0.0;
         double roll = 0.0, pitch = 0.0, yaw = 0.0, thrust = 0.0; // the attitude every published sample carries
         if (k == FRP_COMMAND_TRAJ) { // :905-945
+            double q[ROW]; // mpcq (:911); 0 <= t / Ts < N - 1: phase 1 made the test
             const double t = c.t_cur[b * S + s];
-            const int idx = (int)(t / c.Ts);         // 0 <= t / Ts < N - 1: phase 1 made the test
-            const double w = fmod(t, c.Ts) / c.Ts;
-            const double *r0 = c.pre_plan + (b * c.N + idx) * ROW, *r1 = r0 + ROW;
-            double q[ROW]; // mpcq (:911); slots 4-7 (the previous input) are not published
-#pragma unroll
-            for (int j = 0; j < ROW; j++) q[j] = (j >= 4 && j < 8) ? 0.0 : r0[j] + w * (r1[j] - r0[j]);
+            plan_row(c.pre_plan, b * c.N, plan_stage(t, c.Ts), plan_fraction(t, c.Ts), q);
             o[0] = q[8]; o[1] = q[9]; o[2] = q[10];       // :913-915
             o[7] = q[11]; o[8] = q[12]; o[9] = q[13];     // :917-919
             o[10] = q[0]; o[11] = q[1]; o[12] = q[2];     // :921-923
@@ -195,14 +167,6 @@ __global__ __launch_bounds__(THREADS) void snapshot_kernel(int B, int N, const d
     if (i == b * per) have_traj[b] = 1;
 }
 
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static bool positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; } // finite and > 0; a NaN fails the first test
-
 } // namespace command
 } // namespace frp
 
@@ -215,15 +179,14 @@ int frp_nmpc_command_snapshot(int B, int N, const double *z, const int *accept, 
     const size_t blocks = ((size_t)B * N * ROW + THREADS - 1) / THREADS;
     if (blocks > 0x7fffffffu) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(snapshot_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, static_cast<hipStream_t>(stream), B, N, z, accept, pre_plan, have_traj);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(snapshot_kernel, (unsigned)blocks, stream, B, N, z, accept, pre_plan, have_traj);
 }
 
 int frp_nmpc_command_batch(const frp_nmpc_command *c, void *stream)
 {
     using namespace frp::command;
     if (!c || c->B < 1 || c->N < 2 || c->N > 64 || c->S < 1 || (long long)c->B * c->S > 0x7fffffffLL) return FRP_ERR_ARG;
-    if (!positive(c->Ts) || !positive(c->mass) || !(fabs(c->g) <= 1.7976931348623157e308)) return FRP_ERR_ARG;
+    if (!positive(c->Ts) || !positive(c->mass) || !finite_d(c->g)) return FRP_ERR_ARG;
     if (!c->pre_plan || !c->t_cur || !c->status || !c->have_traj || !c->pub_end || !c->end_pt) return FRP_ERR_ARG;
     if (!c->cmd || !c->kind || !c->finish || !c->reset_output) return FRP_ERR_ARG;
     const int yaw_inputs = (c->odom != nullptr) + (c->init_yaw != nullptr) + (c->t_yaw != nullptr);
@@ -231,8 +194,7 @@ int frp_nmpc_command_batch(const frp_nmpc_command *c, void *stream)
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     const int per_block = c->S >= THREADS ? 1 : THREADS / c->S; // whole planners per workgroup
     const unsigned blocks = (unsigned)(((long long)c->B + per_block - 1) / per_block);
-    hipLaunchKernelGGL(command_kernel, dim3(blocks), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *c, per_block);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(command_kernel, blocks, stream, *c, per_block);
 }
 
 } // extern "C"

@@ -17,8 +17,6 @@
 namespace frp {
 namespace disturbance {
 
-constexpr int THREADS = 256;
-
 __global__ __launch_bounds__(THREADS) void eval_kernel(frp_nmpc_disturbance d, int S, const double *pos, const double *base, int advance, double *force)
 {
     const int b = blockIdx.x * THREADS + threadIdx.x;
@@ -61,14 +59,6 @@ __global__ __launch_bounds__(THREADS) void reset_kernel(int B, const int *mask, 
     }
 }
 
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static unsigned blocks_for(int B) { return (unsigned)(((long long)B + THREADS - 1) / THREADS); }
-
 } // namespace disturbance
 } // namespace frp
 
@@ -79,8 +69,7 @@ int frp_nmpc_disturbance_eval(const frp_nmpc_disturbance *d, int S, const double
     using namespace frp::disturbance;
     if (check(d) != FRP_OK || S < 1 || (long long)d->B * S > 0x7fffffffLL || !pos || !force) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(eval_kernel, dim3(blocks_for(d->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *d, S, pos, base, advance, force);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(eval_kernel, blocks_for(d->B), stream, *d, S, pos, base, advance, force);
 }
 
 int frp_nmpc_disturbance_reset(const frp_nmpc_disturbance *d, const int *mask, void *stream)
@@ -88,8 +77,7 @@ int frp_nmpc_disturbance_reset(const frp_nmpc_disturbance *d, const int *mask, v
     using namespace frp::disturbance;
     if (check(d) != FRP_OK) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(d->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), d->B, mask, d->gust, d->tick);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(reset_kernel, blocks_for(d->B), stream, d->B, mask, d->gust, d->tick);
 }
 
 } // extern "C"

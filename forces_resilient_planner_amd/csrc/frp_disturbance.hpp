@@ -13,11 +13,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
+#include "frp_fleet.hpp"
 
 #pragma clang fp contract(off)
 
 namespace frp {
 namespace disturbance {
+
+using namespace fleet;
 
 constexpr int ZONE = FRP_DISTURBANCE_ZONE_STRIDE, EVENT = FRP_DISTURBANCE_EVENT_STRIDE;
 
@@ -103,16 +106,14 @@ __device__ inline void sample_force(const frp_nmpc_disturbance &d, const double 
 }
 
 // the argument rules of a frp_nmpc_disturbance (host)
-inline bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; } // (a NaN fails the comparison)
-
 inline int check(const frp_nmpc_disturbance *d)
 {
     if (!d || d->B < 1 || d->Z < 0 || d->Z > FRP_DISTURBANCE_MAX_ZONES || d->E < 0 || d->E > FRP_DISTURBANCE_MAX_EVENTS) return FRP_ERR_ARG;
     if ((d->zone == nullptr) != (d->Z == 0) || (d->event == nullptr) != (d->E == 0) || !d->tick) return FRP_ERR_ARG;
-    if (!finite_d(d->t_epoch) || !(d->dt > 0.0 && finite_d(d->dt))) return FRP_ERR_ARG;
+    if (!finite_d(d->t_epoch) || !positive(d->dt)) return FRP_ERR_ARG;
     if (d->gust) {
         for (int i = 0; i < 3; i++)
-            if (!(d->gust_a[i] >= 0.0 && d->gust_a[i] <= 1.0) || !(d->gust_c[i] >= 0.0 && finite_d(d->gust_c[i]))) return FRP_ERR_ARG;
+            if (!(d->gust_a[i] >= 0.0 && d->gust_a[i] <= 1.0) || !non_negative(d->gust_c[i])) return FRP_ERR_ARG;
     }
     return FRP_OK;
 }

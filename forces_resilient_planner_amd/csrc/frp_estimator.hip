@@ -19,16 +19,16 @@
 #include <math.h>
 #include "../../include/frp_nmpc.h"
 #include "frp_model.hpp"
+#include "frp_fleet.hpp"
 
 #pragma clang fp contract(off)
 
 namespace frp {
 namespace estimator {
 
-constexpr int THREADS = 256;
-constexpr int NXV = FRP_VEHICLE_STATE;
+using namespace fleet;
 
-__device__ inline bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; } // (a NaN fails the comparison)
+constexpr int NXV = FRP_VEHICLE_STATE;
 
 __global__ __launch_bounds__(THREADS) void update_kernel(frp_nmpc_estimator c)
 {
@@ -116,16 +116,6 @@ __global__ __launch_bounds__(THREADS) void reset_kernel(int B, const int *mask, 
     fresh[b] = 0;
 }
 
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static bool positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; } // finite and > 0 (a NaN fails)
-
-static unsigned blocks_for(int B) { return (unsigned)(((long long)B + THREADS - 1) / THREADS); }
-
 } // namespace estimator
 } // namespace frp
 
@@ -138,8 +128,7 @@ int frp_nmpc_estimator_update(const frp_nmpc_estimator *e, void *stream)
     if (!positive(e->dt) || !(e->alpha > 0.0 && e->alpha <= 1.0)) return FRP_ERR_ARG;
     if (!e->meas || !e->thrust || !e->f_hat || !e->y_prev || !e->count || !e->force || !e->fresh) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(update_kernel, dim3(blocks_for(e->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *e);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(update_kernel, blocks_for(e->B), stream, *e);
 }
 
 int frp_nmpc_estimator_reset(int B, const int *mask, double *f_hat, double *y_prev, int *count, double *force, int *fresh, void *stream)
@@ -147,8 +136,7 @@ int frp_nmpc_estimator_reset(int B, const int *mask, double *f_hat, double *y_pr
     using namespace frp::estimator;
     if (B < 1 || !f_hat || !y_prev || !count || !force || !fresh) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), B, mask, f_hat, count, force, fresh);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(reset_kernel, blocks_for(B), stream, B, mask, f_hat, count, force, fresh);
 }
 
 } // extern "C"

@@ -22,13 +22,21 @@
 #include <limits.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
+#include "frp_fleet.hpp"
 
 #pragma clang fp contract(off)
 
 namespace frp {
 namespace flight {
 
+// (by name, not the whole namespace: THREADS and ROW below are this unit's own)
+using fleet::blocks_for;
+using fleet::device_ok;
+using fleet::finite_d;
+using fleet::launch;
+
 constexpr int THREADS = FRP_FLIGHT_GROUP;
+static_assert(THREADS == fleet::THREADS, "the summary's group is the workgroup fleet::blocks_for and fleet::launch count in");
 constexpr int WAVE = 64;
 constexpr int WAVES = THREADS / WAVE;
 constexpr int NI = FRP_FLIGHT_SUM_INTS;
@@ -38,7 +46,6 @@ constexpr int ROW = NI + NBIN + NF; // eight-byte words per workgroup in the wor
 static_assert(ROW <= THREADS, "the second launch takes one partial per thread");
 static_assert(sizeof(long long) == 8 && sizeof(double) == 8, "one row is ROW eight-byte words");
 
-__device__ inline bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; } // (a NaN fails the comparison)
 __device__ inline bool finite3(const double *v) { return finite_d(v[0]) && finite_d(v[1]) && finite_d(v[2]); }
 __device__ inline double sq3(double x, double y, double z) { return (x * x + y * y) + z * z; }
 
@@ -286,22 +293,12 @@ __global__ __launch_bounds__(THREADS) void summary_final_kernel(int G, int n_edg
     }
 }
 
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static unsigned blocks_for(int B) { return (unsigned)(((long long)B + THREADS - 1) / THREADS); }
-
 static bool complete(const frp_nmpc_flight_record *r)
 {
     return r && r->B >= 0 && r->p_prev && r->have_prev && r->track_max2 && r->track_sum2 && r->track_n && r->path_len && r->speed_max2 && r->samples &&
            r->flown && r->bad && r->sat_samples && r->sat_bits && r->periods && r->ticks_run && r->ticks_converged && r->result_hist && r->state_hist &&
            r->first_arrival;
 }
-
-static int launched() { return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP; }
 
 } // namespace flight
 } // namespace frp
@@ -316,8 +313,7 @@ int frp_nmpc_flight_record_samples(const frp_nmpc_flight_record *rec, int S, con
     if ((long long)rec->B * S > 0x7fffffffLL || (long long)rec->B * S * stride > 0x7fffffffLL) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     if (rec->B == 0) return FRP_OK;
-    hipLaunchKernelGGL(samples_kernel, dim3(blocks_for(rec->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *rec, S, trace, stride, cmd, kind, sat, active);
-    return launched();
+    return launch(samples_kernel, blocks_for(rec->B), stream, *rec, S, trace, stride, cmd, kind, sat, active);
 }
 
 int frp_nmpc_flight_record_period(const frp_nmpc_flight_record *rec, const int *fsm_state, const int *gate, const int *result,
@@ -327,8 +323,7 @@ int frp_nmpc_flight_record_period(const frp_nmpc_flight_record *rec, const int *
     if (!complete(rec) || !fsm_state || !gate || !result || !exit_code) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     if (rec->B == 0) return FRP_OK;
-    hipLaunchKernelGGL(period_kernel, dim3(blocks_for(rec->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *rec, fsm_state, gate, result, exit_code, active);
-    return launched();
+    return launch(period_kernel, blocks_for(rec->B), stream, *rec, fsm_state, gate, result, exit_code, active);
 }
 
 int frp_nmpc_flight_record_reset(const frp_nmpc_flight_record *rec, const int *mask, const double *x, void *stream)
@@ -337,8 +332,7 @@ int frp_nmpc_flight_record_reset(const frp_nmpc_flight_record *rec, const int *m
     if (!complete(rec)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     if (rec->B == 0) return FRP_OK;
-    hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(rec->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *rec, mask, x);
-    return launched();
+    return launch(reset_kernel, blocks_for(rec->B), stream, *rec, mask, x);
 }
 
 size_t frp_nmpc_flight_summary_workspace_bytes(int B)
@@ -359,14 +353,9 @@ int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min
     if (workspace_bytes < frp_nmpc_flight_summary_workspace_bytes(rec->B)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     const unsigned G = blocks_for(rec->B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     long long *ws = static_cast<long long *>(workspace);
-    if (G > 0) {
-        hipLaunchKernelGGL(summary_partial_kernel, dim3(G), dim3(THREADS), 0, s, *rec, min_clear, hits, mask, n_edges, edges, ws);
-        if (hipGetLastError() != hipSuccess) return FRP_ERR_HIP;
-    }
-    hipLaunchKernelGGL(summary_final_kernel, dim3(1), dim3(THREADS), 0, s, (int)G, n_edges, ws, out_i, out_f, hist);
-    return launched();
+    if (G > 0 && launch(summary_partial_kernel, G, stream, *rec, min_clear, hits, mask, n_edges, edges, ws) != FRP_OK) return FRP_ERR_HIP;
+    return launch(summary_final_kernel, 1, stream, (int)G, n_edges, ws, out_i, out_f, hist);
 }
 
 } // extern "C"

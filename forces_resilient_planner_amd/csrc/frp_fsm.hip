@@ -5,24 +5,23 @@
 //   * One thread per planner, 256 per workgroup, no LDS, no barrier: a planner's callbacks read and write its own entries alone.  Per
 //     planner a dozen 4-byte flags and a few 24-byte vectors; exec_begin also reads two 136-byte plan rows where a planner replans from
 //     its plan.  The kernels cost their launch.
-//   * The start state's index (int)(t / Ts), fraction fmod(t, Ts) / Ts and row[i] + w * (row[i + 1] - row[i]) are frp_command.hip's
-//     PUB_TRAJ operations, one rounding each: no contraction in this file (the build passes -ffp-contract=off as well), an IEEE
-//     division, ocml's exact fmod.  The world acceleration is that file's thrust_world, term by term.  Both are DUPLICATED here, not
-//     shared through a header: frp_command.hip's object stays the one its bit-exact tests were run on.
+//   * The replan start state is the command timer's sample of the same plan at the same time: frp_fleet.hpp's in_plan and plan_row for
+//     position and velocity, its quaternion product and thrust column for the world acceleration.  No contraction in this file (the
+//     build passes -ffp-contract=off as well).
 //   * atan2, sin and cos are ocml's, within an ulp or two of libm's; the 0.8 yaw threshold is tested on the device's own atan2.
 //   * Every index is bounded by what the entry points checked; the plan row index by the in_plan test made on the doubles.
 //   * no atomics, no waiting between workgroups, no inline assembly; every store is a plain C++ store from a vector lane.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
+#include "frp_fleet.hpp"
 
 #pragma clang fp contract(off)
 
 namespace frp {
 namespace fsm {
 
-constexpr int THREADS = 256;
-constexpr int ROW = 17;
+using namespace fleet;
 
 // std::max(a, b) = (a < b) ? b : a
 __device__ inline double smax(double a, double b) { return (a < b) ? b : a; }
@@ -114,37 +113,13 @@ __global__ __launch_bounds__(THREADS) void safety_kernel(frp_nmpc_fsm f, const i
     f.state[b] = st;
 }
 
-struct Quat {
-    double w, x, y, z;
-};
-
-// Eigen's quat_product, scalar form (frp_command.hip: qmul)
-__device__ inline Quat qmul(const Quat &a, const Quat &b)
-{
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
-    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
-    return r;
-}
-
-// eulerToRot(euler) * (0, 0, thrust) (nmpc_solver.cpp:554-564, :176-178): the third column of Matrix3d(qz * qy * qx) times the thrust
-// (frp_command.hip: thrust_world)
+// eulerToRot(euler) * (0, 0, thrust) (nmpc_solver.cpp:554-564, :176-178): Matrix3d(qz * qy * qx) times the body thrust
 __device__ inline void thrust_world(double roll, double pitch, double yaw, double thrust, double *out)
 {
     const double hr = 0.5 * roll, hp = 0.5 * pitch, hy = 0.5 * yaw;
     const Quat qx = {cos(hr), sin(hr), 0.0, 0.0}, qy = {cos(hp), 0.0, sin(hp), 0.0}, qz = {cos(hy), 0.0, 0.0, sin(hy)};
-    const Quat q = qmul(qmul(qz, qy), qx);
-    const double tx = 2.0 * q.x, ty = 2.0 * q.y, tz = 2.0 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, txx = tx * q.x, txz = tz * q.x, tyy = ty * q.y, tyz = tz * q.y;
-    out[0] = (txz + twy) * thrust;
-    out[1] = (tyz - twx) * thrust;
-    out[2] = (1.0 - (txx + tyy)) * thrust;
+    thrust_column(qmul(qmul(qz, qy), qx), thrust, out);
 }
-
-// nmpc_solver.cpp:164-167 on the doubles (frp_command.hip: in_plan): a NaN fails both comparisons, a quotient beyond int the second
-__device__ inline bool in_plan(double t, double Ts, int N) { return t >= 0.0 && t / Ts < (double)(N - 1); }
 
 // NM:127-259 up to getKinoPath, nmpc_solver.cpp:148-186 and callInitYaw's stores (:232-235, :261)
 __global__ __launch_bounds__(THREADS) void exec_begin_kernel(frp_nmpc_fsm f, frp_nmpc_fsm_exec_in in)
@@ -193,12 +168,8 @@ __global__ __launch_bounds__(THREADS) void exec_begin_kernel(frp_nmpc_fsm f, frp
             double sp[3] = {od[0], od[1], od[2]}, sv[3] = {od[3], od[4], od[5]}, sa[3] = {0.0, 0.0, 0.0}; // :151-153
             const double t = in.t_cur[b];
             if (st == FRP_FSM_REPLAN_TRAJ && in.exit_code[b] == 1 && in_plan(t, in.Ts, in.N)) { // :160, :167
-                const int idx = (int)(t / in.Ts);          // :164, 0 <= t / Ts < N - 1
-                const double w = fmod(t, in.Ts) / in.Ts;   // :169
-                const double *r0 = in.pre_plan + ((size_t)b * in.N + idx) * ROW, *r1 = r0 + ROW;
-                double q[ROW];
-#pragma unroll
-                for (int j = 0; j < ROW; j++) q[j] = (j >= 4 && j < 8) ? 0.0 : r0[j] + w * (r1[j] - r0[j]);
+                double q[ROW]; // :164, :169-171, 0 <= t / Ts < N - 1
+                plan_row(in.pre_plan, (size_t)b * in.N, plan_stage(t, in.Ts), plan_fraction(t, in.Ts), q);
                 sp[0] = q[8]; sp[1] = q[9]; sp[2] = q[10];   // :173
                 sv[0] = q[11]; sv[1] = q[12]; sv[2] = q[13]; // :174
                 double tw[3];
@@ -243,22 +214,12 @@ __global__ __launch_bounds__(THREADS) void exec_end_kernel(frp_nmpc_fsm f, const
     }
 }
 
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static bool positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; } // finite and > 0; a NaN fails the first test
-
 static bool fsm_ok(const frp_nmpc_fsm *f)
 {
     return f && f->B >= 1 && f->state && f->have_odom && f->have_target && f->have_traj && f->trigger && f->call_init_yaw && f->consider_force &&
            f->replan_force_surpass && f->surpass_count && f->plan_fail_count && f->exec_mpc && f->cmd_status && f->pub_end && f->end_pt &&
            f->external_acc && f->last_external_acc && f->init_yaw && f->yaw_odom && f->change_yaw_time && f->kino_start_time;
 }
-
-static unsigned blocks_of(int B) { return (unsigned)(((long long)B + THREADS - 1) / THREADS); }
 
 } // namespace fsm
 } // namespace frp
@@ -270,18 +231,16 @@ int frp_nmpc_fsm_goal(const frp_nmpc_fsm *f, const double *goal, const int *fres
     using namespace frp::fsm;
     if (!fsm_ok(f) || !goal || !fresh) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(goal_kernel, dim3(blocks_of(f->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *f, goal, fresh);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(goal_kernel, blocks_for(f->B), stream, *f, goal, fresh);
 }
 
 int frp_nmpc_fsm_force(const frp_nmpc_fsm *f, const double *force, const int *fresh, double ext_noise_bound, void *stream)
 {
     using namespace frp::fsm;
     if (!fsm_ok(f) || !force || !fresh) return FRP_ERR_ARG;
-    if (!(ext_noise_bound >= 0.0 && ext_noise_bound <= 1.7976931348623157e308)) return FRP_ERR_ARG;
+    if (!non_negative(ext_noise_bound)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(force_kernel, dim3(blocks_of(f->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *f, force, fresh, ext_noise_bound);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(force_kernel, blocks_for(f->B), stream, *f, force, fresh, ext_noise_bound);
 }
 
 int frp_nmpc_fsm_mpc(const frp_nmpc_fsm *f, const int *result, void *stream)
@@ -289,8 +248,7 @@ int frp_nmpc_fsm_mpc(const frp_nmpc_fsm *f, const int *result, void *stream)
     using namespace frp::fsm;
     if (!fsm_ok(f) || !result) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(mpc_kernel, dim3(blocks_of(f->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *f, result);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(mpc_kernel, blocks_for(f->B), stream, *f, result);
 }
 
 int frp_nmpc_fsm_safety(const frp_nmpc_fsm *f, const int *goal_blocked, const int *first_hit, void *stream)
@@ -298,20 +256,18 @@ int frp_nmpc_fsm_safety(const frp_nmpc_fsm *f, const int *goal_blocked, const in
     using namespace frp::fsm;
     if (!fsm_ok(f) || !goal_blocked || !first_hit) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(safety_kernel, dim3(blocks_of(f->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *f, goal_blocked, first_hit);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(safety_kernel, blocks_for(f->B), stream, *f, goal_blocked, first_hit);
 }
 
 int frp_nmpc_fsm_exec_begin(const frp_nmpc_fsm *f, const frp_nmpc_fsm_exec_in *in, void *stream)
 {
     using namespace frp::fsm;
     if (!fsm_ok(f) || !in) return FRP_ERR_ARG;
-    if (in->N < 2 || in->N > 64 || !positive(in->Ts) || !positive(in->mass) || !(fabs(in->g) <= 1.7976931348623157e308)) return FRP_ERR_ARG;
+    if (in->N < 2 || in->N > 64 || !positive(in->Ts) || !positive(in->mass) || !finite_d(in->g)) return FRP_ERR_ARG;
     if (!in->state || !in->pre_plan || !in->exit_code || !in->t_cur || !in->now) return FRP_ERR_ARG;
     if (!in->search || !in->start_pt || !in->start_vel || !in->start_acc || !in->retry_pt || !in->retry_vel) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(exec_begin_kernel, dim3(blocks_of(f->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *f, *in);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(exec_begin_kernel, blocks_for(f->B), stream, *f, *in);
 }
 
 int frp_nmpc_fsm_exec_end(const frp_nmpc_fsm *f, const int *search, const int *astar_status, const double *now, void *stream)
@@ -319,8 +275,7 @@ int frp_nmpc_fsm_exec_end(const frp_nmpc_fsm *f, const int *search, const int *a
     using namespace frp::fsm;
     if (!fsm_ok(f) || !search || !astar_status || !now) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(exec_end_kernel, dim3(blocks_of(f->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *f, search, astar_status, now);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(exec_end_kernel, blocks_for(f->B), stream, *f, search, astar_status, now);
 }
 
 } // extern "C"

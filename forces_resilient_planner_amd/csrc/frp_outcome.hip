@@ -14,14 +14,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/frp_nmpc.h"
+#include "frp_fleet.hpp"
 
 #pragma clang fp contract(off)
 
 namespace frp {
 namespace outcome {
 
-constexpr int THREADS = 256;
-constexpr int ROW = 17;
+using namespace fleet;
 
 // Eigen's (a - b).norm() for three doubles: sqrt((d0 * d0 + d1 * d1) + d2 * d2)
 __device__ inline double dist(const double *a, const double *b)
@@ -115,14 +115,6 @@ __global__ __launch_bounds__(THREADS) void tick_end_kernel(frp_nmpc_tick t, frp_
     if (t.exec_mpc && (result == -2 || result == -3)) t.exec_mpc[b] = 0; // nmpc_manage.cpp:78-93
 }
 
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static bool positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; } // finite and > 0; a NaN fails the first test
-
 static bool tick_ok(const frp_nmpc_tick *t)
 {
     return t && t->B >= 1 && t->fail_count && t->replan_count && t->kino_replan && t->exit_code && t->initialized && t->cmd_status && t->pub_end &&
@@ -139,9 +131,7 @@ int frp_nmpc_tick_begin(const frp_nmpc_tick *t, int *reset_output, void *stream)
     using namespace frp::outcome;
     if (!tick_ok(t)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    const unsigned blocks = (unsigned)(((long long)t->B + THREADS - 1) / THREADS);
-    hipLaunchKernelGGL(tick_begin_kernel, dim3(blocks), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *t, reset_output);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(tick_begin_kernel, blocks_for(t->B), stream, *t, reset_output);
 }
 
 int frp_nmpc_tick_end(const frp_nmpc_tick *t, const frp_nmpc_tick_in *in, void *stream)
@@ -152,9 +142,7 @@ int frp_nmpc_tick_end(const frp_nmpc_tick *t, const frp_nmpc_tick_in *in, void *
     if (!in->z || !in->exitflag || !in->mpc_output || !in->state || !in->end_pt || !in->kino_path || !in->kino_size || !in->time_offset || !in->ref_replan)
         return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    const unsigned blocks = (unsigned)(((long long)t->B + THREADS - 1) / THREADS);
-    hipLaunchKernelGGL(tick_end_kernel, dim3(blocks), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *t, *in);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(tick_end_kernel, blocks_for(t->B), stream, *t, *in);
 }
 
 } // extern "C"

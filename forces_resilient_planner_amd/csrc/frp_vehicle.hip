@@ -27,46 +27,21 @@
 #include "../../include/frp_nmpc.h"
 #include "frp_model.hpp"
 #include "frp_disturbance.hpp"
+#include "frp_fleet.hpp"
 
 #pragma clang fp contract(off)
 
 namespace frp {
 namespace vehicle {
 
-constexpr int THREADS = 256;
+using namespace fleet;
+
 constexpr int NXV = FRP_VEHICLE_STATE, HOLD = FRP_VEHICLE_HOLD_STRIDE, MSG = FRP_VEHICLE_MSG_STRIDE, CMD = FRP_COMMAND_STRIDE;
 
 __device__ inline double clampd(double v, double lo, double hi, int *which)
 {
     *which = v < lo ? -1 : v > hi ? 1 : 0;
     return v < lo ? lo : v > hi ? hi : v;
-}
-
-struct Quat {
-    double w, x, y, z;
-};
-
-// a * b (Eigen Geometry/Quaternion.h, the scalar quat_product)
-__device__ inline Quat qmul(const Quat &a, const Quat &b)
-{
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
-    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
-    return r;
-}
-
-// Quaternion::toRotationMatrix, row-major
-__device__ inline void rotation(const Quat &q, double R[9])
-{
-    const double tx = 2.0 * q.x, ty = 2.0 * q.y, tz = 2.0 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
 }
 
 // OBSERVED: frp_nmpc_vehicle_step_observed's instantiation (frp_nmpc_estimator.h) also stores the clamped thrust of every sample;
@@ -283,18 +258,6 @@ __global__ __launch_bounds__(THREADS) void odometry_kernel(int B, int type, cons
     have_odom[b] = 1; // :447, :477
 }
 
-static bool device_ok()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
-static bool is_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }            // (a NaN fails the comparison)
-static bool positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }     // finite and > 0
-static bool gain(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }        // finite and >= 0
-
-static unsigned blocks_for(int B) { return (unsigned)(((long long)B + THREADS - 1) / THREADS); }
-
 } // namespace vehicle
 } // namespace frp
 
@@ -305,9 +268,9 @@ static int step_args(const frp_nmpc_vehicle *v)
 {
     using namespace frp::vehicle;
     if (!v || v->B < 1 || v->S < 1 || (long long)v->B * v->S > 0x7fffffffLL || v->n_sub < 1 || v->n_sub > FRP_VEHICLE_MAX_SUB) return FRP_ERR_ARG;
-    if (!positive(v->mass) || !positive(v->dt_cmd) || !is_finite(v->g)) return FRP_ERR_ARG;
+    if (!positive(v->mass) || !positive(v->dt_cmd) || !finite_d(v->g)) return FRP_ERR_ARG;
     for (int i = 0; i < 3; i++)
-        if (!gain(v->kp[i]) || !gain(v->kv[i]) || !gain(v->ka[i])) return FRP_ERR_ARG;
+        if (!non_negative(v->kp[i]) || !non_negative(v->kv[i]) || !non_negative(v->ka[i])) return FRP_ERR_ARG;
     if (!v->x || !v->f_true || !v->cmd || !v->kind || !v->hold) return FRP_ERR_ARG;
     return FRP_OK;
 }
@@ -317,9 +280,7 @@ int frp_nmpc_vehicle_step(const frp_nmpc_vehicle *v, void *stream)
     using namespace frp::vehicle;
     if (step_args(v) != FRP_OK) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL((step_kernel<false, false>), dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, static_cast<double *>(nullptr),
-                       frp_nmpc_disturbance{}, static_cast<double *>(nullptr));
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(step_kernel<false, false>, blocks_for(v->B), stream, *v, nullptr, frp_nmpc_disturbance{}, nullptr);
 }
 
 // frp_nmpc_estimator.h
@@ -328,9 +289,7 @@ int frp_nmpc_vehicle_step_observed(const frp_nmpc_vehicle *v, double *thrust, vo
     using namespace frp::vehicle;
     if (step_args(v) != FRP_OK || !thrust) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL((step_kernel<true, false>), dim3(blocks_for(v->B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), *v, thrust, frp_nmpc_disturbance{},
-                       static_cast<double *>(nullptr));
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(step_kernel<true, false>, blocks_for(v->B), stream, *v, thrust, frp_nmpc_disturbance{}, nullptr);
 }
 
 // frp_nmpc.h section (15)
@@ -339,12 +298,7 @@ int frp_nmpc_vehicle_step_field(const frp_nmpc_vehicle *v, const frp_nmpc_distur
     using namespace frp::vehicle;
     if (step_args(v) != FRP_OK || frp::disturbance::check(d) != FRP_OK || d->B != v->B || !(d->dt == v->dt_cmd)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    const dim3 grid(blocks_for(v->B)), block(THREADS);
-    if (thrust)
-        hipLaunchKernelGGL((step_kernel<true, true>), grid, block, 0, static_cast<hipStream_t>(stream), *v, thrust, *d, force);
-    else
-        hipLaunchKernelGGL((step_kernel<false, true>), grid, block, 0, static_cast<hipStream_t>(stream), *v, thrust, *d, force);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(thrust ? step_kernel<true, true> : step_kernel<false, true>, blocks_for(v->B), stream, *v, thrust, *d, force);
 }
 
 int frp_nmpc_vehicle_reset(int B, const double *x0, const int *mask, double *x, double *hold, void *stream)
@@ -352,8 +306,7 @@ int frp_nmpc_vehicle_reset(int B, const double *x0, const int *mask, double *x, 
     using namespace frp::vehicle;
     if (B < 1 || !x0 || !x || !hold) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), B, x0, mask, x, hold);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(reset_kernel, blocks_for(B), stream, B, x0, mask, x, hold);
 }
 
 int frp_nmpc_vehicle_message(int B, int type, const double *x, double *msg, void *stream)
@@ -361,8 +314,7 @@ int frp_nmpc_vehicle_message(int B, int type, const double *x, double *msg, void
     using namespace frp::vehicle;
     if (B < 1 || (type != FRP_ODOM_WORLD && type != FRP_ODOM_BODY) || !x || !msg) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(message_kernel, dim3(blocks_for(B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), B, type, x, msg);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(message_kernel, blocks_for(B), stream, B, type, x, msg);
 }
 
 int frp_nmpc_vehicle_odometry(int B, int type, const double *msg, const int *fresh, double *state, double *state_prev, int *have_odom, void *stream)
@@ -370,8 +322,7 @@ int frp_nmpc_vehicle_odometry(int B, int type, const double *msg, const int *fre
     using namespace frp::vehicle;
     if (B < 1 || (type != FRP_ODOM_WORLD && type != FRP_ODOM_BODY) || !msg || !fresh || !state || !have_odom) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(odometry_kernel, dim3(blocks_for(B)), dim3(THREADS), 0, static_cast<hipStream_t>(stream), B, type, msg, fresh, state, state_prev, have_odom);
-    return hipGetLastError() == hipSuccess ? FRP_OK : FRP_ERR_HIP;
+    return launch(odometry_kernel, blocks_for(B), stream, B, type, msg, fresh, state, state_prev, have_odom);
 }
 
 } // extern "C"

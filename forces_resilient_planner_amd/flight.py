@@ -7,7 +7,7 @@ import ctypes
 from . import layout as L
 from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, ODOM_BODY, ODOM_WORLD,
                    TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
-                   checked_ptr, lib, stream_ptr, tensor_ptr)
+                   checked_ptr, lib, optional_ptr, stream_ptr, tensor_ptr)
 from .fleet import TickState
 from .occmap import SafetyCheck
 from .planning import COMMAND_DEFAULTS
@@ -64,7 +64,7 @@ class Vehicle:
         """frp_nmpc_vehicle_reset: where mask [B] int32 != 0 (None: everywhere) x <- x0 [B,9] and hold <- its position and yaw: the
         vehicle hovers there until something is published.  `state` is the callbacks': call odometry(fsm) to publish the new pose."""
         t = self.torch
-        m = checked_ptr(self.x, mask, t.int32, (self.B,)) if mask is not None else None
+        m = optional_ptr(self.x, mask, t.int32, (self.B,))
         _check(lib().frp_nmpc_vehicle_reset(self.B, checked_ptr(self.x, x0, t.float64, (self.B, VEHICLE_STATE)), m, tensor_ptr(self.x),
                                             tensor_ptr(self.hold), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_reset")
         if self.estimator is not None:
@@ -175,7 +175,7 @@ class ForceEstimator:
     def reset(self, mask=None, stream=None):
         """frp_nmpc_estimator_reset: where mask [B] int32 != 0 (None: everywhere) f_hat <- 0, count <- -1, force <- 0, fresh <- 0."""
         t, v = self.torch, self.vehicle
-        m = checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None
+        m = optional_ptr(v.x, mask, t.int32, (self.B,))
         state = map(tensor_ptr, (self.f_hat, self.y_prev, self.count, self.force, self.fresh))
         _check(lib().frp_nmpc_estimator_reset(self.B, m, *state, stream_ptr(stream, v.x)), "frp_nmpc_estimator_reset")
 
@@ -250,7 +250,7 @@ class Disturbance:
         out = t.empty((self.B, S, 3), dtype=t.float64, device=v.x.device) if out is None else out
         d = self.struct()
         _check(lib().frp_nmpc_disturbance_eval(ctypes.byref(d), S, checked_ptr(v.x, pos, t.float64, (self.B, S, 3)),
-                                               checked_ptr(v.x, base, t.float64, (self.B, 3)) if base is not None else None, int(bool(advance)),
+                                               optional_ptr(v.x, base, t.float64, (self.B, 3)), int(bool(advance)),
                                                checked_ptr(v.x, out, t.float64, (self.B, S, 3)), stream_ptr(stream, v.x)), "frp_nmpc_disturbance_eval")
         return out
 
@@ -258,7 +258,7 @@ class Disturbance:
         """frp_nmpc_disturbance_reset: where mask [B] int32 != 0 (None: everywhere) tick <- 0 and the OU state <- 0."""
         t, v = self.torch, self.vehicle
         d = self.struct()
-        _check(lib().frp_nmpc_disturbance_reset(ctypes.byref(d), checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None,
+        _check(lib().frp_nmpc_disturbance_reset(ctypes.byref(d), optional_ptr(v.x, mask, t.int32, (self.B,)),
                                                 stream_ptr(stream, v.x)), "frp_nmpc_disturbance_reset")
 
 
@@ -328,8 +328,8 @@ class FlightRecord:
         _check(lib().frp_nmpc_flight_record_samples(ctypes.byref(r), S, checked_ptr(v.x, trace, t.float64, (self.B, S, stride)), stride,
                                                     checked_ptr(v.x, commands.cmd, t.float64, (self.B, S, COMMAND_STRIDE)),
                                                     checked_ptr(v.x, commands.kind, t.int32, (self.B, S)),
-                                                    checked_ptr(v.x, sat, t.int32, (self.B, S)) if sat is not None else None,
-                                                    checked_ptr(v.x, active, t.int32, (self.B,)) if active is not None else None,
+                                                    optional_ptr(v.x, sat, t.int32, (self.B, S)),
+                                                    optional_ptr(v.x, active, t.int32, (self.B,)),
                                                     stream_ptr(stream, v.x)), "frp_nmpc_flight_record_samples")
 
     def update_period(self, fsm, active=None, stream=None):
@@ -338,7 +338,7 @@ class FlightRecord:
         r = self.struct()
         p = lambda a: checked_ptr(v.x, a, t.int32, (self.B,))
         _check(lib().frp_nmpc_flight_record_period(ctypes.byref(r), p(fsm.state), p(tk.gate), p(tk.result), p(tk.exit_code),
-                                                   p(active) if active is not None else None, stream_ptr(stream, v.x)), "frp_nmpc_flight_record_period")
+                                                   optional_ptr(v.x, active, t.int32, (self.B,)), stream_ptr(stream, v.x)), "frp_nmpc_flight_record_period")
 
     def reset(self, mask=None, x=None, stream=None):
         """frp_nmpc_flight_record_reset: where mask [B] int32 != 0 (None: everywhere) everything <- 0, first_arrival <- -1 and, with x
@@ -346,8 +346,8 @@ class FlightRecord:
         is not tracked."""
         t, v = self.torch, self.vehicle
         r = self.struct()
-        _check(lib().frp_nmpc_flight_record_reset(ctypes.byref(r), checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None,
-                                                  checked_ptr(v.x, x, t.float64, (self.B, VEHICLE_STATE)) if x is not None else None,
+        _check(lib().frp_nmpc_flight_record_reset(ctypes.byref(r), optional_ptr(v.x, mask, t.int32, (self.B,)),
+                                                  optional_ptr(v.x, x, t.float64, (self.B, VEHICLE_STATE)),
                                                   stream_ptr(stream, v.x)), "frp_nmpc_flight_record_reset")
 
     def summary(self, mask=None, edges=None, stream=None):
@@ -361,7 +361,7 @@ class FlightRecord:
             raise ValueError(f"FlightRecord.summary: at most {FLIGHT_MAX_EDGES} edges")
         r = self.struct()
         _check(lib().frp_nmpc_flight_summary(ctypes.byref(r), tensor_ptr(c.min_clear) if c is not None else None, tensor_ptr(c.hits) if c is not None else None,
-                                             checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None, n,
+                                             optional_ptr(v.x, mask, t.int32, (self.B,)), n,
                                              checked_ptr(v.x, edges, t.float64, (n,)) if n else None, tensor_ptr(self.sum_ints), tensor_ptr(self.sum_floats),
                                              tensor_ptr(self.sum_hist), tensor_ptr(self._ws), self._ws_bytes, stream_ptr(stream, v.x)), "frp_nmpc_flight_summary")
         return FlightSummary(self.sum_ints, self.sum_floats, self.sum_hist[:n + 1])

@@ -6,7 +6,7 @@ import numpy as np
 
 from .capi import (CORRIDOR_LARGE_MAX_POINTS, CORRIDOR_MAX_CELLS, CORRIDOR_MAX_POINTS, FRP_ERR_ARG, OCCMAP_DIST_MAX_R, OCCMAP_VIEW_MAX_GROUPS,
                    CorridorCut, CorridorLarge, OccMap, OccMapBody, OccMapFuse, OccMapFuseBatch, OccMapFusePoints, OccMapRender, OccMapRenderScan,
-                   OccMapSharedView, OccMapView, _check, checked_ptr, lib, stream_ptr, tensor_ptr)
+                   OccMapSharedView, OccMapView, _check, checked_ptr, lib, optional_ptr, stream_ptr, tensor_ptr)
 
 # OccMap's ROS parameter defaults (occ_map.cpp:752-754) and the local range of the reference's launch files
 OCCMAP_DEFAULTS = dict(clamp_min_log=0.12, clamp_max_log=0.97, min_occupancy_log=0.80, local_radius=(6.0, 6.0, 3.0))
@@ -726,7 +726,7 @@ class FlightClearance:
         S, stride = int(trace.shape[1]), int(trace.shape[2])
         if S < 1 or stride < 3:
             raise ValueError("FlightClearance.update: trace is [B, S >= 1, stride >= 3]")
-        a = checked_ptr(v.x, active, t.int32, (self.B,)) if active is not None else None
+        a = optional_ptr(v.x, active, t.int32, (self.B,))
         f = self.field
         m = f.occmap._map()
         _check(lib().frp_nmpc_occmap_clearance_trace(ctypes.byref(m), tensor_ptr(f.field), f.R, self.B, S, stride,
@@ -737,7 +737,7 @@ class FlightClearance:
     def reset(self, mask=None, stream=None):
         """frp_nmpc_occmap_clearance_reset: where mask [B] int32 != 0 (None: everywhere) min_clear <- +inf, hits <- 0, samples <- 0."""
         t, v = self.torch, self.vehicle
-        m = checked_ptr(v.x, mask, t.int32, (self.B,)) if mask is not None else None
+        m = optional_ptr(v.x, mask, t.int32, (self.B,))
         _check(lib().frp_nmpc_occmap_clearance_reset(self.B, m, tensor_ptr(self.min_clear), tensor_ptr(self.hits),
                                                      tensor_ptr(self.samples), stream_ptr(stream, v.x)), "frp_nmpc_occmap_clearance_reset")
 

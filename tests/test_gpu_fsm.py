@@ -140,6 +140,40 @@ def test_c_start_state_at_the_edges_of_the_plan_test(N):
     assert n_plan >= 50
 
 
+def test_c_replan_start_state_is_the_command_timers_sample():
+    """The two users of csrc/frp_fleet.hpp's plan sampling on one plan at one time: a planner in REPLAN_TRAJ with exit_code 1 starts its
+    search where the command timer, in PUB_TRAJ with a trajectory, publishes its sample -- position, velocity and acceleration bit for bit.
+    B = 257 (one more than a workgroup), N = 20, S = 1; t_cur on a stage boundary, inside the first and the last stage, 0.0 and seeded
+    draws in [0, (N - 1) Ts): every planner is inside its plan, in both kernels.  The acceleration goes through the device library's sin
+    and cos of the same half angles, called from a function of its own in one kernel and inline in the other: the same bits (measured
+    on an MI355X, before and after the header: max |difference| = 0)."""
+    import torch
+    B, N, Ts = 257, 20, FC.TS
+    rng = np.random.default_rng(2057)
+    t_cur = rng.uniform(0.0, (N - 1) * Ts, B)
+    t_cur[:5] = [3 * Ts, 0.3 * Ts, (N - 2 + 0.6) * Ts, 0.0, 0.999 * Ts]
+    assert np.all(t_cur >= 0.0) and np.all(t_cur / Ts < N - 1)
+    pre_plan = rng.normal(size=(B, N, 17)); pre_plan[:, :, 3] = 7.3 + pre_plan[:, :, 3]
+    odom = rng.normal(size=(B, 9))
+    fleet = _fleet(B, N)
+    fsm = solver.FleetFSM(fleet)
+    fsm.state.fill_(FO.REPLAN_TRAJ); fsm.tick.exit_code.fill_(1); fleet.pre_plan.copy_(_dev(pre_plan, np.float64))
+    bufs = [torch.full((B, 3), SENTINEL, dtype=torch.float64, device=DEV) for _ in range(5)]
+    fsm.exec_begin(_dev(odom, np.float64), _dev(t_cur, np.float64), _dev([1.5], np.float64), *bufs, Ts=Ts, mass=FC.MASS, g=FC.G)
+    ones, zeros = _dev(np.ones(B), np.int32), _dev(np.zeros(B), np.int32)
+    status = _dev(np.full(B, solver.CMD_PUB_TRAJ), np.int32)
+    c = solver.command_batch_device(fleet.pre_plan, ones, _dev(t_cur.reshape(B, 1), np.float64), status, zeros, _dev(np.zeros((B, 3)), np.float64),
+                                    Ts=Ts, mass=FC.MASS, g=FC.G)
+    torch.cuda.synchronize()
+    assert np.all(c.kind.cpu().numpy() == solver.COMMAND_TRAJ) and np.all(fsm.search.cpu().numpy() == 1)   # the sampled branch, in both, for everyone
+    cmd = c.cmd.cpu().numpy()
+    sp, sv, sa = [x.cpu().numpy() for x in bufs[:3]]
+    print("start_acc against the published acceleration: max |difference| = %.3e" % float(np.max(np.abs(sa - cmd[:, 0, 13:16]))))
+    assert _same_bits(sp, cmd[:, 0, 0:3])
+    assert _same_bits(sv, cmd[:, 0, 7:10])
+    assert _same_bits(sa, cmd[:, 0, 13:16])
+
+
 def _world():
     """The empty 20 x 20 x 4 m world of tests/test_gpu_astar.py (origin (-10, -10, -1), 0.1 m voxels) with one pillar at the origin."""
     w = workloads.astar_world(0, "empty", allocate_num=12000)
