@@ -204,6 +204,12 @@ class DisturbanceArgs(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("zone", "event", "gust", "tick")]
 
 
+class SensorNoiseArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int)] + [(n, ctypes.c_double * 3) for n in ("sigma_p", "sigma_v", "sigma_a", "bias_a", "bias_c")] + \
+               [(n, ctypes.c_double) for n in ("depth_scale", "depth_sigma0", "depth_sigma2", "depth_p_drop", "scan_sigma0", "scan_sigma1", "scan_p_drop")] + \
+               [("seed", ctypes.c_longlong), ("id0", ctypes.c_longlong), ("bias", ctypes.c_void_p), ("tick", ctypes.c_void_p)]
+
+
 class OccMapBody(ctypes.Structure):
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -231,7 +237,7 @@ EXTFUNC = ctypes.CFUNCTYPE(None, c_double_p, c_double_p, c_double_p, c_double_p,
 C_TYPES = {cls: (ctype, header) for header, group in {
     "frp_nmpc.h": {Options: "frp_nmpc_options", Batch: "frp_nmpc_batch", Pack: "frp_nmpc_pack", Tube: "frp_nmpc_tube", Corridor: "frp_nmpc_corridor",
                    CorridorCut: "frp_nmpc_corridor_cut", Reference: "frp_nmpc_reference", Astar: "frp_nmpc_astar", OccMap: "frp_nmpc_occmap",
-                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
+                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", SensorNoiseArgs: "frp_nmpc_sensor_noise", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
     "frp_nmpc_occmap_fuse.h": {OccMapFuse: "frp_nmpc_occmap_fuse"}, "frp_nmpc_occmap_fuse_batch.h": {OccMapFuseBatch: "frp_nmpc_occmap_fuse_batch"},
     "frp_nmpc_occmap_fuse_points.h": {OccMapFusePoints: "frp_nmpc_occmap_fuse_points"}, "frp_nmpc_occmap_check.h": {OccMapBody: "frp_nmpc_occmap_body"},
     "frp_nmpc_occmap_render.h": {OccMapRender: "frp_nmpc_occmap_render"}, "frp_nmpc_occmap_render_scan.h": {OccMapRenderScan: "frp_nmpc_occmap_render_scan"},
@@ -266,6 +272,7 @@ FLIGHT_I_SELECTED, FLIGHT_I_ARRIVED, FLIGHT_I_WITH_BAD, FLIGHT_I_WITH_HITS, FLIG
 FLIGHT_I_ARRIVAL_SUM = 18  # (FLIGHT_I_RESULT ... + 5 are result_hist's columns)
 FLIGHT_F_TRACK_MAX2, FLIGHT_F_SPEED_MAX2, FLIGHT_F_PATH_MAX, FLIGHT_F_MIN_CLEAR, FLIGHT_F_TRACK_SUM2, FLIGHT_F_PATH_SUM = range(6)  # out_f
 DISTURBANCE_MAX_ZONES, DISTURBANCE_MAX_EVENTS, DISTURBANCE_ZONE_STRIDE, DISTURBANCE_EVENT_STRIDE = 16, 8, 12, 5
+SENSOR_NOISE_TAG_STATE, SENSOR_NOISE_TAG_DEPTH, SENSOR_NOISE_TAG_SCAN, SENSOR_NOISE_MAX_FRAMES = 0x53544154, 0x44455054, 0x5343414E, 65535
 
 # name here -> macro in include/*.h, for every integer above (one defined below this line is not checked): FRP_<name>, but for three
 MACROS = {n: n if n.startswith("FRP_") else "FRP_" + n for n, v in list(globals().items()) if n.isupper() and type(v) is int}
@@ -276,7 +283,7 @@ MACROS["ABI_VERSION"] = "FRP_NMPC_ABI_VERSION"
 _i, _d, _z, _v = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 _P = ctypes.POINTER
 _batch, _map, _cor, _cut, _fsm, _body = [_P(Batch), _P(Options)], _P(OccMap), _P(Corridor), _P(CorridorCut), _P(Fsm), _P(OccMapBody)
-_rec, _dist = _P(FlightRecordArgs), _P(DisturbanceArgs)
+_rec, _dist, _noise = _P(FlightRecordArgs), _P(DisturbanceArgs), _P(SensorNoiseArgs)
 _forces = (_i, [_P(ForcesParams), _P(ForcesOutput), _P(ForcesInfo), _v, _v])  # (FILE *, extfunc: an EXTFUNC or None, which only c_void_p takes)
 _BY_HEADER = {
     "frp_nmpc.h": {"frp_nmpc_abi_version": (_i, []),
@@ -323,6 +330,10 @@ _BY_HEADER = {
         "frp_nmpc_disturbance_eval": (_i, [_dist, _i, _v, _v, _i, _v, _v]),
         "frp_nmpc_disturbance_reset": (_i, [_dist, _v, _v]),
         "frp_nmpc_vehicle_step_field": (_i, [_P(VehicleArgs), _dist, _v, _v, _v]),
+        "frp_nmpc_sensor_noise_states": (_i, [_noise, _i, _v, _v, _v, _i, _v]),
+        "frp_nmpc_sensor_noise_reset": (_i, [_noise, _v, _v, _v, _v]),
+        "frp_nmpc_sensor_noise_depth": (_i, [_noise, _i, _i, _i, _v, _v, _v, _v, _v]),
+        "frp_nmpc_sensor_noise_scan": (_i, [_noise, _i, _i, _v, _v, _v, _v, _v, _v, _v]),
         "frp_nmpc_flight_record_samples": (_i, [_rec, _i, _v, _i, _v, _v, _v, _v, _v]),
         "frp_nmpc_flight_record_period": (_i, [_rec, _v, _v, _v, _v, _v, _v]),
         "frp_nmpc_flight_record_reset": (_i, [_rec, _v, _v, _v]),

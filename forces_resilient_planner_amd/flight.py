@@ -1,15 +1,15 @@
 """A fleet in flight, on the device: the state machine that drives the planners (FleetFSM), the vehicle that flies their commands
-(Vehicle), the force that acts on it (Disturbance), the estimator that tells them what it felt (ForceEstimator) and the record of what
-the fleet did (FlightRecord) (frp_nmpc_fsm_*, _vehicle_*, _disturbance_*, _estimator_*, _flight_*)."""
+(Vehicle), the force that acts on it (Disturbance), the errors of what it measures (SensorNoise), the estimator that tells them what it felt (ForceEstimator) and the record of what
+the fleet did (FlightRecord) (frp_nmpc_fsm_*, _vehicle_*, _disturbance_*, _estimator_*, _flight_*, _sensor_noise_*)."""
 import collections
 import ctypes
 
 from . import layout as L
 from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, ODOM_BODY, ODOM_WORLD,
-                   TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
+                   SENSOR_NOISE_MAX_FRAMES, SensorNoiseArgs, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
                    checked_ptr, lib, optional_ptr, stream_ptr, tensor_ptr)
 from .fleet import TickState
-from .occmap import SafetyCheck
+from .occmap import OCCMAP_FUSE_DEFAULTS, SafetyCheck
 from .planning import COMMAND_DEFAULTS
 
 FSM_EXT_NOISE_BOUND = 0.5  # nmpc/ext_noise_bound (nmpc_manage.cpp:13)
@@ -23,6 +23,12 @@ VEHICLE_DEFAULTS = dict(kp=(6.0, 6.0, 8.0), kv=(4.0, 4.0, 5.0), ka=(10.0, 10.0, 
 # planner's 50 ms periods, alpha = 1 - exp(-0.01 / 0.1) = 0.095 per 100 Hz sample, a step of 1 m/s^2 passes ext_noise_bound = 0.5 after
 # 7 samples --, and an estimate that counts as fresh once 10 residuals (two periods) went into it
 ESTIMATOR_DEFAULTS = dict(tau=0.1, min_samples=10)
+
+# CHOSEN, not derived (the reference flies RotorS, whose plugins add the noise): no noise at all -- every sigma and p_drop is the caller's to
+# set; the depth image's units per metre are the fusion's and the renderer's
+SENSOR_NOISE_DEFAULTS = dict(sigma_p=0.0, sigma_v=0.0, sigma_a=0.0, sigma_bias=0.0, tau_bias=1.0,
+                             depth=dict(sigma0=0.0, sigma2=0.0, p_drop=0.0, depth_scale=OCCMAP_FUSE_DEFAULTS["depth_scale"]),
+                             scan=dict(sigma0=0.0, sigma1=0.0, p_drop=0.0))
 
 
 class Vehicle:
@@ -59,6 +65,7 @@ class Vehicle:
         self.sat = t.zeros((self.B, self.S), dtype=t.int32, device=dev) if trace else None
         self.estimator = None   # a ForceEstimator attaches itself here: step() and reset() then feed and reset it
         self.disturbance = None  # a Disturbance attaches itself here: step() then takes every sample's force from it, reset() resets it
+        self.noise = None        # a SensorNoise attaches itself here: step() then measures the trace, message() publishes its y, reset() resets it
 
     def reset(self, x0, mask=None, stream=None):
         """frp_nmpc_vehicle_reset: where mask [B] int32 != 0 (None: everywhere) x <- x0 [B,9] and hold <- its position and yaw: the
@@ -71,6 +78,8 @@ class Vehicle:
             self.estimator.reset(mask, stream)
         if self.disturbance is not None:
             self.disturbance.reset(mask, stream)
+        if self.noise is not None:
+            self.noise.reset(mask, stream)
 
     def step(self, commands, stream=None):
         """frp_nmpc_vehicle_step: the S samples of a Commands object (cmd [B,S,16], kind [B,S]) flown in order under f_true; x and hold
@@ -79,7 +88,10 @@ class Vehicle:
         sample into the estimator's `thrust`, the trace into this object's own trace or else the estimator's `meas` --, then its update().
         With a Disturbance attached (self.disturbance): frp_nmpc_vehicle_step_field instead of either -- f_true is then the constant part
         of the force, every sample flies under the model's force at the plant's own position (written to the disturbance's `force`), and
-        the estimator, where there is one, is fed as above."""
+        the estimator, where there is one, is fed as above.
+        With a SensorNoise attached (self.noise): the same flight -- the trace into this object's own trace, the estimator's `meas` or else
+        the noise's `trace` --, then frp_nmpc_sensor_noise_states on the trace, and the estimator, where there is one, hears the noise's
+        `meas` instead of the trace."""
         t = self.torch
         S = int(commands.cmd.shape[1])
         if self.trace is not None and S != self.S:
@@ -87,7 +99,10 @@ class Vehicle:
         est = self.estimator
         if est is not None and S != est.S:
             raise ValueError(f"the attached ForceEstimator takes S = {est.S} samples per call, the commands hold {S}")
-        trace = self.trace if self.trace is not None else est.meas if est is not None else None
+        noise = self.noise
+        if noise is not None and S != noise.S:
+            raise ValueError(f"the attached SensorNoise measures S = {noise.S} samples per call, the commands hold {S}")
+        trace = self.trace if self.trace is not None else est.meas if est is not None else noise.trace if noise is not None else None
         v = VehicleArgs(self.B, S, self.n_sub, self.mass, self.g, self.dt_cmd, (ctypes.c_double * 3)(*self.kp), (ctypes.c_double * 3)(*self.kv),
                         (ctypes.c_double * 3)(*self.ka), self.x.data_ptr(), self.f_true.data_ptr(),
                         checked_ptr(self.x, commands.cmd, t.float64, (self.B, S, COMMAND_STRIDE)), checked_ptr(self.x, commands.kind, t.int32, (self.B, S)),
@@ -103,12 +118,16 @@ class Vehicle:
             _check(lib().frp_nmpc_vehicle_step(ctypes.byref(v), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step")
         else:
             _check(lib().frp_nmpc_vehicle_step_observed(ctypes.byref(v), tensor_ptr(est.thrust), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_step_observed")
+        if noise is not None:
+            noise.states(trace, stream=stream)
         if est is not None:
-            est.update(meas=trace, stream=stream)
+            est.update(meas=trace if noise is None else noise.meas, stream=stream)
 
     def message(self, stream=None):
-        """frp_nmpc_vehicle_message: msg <- the odometry message of x for this object's odom_type."""
-        _check(lib().frp_nmpc_vehicle_message(self.B, self.odom_type, tensor_ptr(self.x), tensor_ptr(self.msg), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_message")
+        """frp_nmpc_vehicle_message: msg <- the odometry message of x for this object's odom_type; with a SensorNoise attached, of its y
+        (the last sample's measurement) instead."""
+        x = self.x if self.noise is None else self.noise.y
+        _check(lib().frp_nmpc_vehicle_message(self.B, self.odom_type, tensor_ptr(x), tensor_ptr(self.msg), stream_ptr(stream, self.x)), "frp_nmpc_vehicle_message")
 
     def odometry(self, fsm, msg=None, fresh=None, stream=None):
         """odometryCallback / odometryTransCallback (nmpc_manage.cpp:421-478) into state, state_prev and fsm.have_odom.  msg None (a
@@ -129,7 +148,7 @@ class ForceEstimator:
     planner's own model that turns the thrust and the states of the samples a vehicle flew into the `force` / `force_fresh` pair of
     FleetFSM.period -- what the planner is TOLD, where vehicle.f_true is what acts.  It has no reference counterpart (the reference
     subscribes to a wrench another node publishes), and its measurements are the TRUE plant states of the vehicle's trace: noise is the
-    caller's to add (update(meas=...) takes any [B,S,9] tensor).
+    caller's to add (update(meas=...) takes any [B,S,9] tensor), or an attached SensorNoise's, whose `meas` Vehicle.step then feeds it.
     Attaches itself as vehicle.estimator: Vehicle.step then launches frp_nmpc_vehicle_step_observed and update(), Vehicle.reset resets
     it under the same mask.  The loop closes through arguments period() already has:
         fsm.period(planner, occmap, None, clock, force=est.force, force_fresh=est.fresh, vehicle=veh)
@@ -260,6 +279,132 @@ class Disturbance:
         d = self.struct()
         _check(lib().frp_nmpc_disturbance_reset(ctypes.byref(d), optional_ptr(v.x, mask, t.int32, (self.B,)),
                                                 stream_ptr(stream, v.x)), "frp_nmpc_disturbance_reset")
+
+
+class SensorNoise:
+    """The errors of what a fleet measures, on the device (include/frp_nmpc.h section 16): seeded noise on the states an estimator and the
+    odometry hear, on depth images and on float64 point scans.  It has no reference counterpart (the reference flies RotorS, whose plugins
+    add the noise); tests/sensor_noise_oracle.py is the statement.  CHOSEN, not derived: white Gaussian noise per component plus one
+    first-order Gauss-Markov bias on the position; sigma(z) = sigma0 + sigma2 z^2 per depth pixel, sigma(r) = sigma0 + sigma1 r along a scan
+    point's ray; independent pixels and points; no rolling shutter, no latency, no quantisation beyond the image's uint16.
+    Attaches itself as vehicle.noise: Vehicle.step then measures the trace into `meas` and `y` and feeds an attached estimator `meas`,
+    Vehicle.message publishes `y`, Vehicle.reset resets it under the same mask.  depth() and scan() are plain calls, the caller's to put
+    between render_* and fuse_*: nothing hooks into OccupancyMap or FleetFSM.period.
+    sigma_p / sigma_v / sigma_a (m, m/s, rad) and sigma_bias / tau_bias (m, s): a number or three, per axis; a = exp(-dt / tau) and
+    c = sigma sqrt(1 - a a) are computed here, as Disturbance computes the gusts'.  depth: sigma0, sigma2, p_drop (and depth_scale, image
+    units per metre); scan: sigma0, sigma1, p_drop.  seed, id0: vehicle b draws the stream (seed, id0 + b), frame or scan f (seed, id0 + f),
+    each channel under its own tag: a Disturbance with the same (seed, id0) shares no draw.  F: frames or scans per call (None: B).
+    Owns, device tensors: meas [B,S,9], y [B,9], bias [B,3], tick [B] int64, depth_tick / scan_tick [F] int64 and, where the vehicle keeps
+    no trace, trace [B,S,9]."""
+
+    def __init__(self, vehicle, sigma_p=None, sigma_v=None, sigma_a=None, sigma_bias=None, tau_bias=None, depth=None, scan=None, seed=0, id0=0, F=None):
+        import math
+        import numpy as np
+        t = vehicle.torch
+        dev = vehicle.x.device
+        self.torch, self.vehicle, self.B, self.S, self.dt = t, vehicle, vehicle.B, vehicle.S, float(vehicle.dt_cmd)
+        self.F = self.B if F is None else int(F)
+        self.seed, self.id0 = int(seed), int(id0)
+        if not (-2 ** 63 <= self.seed < 2 ** 63 and -2 ** 63 <= self.id0 < 2 ** 63):
+            raise ValueError("SensorNoise: seed and id0 are 64-bit signed integers")
+        if self.B < 1 or self.S < 1 or not 1 <= self.F <= SENSOR_NOISE_MAX_FRAMES:
+            raise ValueError(f"SensorNoise: B >= 1, S >= 1, 1 <= F <= {SENSOR_NOISE_MAX_FRAMES}")
+        k = dict(SENSOR_NOISE_DEFAULTS)
+        k.update({n: v for n, v in (("sigma_p", sigma_p), ("sigma_v", sigma_v), ("sigma_a", sigma_a), ("sigma_bias", sigma_bias), ("tau_bias", tau_bias)) if v is not None})
+        three = lambda v: tuple(float(u) for u in (v if np.ndim(v) else (v, v, v)))
+        sig = {n: three(k[n]) for n in ("sigma_p", "sigma_v", "sigma_a", "sigma_bias")}
+        tau = three(k["tau_bias"])
+        if any(len(v) != 3 or not all(math.isfinite(u) and u >= 0.0 for u in v) for v in sig.values()):
+            raise ValueError("SensorNoise: sigma_p, sigma_v, sigma_a and sigma_bias are finite and >= 0, a number or three each")
+        if len(tau) != 3 or not all(math.isfinite(u) and u > 0.0 for u in tau):
+            raise ValueError("SensorNoise: tau_bias is finite and > 0, a number or three")
+        self.sigma_p, self.sigma_v, self.sigma_a = sig["sigma_p"], sig["sigma_v"], sig["sigma_a"]
+        self.bias_a = tuple(math.exp(-self.dt / u) for u in tau)
+        self.bias_c = tuple(s * math.sqrt(1.0 - a * a) for s, a in zip(sig["sigma_bias"], self.bias_a))
+        self.depth_args, self.scan_args = dict(k["depth"]), dict(k["scan"])
+        for mine, given, what in ((self.depth_args, depth, "depth"), (self.scan_args, scan, "scan")):
+            given = dict(given or {})
+            if set(given) - set(mine):
+                raise ValueError(f"SensorNoise: {what} takes {sorted(mine)}, not {sorted(set(given) - set(mine))}")
+            mine.update({n: float(v) for n, v in given.items()})
+            if not all(math.isfinite(mine[n]) and mine[n] >= 0.0 for n in mine) or not mine["p_drop"] <= 1.0:
+                raise ValueError(f"SensorNoise: {what}'s sigmas are finite and >= 0, its p_drop is in [0, 1]")
+        if not self.depth_args["depth_scale"] > 0.0:
+            raise ValueError("SensorNoise: depth_scale is finite and > 0")
+        f64, i64 = dict(dtype=t.float64, device=dev), dict(dtype=t.int64, device=dev)
+        self.meas, self.y = t.zeros((self.B, self.S, VEHICLE_STATE), **f64), vehicle.x.clone()
+        self.bias, self.tick = t.zeros((self.B, 3), **f64), t.zeros((self.B,), **i64)
+        self.depth_tick, self.scan_tick = t.zeros((self.F,), **i64), t.zeros((self.F,), **i64)
+        self.trace = t.zeros((self.B, self.S, VEHICLE_STATE), **f64) if vehicle.trace is None else None
+        vehicle.noise = self
+
+    def struct(self):
+        d, s = self.depth_args, self.scan_args
+        v3 = lambda v: (ctypes.c_double * 3)(*v)
+        return SensorNoiseArgs(self.B, v3(self.sigma_p), v3(self.sigma_v), v3(self.sigma_a), v3(self.bias_a), v3(self.bias_c), d["depth_scale"], d["sigma0"],
+                               d["sigma2"], d["p_drop"], s["sigma0"], s["sigma1"], s["p_drop"], self.seed, self.id0, self.bias.data_ptr(), self.tick.data_ptr())
+
+    def states(self, x_true, advance=True, out=None, y=None, stream=None):
+        """frp_nmpc_sensor_noise_states: out [B,S,9] (None: this object's meas; x_true itself: in place) <- the measurements of x_true
+        [B,S,9] (any S >= 1) at samples tick ... tick + S - 1, y [B,9] (None: this object's y) <- the last one.  advance: bias and tick
+        move on by S; otherwise a pure query.  Returns out."""
+        t, v = self.torch, self.vehicle
+        assert t.is_tensor(x_true) and x_true.dim() == 3, "x_true is a [B, S, 9] tensor"
+        S = int(x_true.shape[1])
+        if S < 1:
+            raise ValueError("SensorNoise.states: S >= 1")
+        if out is None:
+            out = self.meas if S == self.S else t.empty((self.B, S, VEHICLE_STATE), dtype=t.float64, device=v.x.device)
+        n = self.struct()
+        shape = (self.B, S, VEHICLE_STATE)
+        _check(lib().frp_nmpc_sensor_noise_states(ctypes.byref(n), S, checked_ptr(v.x, x_true, t.float64, shape), checked_ptr(v.x, out, t.float64, shape),
+                                                  checked_ptr(v.x, self.y if y is None else y, t.float64, (self.B, VEHICLE_STATE)), int(bool(advance)),
+                                                  stream_ptr(stream, v.x)), "frp_nmpc_sensor_noise_states")
+        return out
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_sensor_noise_reset: where mask [B] int32 != 0 (None: everywhere) bias <- 0, tick <- 0 and y <- the vehicle's x.  The
+        frame counters are not the vehicles': depth_tick and scan_tick stay (zero_() them to restart a sensor)."""
+        t, v = self.torch, self.vehicle
+        n = self.struct()
+        _check(lib().frp_nmpc_sensor_noise_reset(ctypes.byref(n), optional_ptr(v.x, mask, t.int32, (self.B,)), tensor_ptr(v.x), tensor_ptr(self.y),
+                                                 stream_ptr(stream, v.x)), "frp_nmpc_sensor_noise_reset")
+
+    def depth(self, images, active=None, out=None, stream=None):
+        """frp_nmpc_sensor_noise_depth: out (None: a new tensor, an allocation; images itself: in place) <- the noisy images of images
+        [F,rows,cols] uint16 (render_depth's), frame f at depth_tick[f]; active [F] int32 or None: where it is 0 the frame is neither
+        written nor ticked.  depth_tick moves on by one for the active frames.  Returns out."""
+        t, v = self.torch, self.vehicle
+        if not (t.is_tensor(images) and images.dtype == t.uint16 and images.dim() == 3 and int(images.shape[0]) == self.F):
+            raise ValueError(f"SensorNoise.depth: images is a [F = {self.F}, rows, cols] uint16 tensor")
+        F, rows, cols = (int(u) for u in images.shape)
+        if rows < 1 or cols < 1:
+            raise ValueError("SensorNoise.depth: rows and cols >= 1")
+        out = t.zeros((F, rows, cols), dtype=t.int16, device=v.x.device).view(t.uint16) if out is None else out
+        n = self.struct()
+        _check(lib().frp_nmpc_sensor_noise_depth(ctypes.byref(n), F, rows, cols, checked_ptr(v.x, images, t.uint16, (F, rows, cols)),
+                                                 checked_ptr(v.x, out, t.uint16, (F, rows, cols)), optional_ptr(v.x, active, t.int32, (F,)),
+                                                 tensor_ptr(self.depth_tick), stream_ptr(stream, v.x)), "frp_nmpc_sensor_noise_depth")
+        return out
+
+    def scan(self, points, origin, count=None, active=None, out=None, stream=None):
+        """frp_nmpc_sensor_noise_scan: out (None: a new tensor; points itself: in place) <- the noisy points of points [F,P,3] float64
+        (render_scan's `points`; float32 scans are out of scope) seen from origin [F,3], scan f at scan_tick[f]; count [F] int32 or None:
+        storage at index >= count[f] is neither read nor written; active as in depth().  A lost point is three NaNs, which fuse_points
+        drops.  Returns out."""
+        t, v = self.torch, self.vehicle
+        if not (t.is_tensor(points) and points.dtype == t.float64 and points.dim() == 3 and int(points.shape[0]) == self.F and int(points.shape[2]) == 3):
+            raise ValueError(f"SensorNoise.scan: points is a [F = {self.F}, P, 3] float64 tensor")
+        F, P = int(points.shape[0]), int(points.shape[1])
+        if P < 1:
+            raise ValueError("SensorNoise.scan: P >= 1")
+        out = points.clone() if out is None else out
+        n = self.struct()
+        _check(lib().frp_nmpc_sensor_noise_scan(ctypes.byref(n), F, P, checked_ptr(v.x, points, t.float64, (F, P, 3)), checked_ptr(v.x, out, t.float64, (F, P, 3)),
+                                                checked_ptr(v.x, origin, t.float64, (F, 3)), optional_ptr(v.x, count, t.int32, (F,)),
+                                                optional_ptr(v.x, active, t.int32, (F,)), tensor_ptr(self.scan_tick), stream_ptr(stream, v.x)),
+               "frp_nmpc_sensor_noise_scan")
+        return out
 
 
 FlightSummary = collections.namedtuple("FlightSummary", "ints floats hist")

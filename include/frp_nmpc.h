@@ -737,6 +737,91 @@ struct frp_nmpc_vehicle;
 int frp_nmpc_vehicle_step_field(const struct frp_nmpc_vehicle *v, const frp_nmpc_disturbance *d, double *thrust, double *force,
                                 void *stream);
 
+/* ---- (16) sensor noise: seeded errors of the odometry, of depth images and of point scans, on the device ---- */
+/* (Declared here, ahead of section (14), for section (15)'s reason.  In this header and not in one of its own: the signature table's
+ * test names the headers of include/ one by one.)
+ * What the fleet MEASURES where sections (12), (13) and the map's sensors hand it the truth: the states an estimator and the odometry
+ * callbacks hear, the depth images frp_nmpc_occmap_render_depth renders and the float64 points frp_nmpc_occmap_render_scan_batch renders.
+ * NO REFERENCE COUNTERPART (the reference flies RotorS, whose plugins add the noise): tests/sensor_noise_oracle.py is the executable
+ * statement (csrc/frp_sensor_noise.hip is built without contraction).  Same ABI version: no existing struct changed.  CHOSEN, not
+ * derived: white Gaussian noise per component plus ONE first-order Gauss-Markov bias (on the position); sigma(z) = sigma0 + sigma2 z^2 for
+ * a depth pixel (the quadratic range error of a stereo or structured-light sensor) and sigma(r) = sigma0 + sigma1 r along the ray for a
+ * scan point; every pixel and point independent of its neighbours; no rolling shutter, no latency, no quantisation beyond the image's
+ * uint16.  float32 scans (points_f32 of the scan renderer) are OUT OF SCOPE: frp_nmpc_sensor_noise_scan takes float64 points alone.
+ *
+ * Draws.  M, stream_key (h of section 15) and the normal n(h, j) = sqrt(-2 log u1) cos(6.283185307179586 u2) of r0 = M(h + 2 j),
+ * r1 = M(h + 2 j + 1) are section (15)'s, csrc/frp_disturbance.hpp's functions as they are; a uniform is u(h, j) = (double)(M(h + j) >> 11) /
+ * 2^53 in [0, 1).  A sample's key is separated from the gusts' and between the channels by a tag,
+ *     h_sample = M(stream_key(seed, id0 + i, k) + FRP_SENSOR_NOISE_TAG_x)        (64-bit, wrapping)
+ * so a disturbance and a sensor noise with the same (seed, id0) share no draw.  States: i = the vehicle b, k = tick[b] + s, h = h_sample,
+ * normals j = 0 ... 11.  Frames and scans: i = the frame or scan f, k = frame_tick[f], and per pixel or point h = M(h_sample + index) with
+ * index = row * cols + col or the point's index; the normal is n(h, 0), the uniform u(h, 2).  Any sharding of a fleet (id0 shifted), any
+ * split of a flight into calls and any replay of a captured call draws the same numbers: the counters are device memory, read and
+ * advanced by the calls.  A frame counter is advanced by a second small launch, after every thread of the first has read it.
+ * A TERM THAT IS ZERO IS NOT ADDED (x stays x to the bit, a -0.0 included): with every sigma and p_drop zero all three calls are the
+ * identity.  Each product and each sum below is rounded on its own, in the order written.
+ * Every call: every pointer is DEVICE memory, asynchronous on `stream`, nothing allocated, nothing read back, capturable into a hipGraph;
+ * 256 threads per workgroup.  FRP_ERR_ARG before any device call, FRP_ERR_NO_DEVICE without a device. */
+#define FRP_SENSOR_NOISE_TAG_STATE 0x53544154 /* "STAT" */
+#define FRP_SENSOR_NOISE_TAG_DEPTH 0x44455054 /* "DEPT" */
+#define FRP_SENSOR_NOISE_TAG_SCAN 0x5343414E  /* "SCAN" */
+#define FRP_SENSOR_NOISE_MAX_FRAMES 65535      /* frames or scans per call (a grid dimension) */
+
+typedef struct frp_nmpc_sensor_noise {
+    int B;                                     /* vehicles of the state channel (>= 1)                                              */
+    double sigma_p[3], sigma_v[3], sigma_a[3]; /* white noise of position (m), world velocity (m/s), roll pitch yaw (rad): finite, >= 0 */
+    double bias_a[3], bias_c[3];               /* the position bias' recursion, a = exp(-dt / tau), c = sigma_bias sqrt(1 - a a), computed
+                                                  by the caller: finite, a in [0, 1], c >= 0                                          */
+    double depth_scale;                        /* image units per metre (the renderer's depth_scale): finite and > 0                 */
+    double depth_sigma0, depth_sigma2;         /* sigma(z) = sigma0 + sigma2 z z in metres: finite, >= 0                             */
+    double depth_p_drop;                       /* the probability that a pixel with a return loses it: in [0, 1]                     */
+    double scan_sigma0, scan_sigma1;           /* sigma(r) = sigma0 + sigma1 r in metres: finite, >= 0                               */
+    double scan_p_drop;                        /* the probability that a point is lost: in [0, 1]                                    */
+    long long seed, id0;                       /* the stream: vehicle b, frame f or scan f draws as id0 + b or id0 + f (wrapping)    */
+    double *bias;                              /* [B][3] in and out: the position bias (states and reset alone)                      */
+    long long *tick;                           /* [B] in and out: the vehicles' sample counter (states and reset alone)              */
+} frp_nmpc_sensor_noise;
+
+/* States: x_meas[b][s] <- the measurement of x_true[b][s] ([B][S][9]: position, world velocity, roll pitch yaw), one thread per vehicle,
+ * the samples in order; x_meas == x_true (in place) is allowed.  For sample s, k = tick[b] + s, h = h_sample(TAG_STATE), i = 0, 1, 2:
+ *   position  if x[i] is finite:  bias[i] <- a[i] * bias[i] + c[i] * n(h, i);   meas = (x[i] + bias[i]) + sigma_p[i] * n(h, 3 + i)
+ *   velocity  meas = x[3 + i] + sigma_v[i] * n(h, 6 + i)
+ *   angles    meas = x[6 + i] + sigma_a[i] * n(h, 9 + i)
+ * A component that is not finite passes through to the bit and draws nothing into the bias.  y [B][9] (or NULL) <- the last sample's
+ * measurement.  advance != 0: tick[b] += S and the bias is stored; advance == 0: both stay.
+ * FRP_ERR_ARG: n, x_true, x_meas, n->bias or n->tick NULL; B < 1; S < 1; B * S beyond 2^31 - 1; whatever the struct's comments rule out. */
+int frp_nmpc_sensor_noise_states(const frp_nmpc_sensor_noise *n, int S, const double *x_true, double *x_meas, double *y, int advance,
+                                 void *stream);
+
+/* Where mask[b] != 0 (mask == NULL: everywhere): bias[b] <- 0, tick[b] <- 0 and, with y and x [B][9] both given, y[b] <- x[b].
+ * FRP_ERR_ARG: as above for n; exactly one of x and y NULL. */
+int frp_nmpc_sensor_noise_reset(const frp_nmpc_sensor_noise *n, const int *mask, const double *x, double *y, void *stream);
+
+/* Depth images: out[f] <- the noisy image of in[f] ([F][rows][cols] uint16; out == in allowed), one thread per pixel, consecutive pixels
+ * on consecutive lanes; frame f draws as sensor id0 + f at k = frame_tick[f] ([F] in and out).  active [F] or NULL: where it is 0 the
+ * frame is neither written nor ticked.  Per pixel pix:
+ *   pix == 0 (no return)            out = 0, nothing drawn
+ *   z = pix / depth_scale;  sigma = sigma0 + (sigma2 * z) * z
+ *   u(h, 2) < p_drop                out = 0
+ *   otherwise                       v = (double)pix + (depth_scale * sigma) * n(h, 0);  w = floor(v + 0.5);  out = 1 <= w <= 65535 ? w : 0
+ * Two launches: the images, then frame_tick[f] += 1 for the active frames.
+ * FRP_ERR_ARG: n, in, out or frame_tick NULL; F < 1 or beyond FRP_SENSOR_NOISE_MAX_FRAMES; rows or cols < 1; rows * cols beyond 2^31 - 1;
+ * whatever the struct's comments rule out (B included). */
+int frp_nmpc_sensor_noise_depth(const frp_nmpc_sensor_noise *n, int F, int rows, int cols, const unsigned short *in, unsigned short *out,
+                                const int *active, long long *frame_tick, void *stream);
+
+/* Point scans: out[s][p] <- the noisy point of in[s][p] ([S][P][3] float64; out == in allowed) seen from origin[s] ([S][3]), one thread per
+ * point; scan s draws as sensor id0 + s at k = frame_tick[s].  count [S] or NULL (P): points at index >= count[s] are neither read nor
+ * written.  active [S] or NULL: as for frames.  Per point p, in this order:
+ *   a coordinate of p not finite    stays, nothing drawn
+ *   d = p - o;  r = sqrt((d0 * d0 + d1 * d1) + d2 * d2);  r == 0 or r not finite: stays
+ *   u(h, 2) < p_drop                all three coordinates <- NaN (frp_nmpc_occmap_fuse_points_batch drops such a point)
+ *   e = (sigma0 + sigma1 * r) * n(h, 0);  e == 0: stays;  otherwise p'_i = o_i + d_i * (1 + e / r)
+ * Two launches, as above.
+ * FRP_ERR_ARG: n, in, out, origin or frame_tick NULL; S < 1 or beyond FRP_SENSOR_NOISE_MAX_FRAMES; P < 1; whatever the struct rules out. */
+int frp_nmpc_sensor_noise_scan(const frp_nmpc_sensor_noise *n, int S, int P, const double *in, double *out, const double *origin,
+                               const int *count, const int *active, long long *frame_tick, void *stream);
+
 /* ---- (14) the flight record: tracking error, effort, events and a fleet summary, kept on the device ---- */
 /* What a fleet flown by sections (9)-(13) did, accumulated per vehicle from the arrays those sections leave in device memory, and the
  * fleet's figures from the per-vehicle ones -- beside frp_nmpc_occmap_clearance_trace (frp_nmpc_occmap_distance.h), which keeps the
@@ -858,7 +943,7 @@ int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min
                             const double *edges, long long *out_i, double *out_f, long long *hist, void *workspace, size_t workspace_bytes,
                             void *stream);
 
-/* (Section (15), the disturbance, is declared ahead of section (14), above.) */
+/* (Sections (15), the disturbance, and (16), the sensor noise, are declared ahead of section (14), above.) */
 
 #ifdef __cplusplus
 }
