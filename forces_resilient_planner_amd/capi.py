@@ -210,6 +210,14 @@ class SensorNoiseArgs(ctypes.Structure):
                [("seed", ctypes.c_longlong), ("id0", ctypes.c_longlong), ("bias", ctypes.c_void_p), ("tick", ctypes.c_void_p)]
 
 
+class MissionArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("W", ctypes.c_int), ("R", ctypes.c_int), ("loop", ctypes.c_int)] + \
+               [(n, ctypes.c_double) for n in ("arrive_radius", "dwell", "leg_timeout")] + [("goal_box", ctypes.c_double * 4)] + \
+               [(n, ctypes.c_double) for n in ("z_goal", "min_dist", "max_dist", "inflate_ratio")] + [("seed", ctypes.c_longlong), ("id0", ctypes.c_longlong)] + \
+               [(n, ctypes.c_void_p) for n in ("route", "route_len", "phase", "leg", "tries", "t_mark", "issued", "reached", "dropped", "abandoned", "blocked",
+                                               "leg_time_sum", "leg_time_max", "goal", "fresh")]
+
+
 class OccMapBody(ctypes.Structure):
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -237,7 +245,7 @@ EXTFUNC = ctypes.CFUNCTYPE(None, c_double_p, c_double_p, c_double_p, c_double_p,
 C_TYPES = {cls: (ctype, header) for header, group in {
     "frp_nmpc.h": {Options: "frp_nmpc_options", Batch: "frp_nmpc_batch", Pack: "frp_nmpc_pack", Tube: "frp_nmpc_tube", Corridor: "frp_nmpc_corridor",
                    CorridorCut: "frp_nmpc_corridor_cut", Reference: "frp_nmpc_reference", Astar: "frp_nmpc_astar", OccMap: "frp_nmpc_occmap",
-                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", SensorNoiseArgs: "frp_nmpc_sensor_noise", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
+                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", SensorNoiseArgs: "frp_nmpc_sensor_noise", MissionArgs: "frp_nmpc_mission", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
     "frp_nmpc_occmap_fuse.h": {OccMapFuse: "frp_nmpc_occmap_fuse"}, "frp_nmpc_occmap_fuse_batch.h": {OccMapFuseBatch: "frp_nmpc_occmap_fuse_batch"},
     "frp_nmpc_occmap_fuse_points.h": {OccMapFusePoints: "frp_nmpc_occmap_fuse_points"}, "frp_nmpc_occmap_check.h": {OccMapBody: "frp_nmpc_occmap_body"},
     "frp_nmpc_occmap_render.h": {OccMapRender: "frp_nmpc_occmap_render"}, "frp_nmpc_occmap_render_scan.h": {OccMapRenderScan: "frp_nmpc_occmap_render_scan"},
@@ -273,6 +281,7 @@ FLIGHT_I_ARRIVAL_SUM = 18  # (FLIGHT_I_RESULT ... + 5 are result_hist's columns)
 FLIGHT_F_TRACK_MAX2, FLIGHT_F_SPEED_MAX2, FLIGHT_F_PATH_MAX, FLIGHT_F_MIN_CLEAR, FLIGHT_F_TRACK_SUM2, FLIGHT_F_PATH_SUM = range(6)  # out_f
 DISTURBANCE_MAX_ZONES, DISTURBANCE_MAX_EVENTS, DISTURBANCE_ZONE_STRIDE, DISTURBANCE_EVENT_STRIDE = 16, 8, 12, 5
 SENSOR_NOISE_TAG_STATE, SENSOR_NOISE_TAG_DEPTH, SENSOR_NOISE_TAG_SCAN, SENSOR_NOISE_MAX_FRAMES = 0x53544154, 0x44455054, 0x5343414E, 65535
+MISSION_IDLE, MISSION_FLYING, MISSION_DONE, MISSION_MAX_TRIES, MISSION_TAG = 0, 1, 2, 64, 0x4D495353
 
 # name here -> macro in include/*.h, for every integer above (one defined below this line is not checked): FRP_<name>, but for three
 MACROS = {n: n if n.startswith("FRP_") else "FRP_" + n for n, v in list(globals().items()) if n.isupper() and type(v) is int}
@@ -283,7 +292,7 @@ MACROS["ABI_VERSION"] = "FRP_NMPC_ABI_VERSION"
 _i, _d, _z, _v = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 _P = ctypes.POINTER
 _batch, _map, _cor, _cut, _fsm, _body = [_P(Batch), _P(Options)], _P(OccMap), _P(Corridor), _P(CorridorCut), _P(Fsm), _P(OccMapBody)
-_rec, _dist, _noise = _P(FlightRecordArgs), _P(DisturbanceArgs), _P(SensorNoiseArgs)
+_rec, _dist, _noise, _mission = _P(FlightRecordArgs), _P(DisturbanceArgs), _P(SensorNoiseArgs), _P(MissionArgs)
 _forces = (_i, [_P(ForcesParams), _P(ForcesOutput), _P(ForcesInfo), _v, _v])  # (FILE *, extfunc: an EXTFUNC or None, which only c_void_p takes)
 _BY_HEADER = {
     "frp_nmpc.h": {"frp_nmpc_abi_version": (_i, []),
@@ -334,6 +343,9 @@ _BY_HEADER = {
         "frp_nmpc_sensor_noise_reset": (_i, [_noise, _v, _v, _v, _v]),
         "frp_nmpc_sensor_noise_depth": (_i, [_noise, _i, _i, _i, _v, _v, _v, _v, _v]),
         "frp_nmpc_sensor_noise_scan": (_i, [_noise, _i, _i, _v, _v, _v, _v, _v, _v, _v]),
+        "frp_nmpc_mission_step": (_i, [_mission, _fsm, _v, _v, _map, _body, _v, _z, _v]),
+        "frp_nmpc_mission_clock": (_i, [_v, _d, _d, _d, _i, _v, _i, _v]),
+        "frp_nmpc_mission_reset": (_i, [_mission, _v, _v]),
         "frp_nmpc_flight_record_samples": (_i, [_rec, _i, _v, _i, _v, _v, _v, _v, _v]),
         "frp_nmpc_flight_record_period": (_i, [_rec, _v, _v, _v, _v, _v, _v]),
         "frp_nmpc_flight_record_reset": (_i, [_rec, _v, _v, _v]),

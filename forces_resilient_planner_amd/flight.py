@@ -1,15 +1,16 @@
 """A fleet in flight, on the device: the state machine that drives the planners (FleetFSM), the vehicle that flies their commands
 (Vehicle), the force that acts on it (Disturbance), the errors of what it measures (SensorNoise), the estimator that tells them what it felt (ForceEstimator) and the record of what
-the fleet did (FlightRecord) (frp_nmpc_fsm_*, _vehicle_*, _disturbance_*, _estimator_*, _flight_*, _sensor_noise_*)."""
+the fleet did (FlightRecord), and what it flies next and what time it is (Mission) (frp_nmpc_fsm_*, _vehicle_*, _disturbance_*, _estimator_*, _flight_*,
+_sensor_noise_*, _mission_*)."""
 import collections
 import ctypes
 
 from . import layout as L
-from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, ODOM_BODY, ODOM_WORLD,
+from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, MISSION_MAX_TRIES, MissionArgs, OccMapBody, ODOM_BODY, ODOM_WORLD,
                    SENSOR_NOISE_MAX_FRAMES, SensorNoiseArgs, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
                    checked_ptr, lib, optional_ptr, stream_ptr, tensor_ptr)
 from .fleet import TickState
-from .occmap import OCCMAP_FUSE_DEFAULTS, SafetyCheck
+from .occmap import OCCMAP_BODY, OCCMAP_FUSE_DEFAULTS, SAFETY_INFLATE_CHECK, SafetyCheck
 from .planning import COMMAND_DEFAULTS
 
 FSM_EXT_NOISE_BOUND = 0.5  # nmpc/ext_noise_bound (nmpc_manage.cpp:13)
@@ -29,6 +30,12 @@ ESTIMATOR_DEFAULTS = dict(tau=0.1, min_samples=10)
 SENSOR_NOISE_DEFAULTS = dict(sigma_p=0.0, sigma_v=0.0, sigma_a=0.0, sigma_bias=0.0, tau_bias=1.0,
                              depth=dict(sigma0=0.0, sigma2=0.0, p_drop=0.0, depth_scale=OCCMAP_FUSE_DEFAULTS["depth_scale"]),
                              scan=dict(sigma0=0.0, sigma1=0.0, p_drop=0.0))
+
+# CHOSEN, not derived (in the reference a person clicks the goals): a leg counts as reached within 0.3 m of the end point the state machine
+# holds -- twice the 0.15 m at which solveNMPC starts publishing the end point (nmpc_solver.cpp:466) --, the next goal follows at once, no leg
+# times out, a drawn goal lies at goalCallback's z (NM:489) anywhere in the box, is tested as the safety timer tests a goal (ratio 1.2) and
+# gets four candidates per period; the clock's period is the tick's 50 ms
+MISSION_DEFAULTS = dict(arrive_radius=0.3, dwell=0.0, leg_timeout=0.0, z_goal=1.2, min_dist=0.0, max_dist=1.0e6, R=4, inflate_ratio=SAFETY_INFLATE_CHECK, period=0.05)
 
 
 class Vehicle:
@@ -728,3 +735,113 @@ class FleetFSM:
         """The reference's timers for a period starting at t0 (host floats): exec steps at t0, t0 + 0.01, ..., the tick and the first
         command callback one exec period after the last step and after the tick."""
         return [t0 + FSM_EXEC_PERIOD * k for k in range(int(fsm_steps) + 2)]
+
+
+class Mission:
+    """What a fleet flies next, on the device (include/frp_nmpc.h section 17): per-vehicle mission state, the goal / fresh arrays that
+    FleetFSM.period takes, and the period's clock -- the two inputs of a closed-loop period the host otherwise writes before every replay.
+    It has no reference counterpart (in the reference a person clicks goals in rviz and ROS owns the time); tests/mission_oracle.py is the
+    statement.  CHOSEN, not derived: MISSION_DEFAULTS -- arrival is a radius around the end point the state machine holds, tested when it
+    lets go of the target; goals come from a route or uniformly from a box.
+    Nothing hooks into FleetFSM.period: the caller launches, in this order and inside the same graph if it wishes,
+        m.clock(t0, fsm_steps); m.step(veh.state, m.clock_out, occmap); fsm.period(..., m.clock_out, goal=m.goal, goal_fresh=m.fresh, vehicle=veh)
+    Route mode: route [B, W, 3] (or [W, 3]: every vehicle's) host rows and route_len [B] (None: W), loop.  Random mode: goal_box
+    (x lo, x hi, y lo, y hi), min_dist / max_dist from the vehicle, R candidates per call, seed / id0 (vehicle b draws the stream
+    (seed, id0 + b) under the mission's own tag); step(occmap=...) rejects a candidate where checkPosSurround(inflate_ratio) is not free.
+    Exactly one of route and goal_box.  arrive_radius, dwell, leg_timeout (0: never): both modes.
+    Owns, device tensors, [B] int32 unless noted: phase (MISSION_IDLE / FLYING / DONE), leg (-1 at first), tries, t_mark f64, issued,
+    reached, dropped, abandoned, blocked, leg_time_sum / leg_time_max f64, goal [B,3] f64, fresh, k [1] int64 (the clock's period counter),
+    clock_out [MAX_STEPS + 2] f64."""
+
+    INT_FIELDS = ("phase", "leg", "tries", "issued", "reached", "dropped", "abandoned", "blocked", "fresh")
+    F64_FIELDS = (("t_mark", 0), ("leg_time_sum", 0), ("leg_time_max", 0), ("goal", 3))
+
+    def __init__(self, fleet_fsm, route=None, route_len=None, loop=False, goal_box=None, z_goal=None, min_dist=None, max_dist=None, R=None,
+                 inflate_ratio=None, arrive_radius=None, dwell=None, leg_timeout=None, seed=0, id0=0, period=None):
+        import math
+        import numpy as np
+        t = fleet_fsm.torch
+        dev = fleet_fsm.state.device
+        self.torch, self.fsm, self.B = t, fleet_fsm, fleet_fsm.B
+        k = dict(MISSION_DEFAULTS)
+        k.update({n: v for n, v in (("z_goal", z_goal), ("min_dist", min_dist), ("max_dist", max_dist), ("R", R), ("inflate_ratio", inflate_ratio),
+                                    ("arrive_radius", arrive_radius), ("dwell", dwell), ("leg_timeout", leg_timeout), ("period", period)) if v is not None})
+        if (route is None) == (goal_box is None):
+            raise ValueError("Mission: exactly one of route (route mode) and goal_box (random mode)")
+        self.seed, self.id0, self.loop = int(seed), int(id0), bool(loop)
+        if not (-2 ** 63 <= self.seed < 2 ** 63 and -2 ** 63 <= self.id0 < 2 ** 63):
+            raise ValueError("Mission: seed and id0 are 64-bit signed integers")
+        self.arrive_radius, self.dwell, self.leg_timeout, self.period = (float(k[n]) for n in ("arrive_radius", "dwell", "leg_timeout", "period"))
+        self.z_goal, self.min_dist, self.max_dist, self.inflate_ratio = (float(k[n]) for n in ("z_goal", "min_dist", "max_dist", "inflate_ratio"))
+        if not all(math.isfinite(v) and v >= 0.0 for v in (self.arrive_radius, self.dwell, self.leg_timeout, self.period)):
+            raise ValueError("Mission: arrive_radius, dwell, leg_timeout and period are finite and >= 0")
+        self.route = self.route_len = None
+        self.W, self.R, self.goal_box = 0, 0, (0.0, 0.0, 0.0, 0.0)
+        if route is not None:
+            r = np.asarray(route, dtype=np.float64)
+            if r.ndim == 2:
+                r = np.broadcast_to(r[None], (self.B,) + r.shape)
+            if r.ndim != 3 or r.shape[0] != self.B or r.shape[1] < 1 or r.shape[2] != 3:
+                raise ValueError("Mission: route is [B, W >= 1, 3] or [W, 3]")
+            self.W = int(r.shape[1])
+            n = np.full((self.B,), self.W, dtype=np.int32) if route_len is None else np.ascontiguousarray(route_len, dtype=np.int32)
+            if n.shape != (self.B,):
+                raise ValueError("Mission: route_len is [B]")
+            self.route, self.route_len = t.from_numpy(np.ascontiguousarray(r)).to(dev), t.from_numpy(n).to(dev)
+        else:
+            self.goal_box, self.R = tuple(float(v) for v in goal_box), int(k["R"])
+            if len(self.goal_box) != 4 or not all(math.isfinite(v) for v in self.goal_box) or not (self.goal_box[0] < self.goal_box[1] and self.goal_box[2] < self.goal_box[3]):
+                raise ValueError("Mission: goal_box is (x lo, x hi, y lo, y hi), finite, lo < hi")
+            if not 1 <= self.R <= MISSION_MAX_TRIES:
+                raise ValueError(f"Mission: 1 <= R <= {MISSION_MAX_TRIES}")
+            if not (math.isfinite(self.z_goal) and math.isfinite(self.max_dist) and 0.0 <= self.min_dist <= self.max_dist):
+                raise ValueError("Mission: z_goal finite, 0 <= min_dist <= max_dist, both finite")
+        for n in self.INT_FIELDS:
+            setattr(self, n, t.zeros((self.B,), dtype=t.int32, device=dev))
+        for n, w in self.F64_FIELDS:
+            setattr(self, n, t.zeros((self.B, w) if w else (self.B,), dtype=t.float64, device=dev))
+        self.leg.fill_(-1)
+        self.k = t.zeros((1,), dtype=t.int64, device=dev)
+        self.clock_out = t.zeros((FleetFSM.MAX_STEPS + 2,), dtype=t.float64, device=dev)
+
+    def struct(self):
+        p = lambda n: getattr(self, n).data_ptr() if getattr(self, n) is not None else None
+        return MissionArgs(self.B, self.W, self.R, int(self.loop), self.arrive_radius, self.dwell, self.leg_timeout, (ctypes.c_double * 4)(*self.goal_box),
+                           self.z_goal, self.min_dist, self.max_dist, self.inflate_ratio, self.seed, self.id0, *[p(n) for n, _ in MissionArgs._fields_[14:]])
+
+    def arrays(self):
+        """Every state array and output on the host (a synchronising read-back: tests and logs)."""
+        names = self.INT_FIELDS + tuple(n for n, _ in self.F64_FIELDS) + ("k",)
+        return {n: getattr(self, n).cpu().numpy() for n in names}
+
+    def step(self, state, clock, occmap=None, stream=None):
+        """frp_nmpc_mission_step at now = clock[0]: state [B,9] f64 the odometry the period plans from (Vehicle.state), clock a [>= 1] f64
+        device tensor (clock() returns one).  occmap: an OccupancyMap whose bit plane rejects drawn goals (random mode alone), or None.
+        Writes goal and fresh; returns (goal, fresh)."""
+        t, f = self.torch, self.fsm
+        assert t.is_tensor(clock) and clock.dtype == t.float64 and clock.dim() == 1 and int(clock.shape[0]) >= 1 and clock.device == f.state.device
+        m, fs = self.struct(), f.struct()
+        if occmap is not None:
+            om, body = occmap._map(), OccMapBody(float(OCCMAP_BODY[0]), float(OCCMAP_BODY[1]))
+            args = (ctypes.byref(om), ctypes.byref(body), tensor_ptr(occmap.ws), occmap.ws_bytes)
+        else:
+            args = (None, None, None, 0)
+        _check(lib().frp_nmpc_mission_step(ctypes.byref(m), ctypes.byref(fs), checked_ptr(f.state, state, t.float64, (self.B, 9)), tensor_ptr(clock), *args,
+                                           stream_ptr(stream, f.state)), "frp_nmpc_mission_step")
+        return self.goal, self.fresh
+
+    def clock(self, t0, fsm_steps, advance=1, stream=None):
+        """frp_nmpc_mission_clock: clock_out[j] <- (t0 + k * period) + 0.01 * j for j < fsm_steps + 2 -- FleetFSM.clock_for(t0 + period * k,
+        fsm_steps) to the bit --, then k += advance.  Returns the [fsm_steps + 2] view of clock_out that FleetFSM.period takes."""
+        n = int(fsm_steps) + 2
+        assert 1 <= int(fsm_steps) <= FleetFSM.MAX_STEPS
+        _check(lib().frp_nmpc_mission_clock(tensor_ptr(self.k), float(t0), self.period, FSM_EXEC_PERIOD, n, tensor_ptr(self.clock_out), int(advance),
+                                            stream_ptr(stream, self.fsm.state)), "frp_nmpc_mission_clock")
+        return self.clock_out[:n]
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_mission_reset: where mask [B] int32 != 0 (None: everywhere) phase <- IDLE, leg <- -1, everything else <- 0.  The
+        clock's counter k is not a vehicle's: it stays (zero_() it to restart the clock)."""
+        t, m = self.torch, self.struct()
+        _check(lib().frp_nmpc_mission_reset(ctypes.byref(m), optional_ptr(self.fsm.state, mask, t.int32, (self.B,)), stream_ptr(stream, self.fsm.state)),
+               "frp_nmpc_mission_reset")

@@ -822,6 +822,95 @@ int frp_nmpc_sensor_noise_depth(const frp_nmpc_sensor_noise *n, int F, int rows,
 int frp_nmpc_sensor_noise_scan(const frp_nmpc_sensor_noise *n, int S, int P, const double *in, double *out, const double *origin,
                                const int *count, const int *active, long long *frame_tick, void *stream);
 
+/* ---- (17) the mission: routes, seeded goals, arrivals and the period's clock, on the device ---- */
+/* (Declared here, ahead of section (14), for section (15)'s reason, and in this header for section (16)'s.)
+ * What decides a fleet's NEXT goal and what time it is: the two inputs of a closed-loop period that the host still wrote before every
+ * replay.  One call per period turns what the period left behind (section 11's have_odom, have_target and end_pt, and the odometry the
+ * period plans from) into the goal [B][3] / fresh [B] that frp_nmpc_fsm_goal takes; one call writes the period's clock and advances its
+ * counter.  Nothing here hooks into the period: the caller launches both in front of it, inside the same graph if it wishes.
+ * NO REFERENCE COUNTERPART (in the reference a person clicks goals in rviz and ROS owns the time): tests/mission_oracle.py is the
+ * executable statement, and the device agrees with it to the bit -- there is no transcendental on this path, and csrc/frp_mission.hip is
+ * built without contraction.  Same ABI version: no existing struct changed.  CHOSEN, not derived: arrival is a radius around the end point
+ * the state machine holds, tested when the state machine lets go of the target; a leg that ends any other way is `dropped`; a leg may time
+ * out; goals come from a fixed route or uniformly from a box, at a distance in [min_dist, max_dist] from the vehicle, rejected where the
+ * inflated body does not fit the map; z_goal is the 1.2 that goalCallback stores (NM:489).
+ *
+ * The step, per vehicle b, with now = clock[0], p = state[b][0..2], in this order in ONE call (every comparison as written: a NaN fails it):
+ *   fresh[b] <- 0, due <- 0
+ *   phase == FLYING and have_target == 0   (solveNMPC's 0, a blocked goal, the fierce-force branch)
+ *       d = p - end_pt[b];  (dx * dx + dy * dy) + dz * dz <= arrive_radius * arrive_radius:  reached += 1, lt = now - t_mark,
+ *       leg_time_sum += lt, leg_time_max <- lt where leg_time_max < lt;  otherwise dropped += 1.  Both: phase <- IDLE, t_mark <- now
+ *   phase == FLYING, have_target != 0, leg_timeout > 0 and now - t_mark > leg_timeout
+ *       abandoned += 1, phase <- IDLE, t_mark <- now - dwell, due <- 1: the issue below is tried in this same call (the state machine
+ *       takes that goal as any goal message that arrives in flight)
+ *   phase == IDLE and (due, or now - t_mark >= dwell) and have_odom != 0:  the issue
+ *       route mode:  n = route_len[b] outside 1 ... W: phase <- DONE (a refusal per vehicle; nothing is read from route).  j = leg + 1;
+ *           loop: the point is route[b][j % n];  no loop: j == n: phase <- DONE, else the point is route[b][j].  No occupancy test (a
+ *           blocked waypoint is the state machine's goal search's business).
+ *       random mode: candidates c = tries, tries + 1, ..., tries + R - 1 of leg j = leg + 1:
+ *           h = M(stream_key(seed, id0 + b, j) + FRP_MISSION_TAG)       (M and stream_key: section 15's; 64-bit, wrapping)
+ *           x = lo_x + u(h, 2 c) * (hi_x - lo_x),  y = lo_y + u(h, 2 c + 1) * (hi_y - lo_y)      (u: section 16's uniform)
+ *           accepted: min_dist * min_dist <= dx * dx + dy * dy <= max_dist * max_dist with dx = x - p_x, dy = y - p_y, and, with a map,
+ *           checkPosSurround((x, y, z_goal), inflate_ratio) free on the map's bit plane (frp_nmpc_occmap_check.h, no local box).
+ *           The first accepted candidate is the point (x, y, z_goal).  None: blocked += 1, tries += R, the vehicle stays IDLE.
+ *       on a point: leg += 1, tries <- 0, issued += 1, phase <- FLYING, t_mark <- now, goal[b] <- the point, fresh[b] <- 1
+ * A draw depends on (seed, id0 + b, leg, c) alone: not on the sharding of a fleet, on R, on how a flight is split into calls, on replay.
+ * Every call: every pointer is DEVICE memory (but the map description), asynchronous on `stream`, nothing allocated, nothing read back,
+ * capturable into a hipGraph with the period.  FRP_ERR_ARG before any device call, FRP_ERR_NO_DEVICE without a device. */
+#define FRP_MISSION_IDLE 0
+#define FRP_MISSION_FLYING 1
+#define FRP_MISSION_DONE 2
+#define FRP_MISSION_MAX_TRIES 64
+#define FRP_MISSION_TAG 0x4D495353 /* "MISS": no channel of section (16) has it */
+
+typedef struct frp_nmpc_mission {
+    int B;                        /* vehicles (>= 1)                                                                                  */
+    int W;                        /* route mode: waypoint slots per vehicle (>= 1); random mode: 0                                    */
+    int R;                        /* random mode: candidates per call, 1 ... FRP_MISSION_MAX_TRIES; route mode: 0                     */
+    int loop;                     /* route mode: non-zero: after the last waypoint comes the first                                    */
+    double arrive_radius;         /* metres: finite, >= 0                                                                             */
+    double dwell;                 /* seconds between the end of a leg and the next goal: finite, >= 0                                 */
+    double leg_timeout;           /* seconds after which a leg is abandoned: finite, >= 0; 0: never                                   */
+    double goal_box[4];           /* random mode: x lo, x hi, y lo, y hi: finite, lo < hi                                             */
+    double z_goal;                /* random mode: the z of a goal (finite)                                                            */
+    double min_dist, max_dist;    /* random mode: finite, 0 <= min_dist <= max_dist                                                   */
+    double inflate_ratio;         /* random mode with a map: checkPosSurround's ratio                                                 */
+    long long seed, id0;          /* random mode: vehicle b draws as id0 + b (wrapping)                                               */
+    const double *route;          /* [B][W][3]; route mode iff not NULL                                                               */
+    const int *route_len;         /* [B]: waypoints of vehicle b, 1 ... W                                                             */
+    int *phase, *leg, *tries;     /* [B] in and out: FRP_MISSION_*, the last goal issued (-1 at first), candidates consumed           */
+    double *t_mark;               /* [B] in and out: the time of the last issue or of the last return to IDLE                         */
+    int *issued, *reached, *dropped, *abandoned, *blocked; /* [B] in and out: counters                                                */
+    double *leg_time_sum, *leg_time_max;                   /* [B] in and out: over reached legs                                       */
+    double *goal;                 /* [B][3] out: written where a goal is issued                                                       */
+    int *fresh;                   /* [B] out: always written                                                                          */
+} frp_nmpc_mission;
+
+/* The step above.  fsm: section 11's struct (B, have_odom, have_target and end_pt are read); state [B][9]: the odometry the period plans
+ * from; clock: the period's clock, clock[0] is read.  map / body / workspace / workspace_bytes: frp_nmpc_occmap_check_surround's, or all
+ * four NULL / 0 for no occupancy test.  One wavefront per vehicle, four per workgroup of 256.
+ * FRP_ERR_ARG: ms, fsm, state or clock NULL; any state array, goal or fresh of ms NULL; fsm->have_odom, have_target or end_pt NULL;
+ * B < 1 or fsm->B != B; neither mode or both (route != NULL against R != 0); route mode: W < 1 or route_len NULL; random mode: W != 0,
+ * route_len given, R outside 1 ... FRP_MISSION_MAX_TRIES, a bound of the box not finite or lo >= hi, z_goal not finite, min_dist or
+ * max_dist not finite or negative, min_dist > max_dist; arrive_radius, dwell or leg_timeout not finite or negative; a map in route mode;
+ * some but not all of map, body, workspace; what frp_nmpc_occmap_check_surround refuses of them and of inflate_ratio (an invalid map,
+ * half extents beyond 31). */
+/* (fsm and body are written with their struct tags, as above: frp_nmpc_fsm.h or frp_nmpc_occmap_check.h may be the file a program includes.) */
+struct frp_nmpc_fsm;
+struct frp_nmpc_occmap_body;
+int frp_nmpc_mission_step(const frp_nmpc_mission *ms, const struct frp_nmpc_fsm *fsm, const double *state, const double *clock,
+                          const frp_nmpc_occmap *map, const struct frp_nmpc_occmap_body *body, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
+/* The clock of period k[0]: clock[j] <- (t0 + (double)k[0] * period) + dt * (double)j for j < n, then k[0] += advance -- what the host's
+ * (t0 + period * k) + dt * j gives to the bit for any k, which a repeated += period does not.  k [1] and clock [n] are device memory;
+ * one thread.  FRP_ERR_ARG: k or clock NULL; n < 1 or n > 64; t0 not finite; period or dt not finite or negative; advance < 0. */
+int frp_nmpc_mission_clock(long long *k, double t0, double period, double dt, int n, double *clock, int advance, void *stream);
+
+/* Where mask[b] != 0 (mask == NULL: everywhere): phase <- IDLE, leg <- -1, every other state array and goal <- 0, fresh <- 0.
+ * FRP_ERR_ARG: ms NULL, B < 1, any state array, goal or fresh NULL. */
+int frp_nmpc_mission_reset(const frp_nmpc_mission *ms, const int *mask, void *stream);
+
 /* ---- (14) the flight record: tracking error, effort, events and a fleet summary, kept on the device ---- */
 /* What a fleet flown by sections (9)-(13) did, accumulated per vehicle from the arrays those sections leave in device memory, and the
  * fleet's figures from the per-vehicle ones -- beside frp_nmpc_occmap_clearance_trace (frp_nmpc_occmap_distance.h), which keeps the
@@ -943,7 +1032,7 @@ int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min
                             const double *edges, long long *out_i, double *out_f, long long *hist, void *workspace, size_t workspace_bytes,
                             void *stream);
 
-/* (Sections (15), the disturbance, and (16), the sensor noise, are declared ahead of section (14), above.) */
+/* (Sections (15), the disturbance, (16), the sensor noise, and (17), the mission, are declared ahead of section (14), above.) */
 
 #ifdef __cplusplus
 }
