@@ -218,6 +218,19 @@ class MissionArgs(ctypes.Structure):
                                                "leg_time_sum", "leg_time_max", "goal", "fresh")]
 
 
+class PeersArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("S", ctypes.c_int), ("origin", ctypes.c_double * 3), ("dims", ctypes.c_int * 3)] + \
+               [(n, ctypes.c_double) for n in ("cell", "R", "d_warn", "d_hit")] + \
+               [(n, ctypes.c_void_p) for n in ("start", "items", "key", "slot", "block_sums", "outside", "sep2_min", "nearest", "near_samples", "hit_samples",
+                                               "samples", "first_hit", "tick", "sum_ws")]
+
+
+class PeersViewArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int), ("K", ctypes.c_int), ("P", ctypes.c_int), ("r_body", ctypes.c_double), ("origin", ctypes.c_double * 3),
+                ("resolution", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("pre_plan", "have_traj", "stages", "local_box", "cloud", "cloud_count", "added", "overflow")]
+
+
 class OccMapBody(ctypes.Structure):
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -245,7 +258,7 @@ EXTFUNC = ctypes.CFUNCTYPE(None, c_double_p, c_double_p, c_double_p, c_double_p,
 C_TYPES = {cls: (ctype, header) for header, group in {
     "frp_nmpc.h": {Options: "frp_nmpc_options", Batch: "frp_nmpc_batch", Pack: "frp_nmpc_pack", Tube: "frp_nmpc_tube", Corridor: "frp_nmpc_corridor",
                    CorridorCut: "frp_nmpc_corridor_cut", Reference: "frp_nmpc_reference", Astar: "frp_nmpc_astar", OccMap: "frp_nmpc_occmap",
-                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", SensorNoiseArgs: "frp_nmpc_sensor_noise", MissionArgs: "frp_nmpc_mission", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
+                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", SensorNoiseArgs: "frp_nmpc_sensor_noise", MissionArgs: "frp_nmpc_mission", PeersArgs: "frp_nmpc_peers", PeersViewArgs: "frp_nmpc_peers_view", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
     "frp_nmpc_occmap_fuse.h": {OccMapFuse: "frp_nmpc_occmap_fuse"}, "frp_nmpc_occmap_fuse_batch.h": {OccMapFuseBatch: "frp_nmpc_occmap_fuse_batch"},
     "frp_nmpc_occmap_fuse_points.h": {OccMapFusePoints: "frp_nmpc_occmap_fuse_points"}, "frp_nmpc_occmap_check.h": {OccMapBody: "frp_nmpc_occmap_body"},
     "frp_nmpc_occmap_render.h": {OccMapRender: "frp_nmpc_occmap_render"}, "frp_nmpc_occmap_render_scan.h": {OccMapRenderScan: "frp_nmpc_occmap_render_scan"},
@@ -282,6 +295,8 @@ FLIGHT_F_TRACK_MAX2, FLIGHT_F_SPEED_MAX2, FLIGHT_F_PATH_MAX, FLIGHT_F_MIN_CLEAR,
 DISTURBANCE_MAX_ZONES, DISTURBANCE_MAX_EVENTS, DISTURBANCE_ZONE_STRIDE, DISTURBANCE_EVENT_STRIDE = 16, 8, 12, 5
 SENSOR_NOISE_TAG_STATE, SENSOR_NOISE_TAG_DEPTH, SENSOR_NOISE_TAG_SCAN, SENSOR_NOISE_MAX_FRAMES = 0x53544154, 0x44455054, 0x5343414E, 65535
 MISSION_IDLE, MISSION_FLYING, MISSION_DONE, MISSION_MAX_TRIES, MISSION_TAG = 0, 1, 2, 64, 0x4D495353
+PEERS_MAX_CELLS, PEERS_MAX_NEAR, PEERS_MAX_CAND, PEERS_MAX_STAGES, PEERS_SCAN_CHUNK, PEERS_SUM_INTS, PEERS_SUM_WORDS = 1 << 22, 64, 1024, 8, 2048, 5, 6
+PEERS_I_NEAREST, PEERS_I_WITH_HITS, PEERS_I_NEAR, PEERS_I_HIT, PEERS_I_SAMPLES = range(5)  # out_i of frp_nmpc_peers_summary
 
 # name here -> macro in include/*.h, for every integer above (one defined below this line is not checked): FRP_<name>, but for three
 MACROS = {n: n if n.startswith("FRP_") else "FRP_" + n for n, v in list(globals().items()) if n.isupper() and type(v) is int}
@@ -292,7 +307,7 @@ MACROS["ABI_VERSION"] = "FRP_NMPC_ABI_VERSION"
 _i, _d, _z, _v = ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
 _P = ctypes.POINTER
 _batch, _map, _cor, _cut, _fsm, _body = [_P(Batch), _P(Options)], _P(OccMap), _P(Corridor), _P(CorridorCut), _P(Fsm), _P(OccMapBody)
-_rec, _dist, _noise, _mission = _P(FlightRecordArgs), _P(DisturbanceArgs), _P(SensorNoiseArgs), _P(MissionArgs)
+_rec, _dist, _noise, _mission, _peers = _P(FlightRecordArgs), _P(DisturbanceArgs), _P(SensorNoiseArgs), _P(MissionArgs), _P(PeersArgs)
 _forces = (_i, [_P(ForcesParams), _P(ForcesOutput), _P(ForcesInfo), _v, _v])  # (FILE *, extfunc: an EXTFUNC or None, which only c_void_p takes)
 _BY_HEADER = {
     "frp_nmpc.h": {"frp_nmpc_abi_version": (_i, []),
@@ -339,6 +354,11 @@ _BY_HEADER = {
         "frp_nmpc_disturbance_eval": (_i, [_dist, _i, _v, _v, _i, _v, _v]),
         "frp_nmpc_disturbance_reset": (_i, [_dist, _v, _v]),
         "frp_nmpc_vehicle_step_field": (_i, [_P(VehicleArgs), _dist, _v, _v, _v]),
+        "frp_nmpc_peers_build": (_i, [_peers, _v, _i, _v, _v]),
+        "frp_nmpc_peers_separation": (_i, [_peers, _v, _i, _i, _v]),
+        "frp_nmpc_peers_reset": (_i, [_peers, _v, _v]),
+        "frp_nmpc_peers_summary": (_i, [_peers, _v, _v, _v, _v]),
+        "frp_nmpc_peers_cloud": (_i, [_peers, _P(PeersViewArgs), _v, _i, _v]),
         "frp_nmpc_sensor_noise_states": (_i, [_noise, _i, _v, _v, _v, _i, _v]),
         "frp_nmpc_sensor_noise_reset": (_i, [_noise, _v, _v, _v, _v]),
         "frp_nmpc_sensor_noise_depth": (_i, [_noise, _i, _i, _i, _v, _v, _v, _v, _v]),

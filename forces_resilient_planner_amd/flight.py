@@ -1,12 +1,12 @@
 """A fleet in flight, on the device: the state machine that drives the planners (FleetFSM), the vehicle that flies their commands
 (Vehicle), the force that acts on it (Disturbance), the errors of what it measures (SensorNoise), the estimator that tells them what it felt (ForceEstimator) and the record of what
-the fleet did (FlightRecord), and what it flies next and what time it is (Mission) (frp_nmpc_fsm_*, _vehicle_*, _disturbance_*, _estimator_*, _flight_*,
-_sensor_noise_*, _mission_*)."""
+the fleet did (FlightRecord), and what it flies next and what time it is (Mission), and who flies next to whom (FleetPeers) (frp_nmpc_fsm_*, _vehicle_*,
+_disturbance_*, _estimator_*, _flight_*, _sensor_noise_*, _mission_*, _peers_*)."""
 import collections
 import ctypes
 
 from . import layout as L
-from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, MISSION_MAX_TRIES, MissionArgs, OccMapBody, ODOM_BODY, ODOM_WORLD,
+from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, MISSION_MAX_TRIES, MissionArgs, OccMapBody, ODOM_BODY, ODOM_WORLD, PEERS_MAX_CELLS, PEERS_MAX_STAGES, PEERS_SCAN_CHUNK, PEERS_SUM_INTS, PEERS_SUM_WORDS, PeersArgs, PeersViewArgs,
                    SENSOR_NOISE_MAX_FRAMES, SensorNoiseArgs, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
                    checked_ptr, lib, optional_ptr, stream_ptr, tensor_ptr)
 from .fleet import TickState
@@ -845,3 +845,152 @@ class Mission:
         t, m = self.torch, self.struct()
         _check(lib().frp_nmpc_mission_reset(ctypes.byref(m), optional_ptr(self.fsm.state, mask, t.int32, (self.B,)), stream_ptr(stream, self.fsm.state)),
                "frp_nmpc_mission_reset")
+
+
+class FleetPeers:
+    """Who flies next to whom, on the device (include/frp_nmpc.h section 18): a neighbour grid of the fleet's positions -- for every vehicle,
+    who is within R of it --, the separation record that measures with it, and the peer cloud that lets planners see each other through the
+    per-planner cloud full_tick already takes.  It has no reference counterpart (the reference flies one vehicle); tests/peers_oracle.py is
+    the statement, brute force over all pairs.  CHOSEN, not derived: stage i of every peer's plan is the same instant; a body is seven
+    points (centre, centre +- r_body along the world axes); the A*, the safety checks and the rendered sensors do not see peers.
+    Nothing hooks into FleetFSM.period: the caller launches, inside the same graph if it wishes,
+        view = occmap.local_view(veh.state[:, :3], P, out=view); peers.cloud(fleet, veh.state, view, occmap)
+        fsm.period(..., cloud=view.cloud, cloud_count=view.cloud_count, vehicle=veh); peers.update()
+    vehicle_or_B: a Vehicle made with trace=True (update() then reads its trace) or the number of vehicles.  origin [3], dims [3], cell:
+    the grid's box; R <= cell the radius; d_hit <= d_warn <= R the record's radii; S the samples per update() at the most; r_body and
+    stages (0 ... 8 rows of a plan) the cloud's.
+    Owns, device tensors, [B] int32 unless noted: sep2_min f64 (R * R at first), nearest (-1), near_samples, hit_samples, samples, first_hit
+    int64 (-1), tick [1] int64, outside (of the last build), added / overflow / cloud_outside (of the last cloud()), out_i [5] int64 and
+    out_f [1] f64 (of the last summary()), and the two grids' buffers.  Nothing here synchronises; every call is capturable."""
+
+    INT_FIELDS = ("nearest", "near_samples", "hit_samples", "samples")
+
+    def __init__(self, vehicle_or_B, origin, dims, cell, R, d_warn, d_hit, S=5, r_body=0.0, stages=(), device=None):
+        import math
+        if isinstance(vehicle_or_B, Vehicle):
+            self.vehicle, self.B, t = vehicle_or_B, vehicle_or_B.B, vehicle_or_B.torch
+            dev = vehicle_or_B.x.device if device is None else device
+        else:
+            import torch as t
+            self.vehicle, self.B = None, int(vehicle_or_B)
+            dev = t.device("cuda:0" if device is None else device)
+        self.torch, self.device, self.S = t, dev, int(S)
+        self.origin, self.dims = tuple(float(v) for v in origin), tuple(int(v) for v in dims)
+        self.cell, self.R, self.d_warn, self.d_hit, self.r_body = float(cell), float(R), float(d_warn), float(d_hit), float(r_body)
+        self.stage_list = tuple(int(k) for k in stages)
+        if self.B < 1 or self.S < 1 or len(self.origin) != 3 or len(self.dims) != 3 or min(self.dims) < 1 or not all(math.isfinite(v) for v in self.origin):
+            raise ValueError("FleetPeers: B >= 1, S >= 1, origin [3] finite, dims [3] >= 1")
+        self.ncell = self.dims[0] * self.dims[1] * self.dims[2]
+        if self.S * self.ncell > PEERS_MAX_CELLS:
+            raise ValueError(f"FleetPeers: S * cells = {self.S * self.ncell} is beyond {PEERS_MAX_CELLS}")
+        if not (math.isfinite(self.cell) and math.isfinite(self.R) and 0.0 < self.R <= self.cell):
+            raise ValueError("FleetPeers: 0 < R <= cell, both finite")
+        if not (0.0 <= self.d_hit <= self.d_warn <= self.R):
+            raise ValueError("FleetPeers: 0 <= d_hit <= d_warn <= R")
+        if not (math.isfinite(self.r_body) and self.r_body >= 0.0) or len(self.stage_list) > PEERS_MAX_STAGES or any(k < 0 for k in self.stage_list):
+            raise ValueError(f"FleetPeers: r_body finite and >= 0, at most {PEERS_MAX_STAGES} stages, each >= 0")
+        i32 = lambda *shape: t.zeros(shape, dtype=t.int32, device=dev)
+        B = self.B
+
+        def grid(S):
+            n1 = S * self.ncell + 1
+            return dict(start=i32(n1), items=i32(max(B * S, 1)), key=i32(max(B * S, 1)), slot=i32(max(B * S, 1)),
+                        block_sums=i32((n1 + PEERS_SCAN_CHUNK - 1) // PEERS_SCAN_CHUNK), outside=i32(max(B, 1)))
+        self._grid, self._grid1 = grid(self.S), grid(1)
+        self.outside, self.cloud_outside = self._grid["outside"][:B], self._grid1["outside"][:B]
+        self.sep2_min = t.full((B,), self.R * self.R, dtype=t.float64, device=dev)
+        self.nearest, self.near_samples, self.hit_samples, self.samples = i32(B) - 1, i32(B), i32(B), i32(B)
+        self.first_hit = t.full((B,), -1, dtype=t.int64, device=dev)
+        self.tick = t.zeros((1,), dtype=t.int64, device=dev)
+        self.sum_ws = t.zeros((max(1, (B + 255) // 256), PEERS_SUM_WORDS), dtype=t.int64, device=dev)
+        self.out_i, self.out_f = t.zeros((PEERS_SUM_INTS,), dtype=t.int64, device=dev), t.zeros((1,), dtype=t.float64, device=dev)
+        self.added, self.overflow = i32(B), i32(B)
+        self.stages = t.tensor(self.stage_list, dtype=t.int32, device=dev) if self.stage_list else None
+        self._built = None  # (pos, S, stride) of the last build(): what separation() reads
+
+    def struct(self, S=None, grid=None):
+        """The frp_nmpc_peers of a grid of S samples (None: the constructor's) on the buffers `grid` (None: update()'s own)."""
+        g = self._grid if grid is None else grid
+        p = lambda a: a.data_ptr()
+        return PeersArgs(self.B, self.S if S is None else int(S), (ctypes.c_double * 3)(*self.origin), (ctypes.c_int * 3)(*self.dims), self.cell, self.R,
+                         self.d_warn, self.d_hit, p(g["start"]), p(g["items"]), p(g["key"]), p(g["slot"]), p(g["block_sums"]), p(g["outside"]),
+                         p(self.sep2_min), p(self.nearest), p(self.near_samples), p(self.hit_samples), p(self.samples), p(self.first_hit), p(self.tick),
+                         p(self.sum_ws))
+
+    def arrays(self):
+        """Every record array, the counter and the last build's outside on the host (a synchronising read-back: tests and logs)."""
+        names = ("sep2_min",) + self.INT_FIELDS + ("first_hit", "tick", "outside")
+        return {n: getattr(self, n).cpu().numpy() for n in names}
+
+    def _samples(self, pos):
+        t = self.torch
+        assert t.is_tensor(pos) and pos.dtype == t.float64 and pos.is_contiguous() and pos.device == self.sep2_min.device and pos.dim() in (2, 3), "pos is [B,S,stride] or [B,stride] f64"
+        S = int(pos.shape[1]) if pos.dim() == 3 else 1
+        assert int(pos.shape[0]) == self.B and int(pos.shape[-1]) >= 3, (tuple(pos.shape), self.B)
+        return S, int(pos.shape[-1])
+
+    def build(self, pos, active=None, stream=None):
+        """frp_nmpc_peers_build: the grid of pos [B,S,stride] (S <= the constructor's) or [B,stride] f64 -- a Vehicle's trace, its state, or
+        plain points --, active [B] uint8 or None for all.  Writes outside."""
+        t = self.torch
+        S, stride = self._samples(pos)
+        if S > self.S:
+            raise ValueError(f"FleetPeers was made for S <= {self.S} samples per call, pos holds {S}")
+        f = self.struct(S)
+        _check(lib().frp_nmpc_peers_build(ctypes.byref(f), tensor_ptr(pos), stride, optional_ptr(self.sep2_min, active, t.uint8, (self.B,)),
+                                          stream_ptr(stream, self.sep2_min)), "frp_nmpc_peers_build")
+        self._built = (pos, S, stride)
+
+    def separation(self, advance=1, stream=None):
+        """frp_nmpc_peers_separation on the grid and the positions of the last build(); tick += advance behind it."""
+        assert self._built is not None, "call build() first"
+        pos, S, stride = self._built
+        f = self.struct(S)
+        _check(lib().frp_nmpc_peers_separation(ctypes.byref(f), tensor_ptr(pos), stride, int(advance), stream_ptr(stream, self.sep2_min)),
+               "frp_nmpc_peers_separation")
+
+    def update(self, trace=None, active=None, advance=1, stream=None):
+        """build() plus separation() on a trace [B,S,stride] (None: the Vehicle's own, made with trace=True): the everyday call, behind a period."""
+        if trace is None:
+            assert self.vehicle is not None and self.vehicle.trace is not None, "FleetPeers.update() without a trace needs a Vehicle made with trace=True"
+            trace = self.vehicle.trace
+        self.build(trace, active, stream)
+        self.separation(advance, stream)
+
+    def cloud(self, fleet, state, view, occmap, stream=None):
+        """frp_nmpc_peers_cloud: a grid of its own (S = 1) of state [B,9] f64, the odometry the planners know, then every planner's peers
+        within R -- their positions and, where they have a plan, the constructor's stages of fleet.pre_plan -- appended to view.cloud /
+        view.cloud_count (a LocalView of occmap.local_view) inside the planner's local box.  Writes added, overflow and cloud_outside;
+        returns view."""
+        t = self.torch
+        S, stride = self._samples(state)
+        assert S == 1 and state.dim() == 2
+        assert getattr(fleet, "pre_plan", None) is not None, "the fleet has no pre_plan yet: snapshot_commands() (or a TickState) makes it"
+        B, N, P = self.B, int(fleet.N), int(view.cloud.shape[1])
+        if any(k >= N for k in self.stage_list):
+            raise ValueError(f"FleetPeers: a stage beyond the plan's {N} rows")
+        f = self.struct(1, self._grid1)
+        like = self.sep2_min
+        v = PeersViewArgs(N, len(self.stage_list), P, self.r_body, (ctypes.c_double * 3)(*[float(o) for o in occmap.origin]), float(occmap.resolution),
+                          checked_ptr(like, fleet.pre_plan, t.float64, (B, N, L.NZ)), checked_ptr(like, fleet.have_traj, t.int32, (B,)),
+                          tensor_ptr(self.stages), checked_ptr(like, view.local_box, t.int32, (B, 6)),
+                          checked_ptr(like, view.cloud, t.float64, (B, P, 3)), checked_ptr(like, view.cloud_count, t.int32, (B,)),
+                          self.added.data_ptr(), self.overflow.data_ptr())
+        s = stream_ptr(stream, like)
+        _check(lib().frp_nmpc_peers_build(ctypes.byref(f), tensor_ptr(state), stride, None, s), "frp_nmpc_peers_build")
+        _check(lib().frp_nmpc_peers_cloud(ctypes.byref(f), ctypes.byref(v), tensor_ptr(state), stride, s), "frp_nmpc_peers_cloud")
+        return view
+
+    def summary(self, mask=None, stream=None):
+        """frp_nmpc_peers_summary over the vehicles with mask [B] int32 != 0 (None: all): returns (out_i [5] int64: PEERS_I_*, out_f [1] f64:
+        the fleet's minimum of sep2_min), device tensors this object owns."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_peers_summary(ctypes.byref(f), optional_ptr(self.sep2_min, mask, t.int32, (self.B,)), tensor_ptr(self.out_i), tensor_ptr(self.out_f),
+                                            stream_ptr(stream, self.sep2_min)), "frp_nmpc_peers_summary")
+        return self.out_i, self.out_f
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_peers_reset: where mask [B] int32 != 0 (None: everywhere) the record as the constructor left it.  tick stays."""
+        t, f = self.torch, self.struct()
+        _check(lib().frp_nmpc_peers_reset(ctypes.byref(f), optional_ptr(self.sep2_min, mask, t.int32, (self.B,)), stream_ptr(stream, self.sep2_min)),
+               "frp_nmpc_peers_reset")

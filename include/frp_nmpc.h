@@ -737,6 +737,130 @@ struct frp_nmpc_vehicle;
 int frp_nmpc_vehicle_step_field(const struct frp_nmpc_vehicle *v, const frp_nmpc_disturbance *d, double *thrust, double *force,
                                 void *stream);
 
+/* ---- (18) fleet peers: who is within R of whom, a separation record and peers as obstacles, on the device ---- */
+/* (Declared here, ahead of section (14), for section (15)'s reason, and in this header for section (16)'s; ahead of sections (16) and
+ * (17) because the mission's three calls stay the exports directly in front of the flight record's.)
+ * The vehicles of a fleet share one airspace, and no other section knows that a second vehicle exists.  This one builds, from positions a
+ * period leaves in device memory, a neighbour grid -- for every vehicle, who is within a radius R of it -- and has two consumers: a
+ * separation record, which measures, and a peer cloud, which appends a planner's neighbours to the per-planner cloud [B][P][3] /
+ * cloud_count [B] that frp_nmpc_corridor_batch already reads.  Nothing here hooks into a period: the caller launches the calls before or
+ * after it, inside the same graph if it wishes.
+ * NO REFERENCE COUNTERPART (the reference flies one vehicle): tests/peers_oracle.py is the executable statement -- brute force over all
+ * pairs, no grid -- and the device agrees with it to the bit: there is no transcendental on this path, and csrc/frp_peers.hip is built
+ * without contraction.  Same ABI version: no existing struct changed.  CHOSEN, not derived: stage i of every peer's plan is taken to be the
+ * same instant (the fleet ticks together); a body is seven points, its centre and centre +- r_body along the world axes; the A*, the safety
+ * checks and the rendered sensors do not see peers.
+ *
+ * The grid: a box of dims[0] x dims[1] x dims[2] cells of edge `cell` at `origin`, stacked S times (one layer per sample of a call).  The
+ * cell of a coordinate is (int)floor((p - origin) / cell).  Sample (b, s) is ENTERED unless a coordinate is not finite, a cell index is
+ * outside dims, or active[b] == 0; outside[b] <- 1 where any of the S samples of b was not entered, 0 otherwise.  A sample that is not
+ * entered has no peers and is nobody's peer.  Every result below is defined on the entered samples alone and does not depend on the order
+ * of the items inside a cell, on cell, on dims or on origin (as long as the samples are inside), because R <= cell is required: whoever is
+ * within R lies in the 27 surrounding cells.  ONE EXCEPTION, with R == cell alone: the two quotients (p - origin) / cell of a pair round on
+ * their own, so a pair whose separation along an axis equals `cell` to the last bit (d2 <= R * R only if the other two differences are
+ * zero) can land two cells apart and is then not found.  Positions on the grid's own lattice (origin + k * cell) are found; a caller for
+ * whom such a pair must count takes cell a hair above R (cell = R * (1 + 2^-40) costs nothing).
+ * d2 between two samples is (dx * dx + dy * dy) + dz * dz in float64, each product and sum rounded on its own.
+ *
+ * The separation record, per entered sample (b, s), s ascending within a call, over the entered samples (q, s) of the same s, q != b, with
+ * d2 <= R * R (every comparison as written: a NaN fails it):
+ *   samples[b] += 1
+ *   (m, q*) = the smallest key (d2, q) of them; where there is one and m < sep2_min[b] (strictly): sep2_min[b] <- m, nearest[b] <- q*
+ *   near_samples[b] += 1 where some d2 <= d_warn * d_warn;  hit_samples[b] += 1 where some d2 <= d_hit * d_hit, and with it
+ *   first_hit[b] <- tick[0] where first_hit[b] < 0
+ * and, after every thread has read it, tick[0] += advance in a launch of its own.  sep2_min starts at R * R (a truncated separation, as
+ * frp_nmpc_occmap_distance.h's field is a truncated distance), nearest and first_hit at -1.
+ *
+ * The peer cloud, per planner b of a grid built with S = 1 from the odometry the planners know, cloud_count[b] >= 0 (a negative count --
+ * the map's cloud overflowed -- leaves the planner as it is: added[b] <- 0, overflow[b] <- 0):
+ *   peers: the entered q != b with d2 <= R * R between the CURRENT positions, ascending in the key (d2, q); the first FRP_PEERS_MAX_NEAR
+ *          are kept, overflow[b] <- 1 where there were more (0 otherwise)
+ *   centres of a kept peer, in this order: its current position; where have_traj[q] != 0, pre_plan[q][stages[k]][8..10] for k = 0 ... K - 1
+ *          (a stage outside 0 ... N - 1 gives no centre)
+ *   points of a centre c, in this order: c, c + r e_x, c - r e_x, c + r e_y, c - r e_y, c + r e_z, c - r e_z with r = r_body (one sum
+ *          each); r_body == 0: c alone
+ *   a point with a non-finite coordinate is dropped; a point outside planner b's local box is dropped: it stays iff
+ *          origin[k] + (double)local_box[b][k] * resolution <= q[k] < origin[k] + (double)local_box[b][3 + k] * resolution on every axis
+ *          (frp_nmpc_corridor_batch_cut's test: one product, one sum)
+ *   the n surviving points go to cloud[b][cloud_count[b] + j] in that order and cloud_count[b] += n -- or, where cloud_count[b] + n > P,
+ *          nothing is stored and cloud_count[b] <- -(cloud_count[b] + n): frp_nmpc_occmap_local_view's own overflow convention.
+ *          added[b] <- n either way.  Rows past the new count are not touched.
+ * Every call: every pointer is DEVICE memory, asynchronous on `stream`, nothing allocated, nothing read back, capturable into a hipGraph
+ * with the period.  FRP_ERR_ARG before any device call, FRP_ERR_NO_DEVICE without a device; B == 0 is FRP_OK without a launch. */
+#define FRP_PEERS_MAX_CELLS (1 << 22) /* S * dims[0] * dims[1] * dims[2] at the most                                                    */
+#define FRP_PEERS_MAX_NEAR 64         /* peers a planner's cloud takes                                                                  */
+#define FRP_PEERS_MAX_CAND 1024       /* candidates within R a wavefront lists at a time; beyond, the list is reduced to its             */
+                                      /* FRP_PEERS_MAX_NEAR smallest keys and goes on: the result is the same, overflow is set anyway    */
+#define FRP_PEERS_MAX_STAGES 8        /* K at the most                                                                                  */
+#define FRP_PEERS_SCAN_CHUNK 2048     /* cell counters a workgroup scans: block_sums holds one int per chunk of the S * ncell + 1         */
+#define FRP_PEERS_SUM_INTS 5          /* out_i of frp_nmpc_peers_summary                                                                */
+#define FRP_PEERS_SUM_WORDS 6         /* eight-byte words per 256 vehicles in sum_ws                                                    */
+#define FRP_PEERS_I_NEAREST 0         /* the lowest vehicle id that attains the fleet's minimum of sep2_min; -1: nobody selected         */
+#define FRP_PEERS_I_WITH_HITS 1       /* vehicles with hit_samples > 0                                                                  */
+#define FRP_PEERS_I_NEAR 2            /* the sums of near_samples, hit_samples and samples                                              */
+#define FRP_PEERS_I_HIT 3
+#define FRP_PEERS_I_SAMPLES 4
+
+typedef struct frp_nmpc_peers {
+    int B, S;                     /* vehicles (>= 0), samples per vehicle of this grid (>= 1)                                         */
+    double origin[3];             /* the box's low corner (finite)                                                                    */
+    int dims[3];                  /* cells per axis (>= 1); S * dims[0] * dims[1] * dims[2] <= FRP_PEERS_MAX_CELLS                    */
+    double cell, R;               /* metres, finite and > 0, R <= cell                                                                */
+    double d_warn, d_hit;         /* the record's radii: 0 <= d_hit <= d_warn <= R                                                    */
+    int *start;                   /* [S * ncell + 1] the grid: cell `key` holds items[start[key] ... start[key + 1] - 1]              */
+    int *items;                   /* [B * S] vehicle ids, cell by cell                                                                */
+    int *key, *slot;              /* [B][S] a sample's cell key s * ncell + (cz * dims[1] + cy) * dims[0] + cx (-1: not entered) and  */
+                                  /* its rank inside the cell                                                                         */
+    int *block_sums;              /* [ceil((S * ncell + 1) / FRP_PEERS_SCAN_CHUNK)] scratch of the scan                               */
+    int *outside;                 /* [B] out of a build                                                                               */
+    double *sep2_min;             /* [B] in and out: the record (the grid calls and the cloud read none of the fields from here on)   */
+    int *nearest, *near_samples, *hit_samples, *samples; /* [B] in and out                                                            */
+    long long *first_hit;         /* [B] in and out                                                                                   */
+    long long *tick;              /* [1] in and out: the counter first_hit takes its value from                                       */
+    long long *sum_ws;            /* [max(1, ceil(B / 256))][FRP_PEERS_SUM_WORDS] scratch of the summary                              */
+} frp_nmpc_peers;
+
+typedef struct frp_nmpc_peers_view {
+    int N, K, P;                  /* rows of a plan (>= 1), stages taken (0 ... FRP_PEERS_MAX_STAGES), rows of a planner's cloud      */
+    double r_body;                /* metres, finite and >= 0                                                                          */
+    double origin[3], resolution; /* the MAP's origin (finite) and resolution (finite, > 0): what local_box counts in                 */
+    const double *pre_plan;       /* [B][N][17], frp_nmpc_command_snapshot's                                                          */
+    const int *have_traj;         /* [B]                                                                                              */
+    const int *stages;            /* [K]; NULL iff K == 0                                                                             */
+    const int *local_box;         /* [B][6] min_id, max_id of frp_nmpc_occmap_local_view                                              */
+    double *cloud;                /* [B][P][3] in and out                                                                             */
+    int *cloud_count;             /* [B] in and out                                                                                   */
+    int *added, *overflow;        /* [B] out                                                                                          */
+} frp_nmpc_peers_view;
+
+/* The grid of the samples pos [B][S][stride] (the first three of `stride` doubles are the position: a vehicle's trace [B][S][9], its
+ * state [B][9] with S = 1, or plain points), active [B] bytes or NULL for all.  Five launches: clear, count (int32 atomic adds on the
+ * cells' counters; the value an add returns is the sample's rank), the chunks' sums, the exclusive scan, fill.
+ * FRP_ERR_ARG: p or pos NULL; B < 0; S < 1; stride < 3; B * S * stride beyond 2^31 - 1; cell or R not finite and positive; R > cell; an
+ * origin not finite; a dim < 1; S * ncell beyond FRP_PEERS_MAX_CELLS; start, items, key, slot, block_sums or outside NULL. */
+int frp_nmpc_peers_build(const frp_nmpc_peers *p, const double *pos, int stride, const unsigned char *active, void *stream);
+
+/* The record above on the grid the last build made of the same pos, then tick[0] += advance.  Two launches; one thread per vehicle.
+ * FRP_ERR_ARG: whatever the build refuses; a record array, tick or sum_ws NULL; d_hit <= d_warn <= R violated (a NaN violates it) or
+ * d_hit < 0; advance < 0. */
+int frp_nmpc_peers_separation(const frp_nmpc_peers *p, const double *pos, int stride, int advance, void *stream);
+
+/* Where mask[b] != 0 (mask == NULL: everywhere): sep2_min <- R * R, nearest <- -1, the three counters <- 0, first_hit <- -1.  tick is
+ * not a vehicle's: it stays.  FRP_ERR_ARG: p NULL, B < 0, R, d_warn or d_hit against their rules, a record array, tick or sum_ws NULL. */
+int frp_nmpc_peers_reset(const frp_nmpc_peers *p, const int *mask, void *stream);
+
+/* The fleet's figures over the vehicles with mask[b] != 0 (NULL: all): out_f [1] <- the minimum of sep2_min (+inf: nobody selected),
+ * out_i [FRP_PEERS_SUM_INTS] <- FRP_PEERS_I_*.  Two launches: one workgroup per 256 vehicles writes a row of sum_ws, then ONE workgroup
+ * takes the rows in their order.  Integers and a minimum over the key (sep2_min, id): every run gives the same bits.
+ * FRP_ERR_ARG: as the reset's; out_i or out_f NULL. */
+int frp_nmpc_peers_summary(const frp_nmpc_peers *p, const int *mask, long long *out_i, double *out_f, void *stream);
+
+/* The peer cloud above on a grid built with S = 1 from pos [B][stride] (the odometry: state [B][9]).  One launch, one wavefront per planner.
+ * FRP_ERR_ARG: whatever the build refuses; S != 1; v NULL; N < 1; K outside 0 ... FRP_PEERS_MAX_STAGES; P < 0; r_body not finite or
+ * negative; resolution not finite and positive; an origin of v not finite; pre_plan, have_traj, local_box, cloud_count, added or overflow
+ * NULL; stages NULL with K > 0; cloud NULL with P > 0; B * N * 17 beyond 2^31 - 1. */
+int frp_nmpc_peers_cloud(const frp_nmpc_peers *p, const frp_nmpc_peers_view *v, const double *pos, int stride, void *stream);
+
 /* ---- (16) sensor noise: seeded errors of the odometry, of depth images and of point scans, on the device ---- */
 /* (Declared here, ahead of section (14), for section (15)'s reason.  In this header and not in one of its own: the signature table's
  * test names the headers of include/ one by one.)
@@ -1032,7 +1156,8 @@ int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min
                             const double *edges, long long *out_i, double *out_f, long long *hist, void *workspace, size_t workspace_bytes,
                             void *stream);
 
-/* (Sections (15), the disturbance, (16), the sensor noise, and (17), the mission, are declared ahead of section (14), above.) */
+/* (Sections (15), the disturbance, (18), the fleet peers, (16), the sensor noise, and (17), the mission, are declared ahead of section
+ * (14), above.) */
 
 #ifdef __cplusplus
 }
