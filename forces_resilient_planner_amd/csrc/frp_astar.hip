@@ -32,8 +32,16 @@
 #include <stdint.h>
 #include "../../include/frp_nmpc.h"
 
+// FRP_ASTAR_PEERS (frp_astar_peers.hip defines it and includes this file): the same search on the map plus a planner's boxes
+// (frp_nmpc.h section 19), in a namespace of its own.  Without the macro this file is the text it was.
+#ifdef FRP_ASTAR_PEERS
+#define FRP_ASTAR_NS astar_peers
+#else
+#define FRP_ASTAR_NS astar
+#endif
+
 namespace frp {
-namespace astar {
+namespace FRP_ASTAR_NS {
 
 constexpr int MAX_CAND = 128;    // primitives per expansion (125 in the reference's configuration)
 constexpr int MAX_PATH = FRP_ASTAR_MAX_PATH;
@@ -63,6 +71,10 @@ struct Args {
     int fast, off[3];                 // ray cell -> voxel index is an integer offset (checked on the host)
     Node *nodes; HeapEnt *heap; HashEnt *hash; // per-planner areas of allocate_num / allocate_num / hcap entries
     int hcap;
+#ifdef FRP_ASTAR_PEERS
+    const int *boxes, *count; // [B][Q][6], [B]: frp_nmpc_peers_boxes's
+    int Q;
+#endif
 };
 
 // ------------------------------------------------------------------ deterministic elementary functions (fdlibm; see astar_oracle.c)
@@ -178,8 +190,65 @@ struct Ctx {
     // inside the range the integer cell -> voxel offset was verified for -- as first cell, extent (0 = empty) and window / bit origin
     int fx0, fy0, fz0, fwx, fwy, fwz;
     unsigned fxn, fyn, fzn;
+#ifdef FRP_ASTAR_PEERS
+    const int *bx; // the planner's nbx rows of min_id (3), max_id (3) in global memory: every index below is uniform over the
+    int nbx;       // workgroup, so the rows come through scalar loads and take neither LDS nor vector registers
+#endif
 };
 constexpr int CELL_SAFE = 4096;
+
+#ifdef FRP_ASTAR_PEERS
+// The overlay.  A row is read as it is and only compared or turned into a shift count that was clamped to 0 ... 63 first: a row that is
+// not a box of the map (hi < lo, indices outside it) marks nothing or is clipped, whatever it holds.
+// the z bits of column (i0, i1) that lie in one of the planner's boxes (packed maps: grid[2] <= 64)
+__device__ __forceinline__ unsigned long long box_column(const Ctx &c, int i0, int i1)
+{
+    unsigned long long m = 0ull;
+    for (int j = 0; j < c.nbx; j++) {
+        const int *r = c.bx + 6 * j;
+        const int z0 = r[2] < 0 ? 0 : r[2], z1 = r[5] > 63 ? 63 : r[5];
+        if (r[0] <= i0 && i0 <= r[3] && r[1] <= i1 && i1 <= r[4] && z0 <= z1) m |= (~0ull >> (63 - (z1 - z0))) << z0;
+    }
+    return m;
+}
+// is voxel (i0, i1, i2) in one of the planner's boxes (the byte-map route)
+__device__ __forceinline__ bool in_box(const Ctx &c, int i0, int i1, int i2)
+{
+    for (int j = 0; j < c.nbx; j++) {
+        const int *r = c.bx + 6 * j;
+        if (r[0] <= i0 && i0 <= r[3] && r[1] <= i1 && i1 <= r[4] && r[2] <= i2 && i2 <= r[5]) return true;
+    }
+    return false;
+}
+// The boxes' z masks OR-ed into the window words a lane has just staged (its own columns i = lane, lane + nw, ...: no other lane's, so no
+// barrier and no atomic).  The walk is over the ROWS first: a row whose x / y range misses the window -- uniform over the workgroup, a
+// scalar branch -- costs nothing per column; the others are tested against the four or five columns of the lane.
+__device__ __forceinline__ void stage_boxes(const Ctx &c, unsigned long long *win, int wx0, int wy0, int side, int lane, int nw)
+{
+    if (lane >= nw) return;
+    const int g0 = c.P->grid[0] - 1, g1 = c.P->grid[1] - 1;
+    for (int j = 0; j < c.nbx; j++) {
+        const int *r = c.bx + 6 * j;
+        // the row's columns inside the window and inside the map, as window coordinates (columns outside the map stay 0, as staged)
+        const int x0 = max(max(r[0], 0), wx0) - wx0, x1 = min(min(r[3], g0), wx0 + side - 1) - wx0;
+        const int y0 = max(max(r[1], 0), wy0) - wy0, y1 = min(min(r[4], g1), wy0 + side - 1) - wy0;
+        const int z0 = r[2] < 0 ? 0 : r[2], z1 = r[5] > 63 ? 63 : r[5];
+        if (x1 < x0 || y1 < y0 || z1 < z0) continue;
+        const unsigned long long m = (~0ull >> (63 - (z1 - z0))) << z0;
+        for (int i = lane; i < side * side; i += nw) { // (the columns this lane staged)
+            const int ix = i / side, iy = i - ix * side;
+            if (ix >= x0 && ix <= x1 && iy >= y0 && iy <= y1) win[ix * WIN + iy] |= m;
+        }
+    }
+}
+#define FRP_ASTAR_BOX_COLUMN(c, i0, i1) | box_column(c, i0, i1)
+#define FRP_ASTAR_IN_BOX(c, i0, i1, i2) || in_box(c, i0, i1, i2)
+#define FRP_ASTAR_STAGE_BOXES(c, win, wx0, wy0, side, lane, nw) stage_boxes(c, win, wx0, wy0, side, lane, nw)
+#else
+#define FRP_ASTAR_BOX_COLUMN(c, i0, i1)
+#define FRP_ASTAR_IN_BOX(c, i0, i1, i2)
+#define FRP_ASTAR_STAGE_BOXES(c, win, wx0, wy0, side, lane, nw)
+#endif
 
 // the state of the voxel with map index (i0, i1, i2): getVoxelState after its posToIndex
 __device__ __forceinline__ int voxel_state_idx(const Ctx &c, int i0, int i1, int i2)
@@ -191,11 +260,12 @@ __device__ __forceinline__ int voxel_state_idx(const Ctx &c, int i0, int i1, int
         return 0;
     if (c.packed) {
         const int wx = i0 - c.wx0, wy = i1 - c.wy0;
+        // (a staged word holds the planner's boxes already; the packed map's own word takes them here)
         const unsigned long long w = (c.use_win && ((wx | (2 * c.win_r - wx) | wy | (2 * c.win_r - wy)) >= 0)) ? c.win[wx * WIN + wy]
-                                                                                                  : c.packed[(size_t)i0 * P->grid[1] + i1];
+                                                                                                  : (c.packed[(size_t)i0 * P->grid[1] + i1] FRP_ASTAR_BOX_COLUMN(c, i0, i1));
         return (int)((w >> i2) & 1ull);
     }
-    return c.occ[((size_t)i0 * P->grid[1] + i1) * P->grid[2] + i2] ? 1 : 0;
+    return (c.occ[((size_t)i0 * P->grid[1] + i1) * P->grid[2] + i2] FRP_ASTAR_IN_BOX(c, i0, i1, i2)) ? 1 : 0;
 }
 
 // OccMap::getVoxelState (occ_map.cpp:95-106): -1 outside the map, 0 free (or outside the local range), 1 occupied
@@ -623,6 +693,7 @@ __device__ __forceinline__ void run_search(const Args &a, Shared &sh, Ctx &ctx, 
                 const int gx = wx0 + ix, gy = wy0 + iy;
                 sh.win[ix * WIN + iy] = (gx >= 0 && gx < P->grid[0] && gy >= 0 && gy < P->grid[1]) ? ctx.packed[(size_t)gx * P->grid[1] + gy] : 0ull;
             }
+            FRP_ASTAR_STAGE_BOXES(ctx, sh.win, wx0, wy0, side, lane, NW);
             ctx.wx0 = wx0; ctx.wy0 = wy0; ctx.use_win = 1;
             set_cell_box(ctx);
         }
@@ -999,6 +1070,13 @@ __global__ __launch_bounds__(NT) void astar_kernel(Args a)
         ctx.win_r = r < 1 ? 1 : (r > (WIN - 1) / 2 ? (WIN - 1) / 2 : r);
     }
     ctx.fast = a.fast; ctx.off[0] = a.off[0]; ctx.off[1] = a.off[1]; ctx.off[2] = a.off[2];
+#ifdef FRP_ASTAR_PEERS
+    {   // a count below 1: no boxes; never more than Q rows
+        const int nb = a.count[b];
+        ctx.nbx = nb < 1 ? 0 : (nb > a.Q ? a.Q : nb);
+        ctx.bx = a.boxes + (size_t)b * a.Q * 6;
+    }
+#endif
     ctx.use_local = P->local_box ? 1 : 0;
     for (int i = 0; i < 3; i++) {
         ctx.lmin[i] = P->local_box ? P->local_box[6 * b + i] : 0;
@@ -1123,11 +1201,12 @@ __global__ __launch_bounds__(NT) void astar_kernel(Args a)
     }
 }
 
-} // namespace astar
+} // namespace FRP_ASTAR_NS
 } // namespace frp
 
 extern "C" {
 
+#ifndef FRP_ASTAR_PEERS
 size_t frp_nmpc_astar_workspace_bytes(const frp_nmpc_astar *p)
 {
     if (!p || p->B <= 0 || p->allocate_num <= 1) return 0;
@@ -1141,6 +1220,14 @@ size_t frp_nmpc_astar_workspace_bytes(const frp_nmpc_astar *p)
 int frp_nmpc_astar_batch(const frp_nmpc_astar *p, void *workspace, size_t workspace_bytes, void *stream)
 {
     using namespace frp::astar;
+#else
+int frp_nmpc_astar_batch_peers(const frp_nmpc_astar *p, const int *boxes, const int *count, int Q, void *workspace, size_t workspace_bytes, void *stream)
+{
+    using namespace frp::astar_peers;
+    if (Q < 0 || (boxes == nullptr) != (count == nullptr) || (Q > 0) != (boxes != nullptr)) return FRP_ERR_ARG;
+    if (Q == 0) return frp_nmpc_astar_batch(p, workspace, workspace_bytes, stream); // the plain search, the plain kernel
+    if (p && (long long)p->B * Q * 6 > 0x7fffffffLL) return FRP_ERR_ARG;
+#endif
     if (!p || p->B <= 0 || !p->occ || !p->start_pt || !p->start_vel || !p->start_acc || !p->end_pt || !p->end_vel || !p->external_acc ||
         !p->kino_path || !p->kino_size || !p->status || !workspace)
         return FRP_ERR_ARG;
@@ -1166,6 +1253,9 @@ int frp_nmpc_astar_batch(const frp_nmpc_astar *p, void *workspace, size_t worksp
     a.nodes = reinterpret_cast<Node *>(w); w += (size_t)p->B * p->allocate_num * sizeof(Node);
     a.heap = reinterpret_cast<HeapEnt *>(w); w += (size_t)p->B * p->allocate_num * sizeof(HeapEnt);
     a.hash = reinterpret_cast<HashEnt *>(w);
+#ifdef FRP_ASTAR_PEERS
+    a.boxes = boxes; a.count = count; a.Q = Q;
+#endif
     // getlineGrids hands cell centres (c res + res / 2) to getVoxelState, which floors ((centre - origin) / res) again: when that
     // round trip is c + off for every cell index a ray can reach, the kernel adds the offset instead (same results by this check)
     a.fast = 1;

@@ -27,40 +27,18 @@
 //     are clamped to [0, B * S]; an item is tested 0 <= q < B; a stage 0 <= st < N; a cloud row cloud_count + j < P.
 //   * No contraction (the build passes -ffp-contract=off as well): (dx * dx + dy * dy) + dz * dz is three products and two sums.
 //   * Every store is a plain C++ store from a vector lane; the only atomics are the int32 adds on cell counters; no inline assembly.
-#include <hip/hip_runtime.h>
-#include <limits.h>
-#include <math.h>
-#include "../../include/frp_nmpc.h"
+// (the walk over the 27 cells, the selection of the nearest peers and the grid's argument rules: frp_peers.hpp, shared with the peer boxes)
 #include "frp_fleet.hpp"
-
-#pragma clang fp contract(off)
+#include "frp_peers.hpp"
 
 namespace frp {
 namespace peers {
 
-using namespace fleet;
-
-constexpr int WAVE = 64;
-constexpr int WAVES = THREADS / WAVE;
 constexpr int CHUNK = FRP_PEERS_SCAN_CHUNK;
 constexpr int PER = CHUNK / THREADS;
-constexpr int CAND = FRP_PEERS_MAX_CAND;
-constexpr int NEAR = FRP_PEERS_MAX_NEAR;
 constexpr int WORDS = FRP_PEERS_SUM_WORDS;
 static_assert(CHUNK % THREADS == 0 && PER >= 1, "a thread scans PER consecutive counters");
-static_assert(CAND >= NEAR + WAVE && NEAR == WAVE, "a reduced list takes one more step of the wave; one lane per kept peer");
 static_assert(WORDS == FRP_PEERS_SUM_INTS + 1 && sizeof(long long) == 8 && sizeof(double) == 8, "one row is the minimum's bits and the integers");
-
-// the wavefront's own ordering of its LDS traffic (frp_device.hpp's form): no instruction on this target beyond the waits
-#define FRP_PEERS_SYNC()                                          \
-    do {                                                          \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");    \
-        __builtin_amdgcn_wave_barrier();                          \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");    \
-    } while (0)
-
-__device__ inline bool finite3(double x, double y, double z) { return finite_d(x) && finite_d(y) && finite_d(z); }
-__device__ inline double sq3(double x, double y, double z) { return (x * x + y * y) + z * z; }
 
 // (int)floor((p - origin) / cell) where that is a cell of the axis, -1 otherwise: the double is compared first, so a NaN, an infinity or
 // a quotient beyond int never reaches the conversion
@@ -69,8 +47,6 @@ __device__ inline int axis_cell(double p, double origin, double cell, int dim)
     const double f = floor((p - origin) / cell);
     return (f >= 0.0 && f < (double)dim) ? (int)f : -1;
 }
-
-__device__ inline int ncell_of(const frp_nmpc_peers &p) { return p.dims[0] * p.dims[1] * p.dims[2]; }
 
 __global__ __launch_bounds__(THREADS) void clear_kernel(int n1, int *start)
 {
@@ -186,21 +162,6 @@ __global__ __launch_bounds__(THREADS) void fill_kernel(frp_nmpc_peers p)
     if (at >= 0 && at < n) p.items[at] = (int)(i / p.S);
 }
 
-// The 9 ranges of `items` that hold the 27 cells around cell (cx, cy, cz) of segment s: range r = (dy + 1) + 3 * (dz + 1) is
-// [lo, hi), clamped to [0, nitems]; an absent row is the empty range
-__device__ inline void range_of(const frp_nmpc_peers &p, int s, int ncell, int nitems, int cx, int cy, int cz, int r, int &lo, int &hi)
-{
-    const int yy = cy + r % 3 - 1, zz = cz + r / 3 - 1;
-    lo = hi = 0;
-    if (yy < 0 || yy >= p.dims[1] || zz < 0 || zz >= p.dims[2]) return;
-    const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx < p.dims[0] - 1 ? cx + 1 : p.dims[0] - 1;
-    const int row = s * ncell + (zz * p.dims[1] + yy) * p.dims[0];
-    int a = p.start[row + x0], e = p.start[row + x1 + 1];
-    a = a < 0 ? 0 : a;
-    e = e > nitems ? nitems : e;
-    if (e > a) { lo = a; hi = e; }
-}
-
 __global__ __launch_bounds__(THREADS) void separation_kernel(frp_nmpc_peers p, const double *pos, int stride, double R2, double warn2, double hit2)
 {
     const int b = blockIdx.x * THREADS + threadIdx.x;
@@ -268,9 +229,6 @@ __device__ inline long long wave_sum_ll(long long v)
     for (int d = WAVE / 2; d >= 1; d >>= 1) v += __shfl_down(v, d, WAVE);
     return v;
 }
-
-// is the key (d, i) before (e, j)
-__device__ inline bool before(double d, int i, double e, int j) { return d < e || (d == e && i < j); }
 
 // launch 1: the partials of workgroup g over vehicles 256 g ... 256 g + 255 into row g of the workspace
 __global__ __launch_bounds__(THREADS) void summary_partial_kernel(frp_nmpc_peers p, const int *mask, long long *ws)
@@ -340,25 +298,6 @@ __global__ __launch_bounds__(THREADS) void summary_final_kernel(int G, const lon
     }
 }
 
-// The wave's list (cd, cp)[0 .. n) reduced to its min(n, NEAR) smallest keys, ascending, in (kd, kp) and copied back to the front of the
-// list; returns their number.  Called by the whole wave with a uniform n.
-__device__ inline int keep_smallest(double *cd, int *cp, double *kd, int *kp, int n, int lane)
-{
-    FRP_PEERS_SYNC();
-    for (int i = lane; i < n; i += WAVE) {
-        const double d = cd[i];
-        const int q = cp[i];
-        int rank = 0;
-        for (int j = 0; j < n; j++) rank += before(cd[j], cp[j], d, q) ? 1 : 0;
-        if (rank < NEAR) { kd[rank] = d; kp[rank] = q; }
-    }
-    FRP_PEERS_SYNC();
-    const int m = n < NEAR ? n : NEAR;
-    if (lane < m) { cd[lane] = kd[lane]; cp[lane] = kp[lane]; }
-    FRP_PEERS_SYNC();
-    return m;
-}
-
 // point t of planner b's emission order: kept peer t / (nc * per), centre (t / per) % nc, point t % per.  False where it is dropped.
 __device__ inline bool peer_point(const frp_nmpc_peers &p, const frp_nmpc_peers_view &v, const double *pos, int stride, const int *kp, int nc, int per, int t,
                                   const double lo[3], const double hi[3], double q[3])
@@ -402,6 +341,8 @@ __global__ __launch_bounds__(THREADS) void cloud_kernel(frp_nmpc_peers p, frp_nm
         if (lane == 0) { v.added[b] = 0; v.overflow[b] = 0; }
         return;
     }
+    // (this selection is select_near of frp_peers.hpp, stated here as it was: called as that function the kernel came out with other bytes.
+    //  KEEP IN STEP: an edit here is an edit there)
     const int ncell = ncell_of(p), nitems = p.B;
     const int cid = p.key[b];
     int n = 0, seen = 0;
@@ -487,28 +428,10 @@ __global__ __launch_bounds__(THREADS) void cloud_kernel(frp_nmpc_peers p, frp_nm
 
 // ---- host: the argument rules ----
 
-static bool grid_ok(const frp_nmpc_peers *p)
-{
-    if (!p || p->B < 0 || p->S < 1 || !positive(p->cell) || !positive(p->R) || !(p->R <= p->cell)) return false;
-    long long cells = p->S;
-    for (int i = 0; i < 3; i++) {
-        if (!finite_d(p->origin[i]) || p->dims[i] < 1 || p->dims[i] > FRP_PEERS_MAX_CELLS) return false;
-        cells *= p->dims[i];
-        if (cells > FRP_PEERS_MAX_CELLS) return false;
-    }
-    if ((long long)p->B * p->S > 0x7fffffffLL) return false;
-    return p->start && p->items && p->key && p->slot && p->block_sums && p->outside;
-}
-
 static bool record_ok(const frp_nmpc_peers *p)
 {
     return p->sep2_min && p->nearest && p->near_samples && p->hit_samples && p->samples && p->first_hit && p->tick && p->sum_ws &&
            non_negative(p->d_hit) && p->d_hit <= p->d_warn && p->d_warn <= p->R;
-}
-
-static bool pos_ok(const frp_nmpc_peers *p, const double *pos, int stride)
-{
-    return pos && stride >= 3 && (long long)p->B * p->S * stride <= 0x7fffffffLL;
 }
 
 } // namespace peers

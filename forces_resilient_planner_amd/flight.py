@@ -6,7 +6,7 @@ import collections
 import ctypes
 
 from . import layout as L
-from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, MISSION_MAX_TRIES, MissionArgs, OccMapBody, ODOM_BODY, ODOM_WORLD, PEERS_MAX_CELLS, PEERS_MAX_STAGES, PEERS_SCAN_CHUNK, PEERS_SUM_INTS, PEERS_SUM_WORDS, PeersArgs, PeersViewArgs,
+from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, MISSION_MAX_TRIES, MissionArgs, OccMapBody, ODOM_BODY, ODOM_WORLD, PEERS_MAX_CELLS, PEERS_MAX_NEAR, PEERS_MAX_STAGES, PEERS_SCAN_CHUNK, PEERS_SUM_INTS, PEERS_SUM_WORDS, PeersArgs, PeersBoxArgs, PeersViewArgs,
                    SENSOR_NOISE_MAX_FRAMES, SensorNoiseArgs, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
                    checked_ptr, lib, optional_ptr, stream_ptr, tensor_ptr)
 from .fleet import TickState
@@ -856,6 +856,12 @@ class FleetPeers:
     Nothing hooks into FleetFSM.period: the caller launches, inside the same graph if it wishes,
         view = occmap.local_view(veh.state[:, :3], P, out=view); peers.cloud(fleet, veh.state, view, occmap)
         fsm.period(..., cloud=view.cloud, cloud_count=view.cloud_count, vehicle=veh); peers.update()
+    Avoidance (section 19), opt-in: boxes() turns every planner's peers -- now and at the constructor's stages of their plans -- into boxes
+    of map voxels; check_paths() walks the path a planner holds against them and hands the verdict to the state machine (one more
+    checkReplanCallback: a hit sends the planner to REPLAN_TRAJ); planner.overlay = peers makes every search of that planner route around
+    them.  In a period:  peers.boxes(fleet, veh.state, occmap, half); peers.check_paths(planner, fsm); fsm.period(...).  CHOSEN, not
+    derived: a peer's future stages stand as obstacles for the whole search; boxes, not spheres; a box over the planner's own voxel is
+    dropped (dropped_own counts them); a goal a parked peer blocks is not handled.
     vehicle_or_B: a Vehicle made with trace=True (update() then reads its trace) or the number of vehicles.  origin [3], dims [3], cell:
     the grid's box; R <= cell the radius; d_hit <= d_warn <= R the record's radii; S the samples per update() at the most; r_body and
     stages (0 ... 8 rows of a plan) the cloud's.
@@ -907,6 +913,7 @@ class FleetPeers:
         self.added, self.overflow = i32(B), i32(B)
         self.stages = t.tensor(self.stage_list, dtype=t.int32, device=dev) if self.stage_list else None
         self._built = None  # (pos, S, stride) of the last build(): what separation() reads
+        self.box_rows = self.box_count = self.box_overflow = self.dropped_own = self.path_hit = self._no_goal = self._box_view = None  # boxes() makes them
 
     def struct(self, S=None, grid=None):
         """The frp_nmpc_peers of a grid of S samples (None: the constructor's) on the buffers `grid` (None: update()'s own)."""
@@ -980,6 +987,62 @@ class FleetPeers:
         _check(lib().frp_nmpc_peers_build(ctypes.byref(f), tensor_ptr(state), stride, None, s), "frp_nmpc_peers_build")
         _check(lib().frp_nmpc_peers_cloud(ctypes.byref(f), ctypes.byref(v), tensor_ptr(state), stride, s), "frp_nmpc_peers_cloud")
         return view
+
+    def boxes(self, fleet, state, occmap, half, Q=None, stream=None):
+        """frp_nmpc_peers_boxes: a grid of its own (S = 1) of state [B,9] f64, then every planner's peers within R as boxes of occmap's voxels,
+        centre -+ half [3] metres (a scalar: every axis), at their positions and at the constructor's stages of fleet.pre_plan.  Q rows per
+        planner (None: FRP_PEERS_MAX_NEAR * (1 + stages), which cannot overflow).  Writes box_rows [B,Q,6] int32, box_count, box_overflow and
+        dropped_own [B] int32 -- allocated at the first call, the same tensors afterwards (a captured call replays into them)."""
+        import math
+        t = self.torch
+        S, stride = self._samples(state)
+        if S != 1 or state.dim() != 2:
+            raise ValueError("FleetPeers.boxes: state is [B,stride] f64, one sample a vehicle")
+        if getattr(fleet, "pre_plan", None) is None:
+            raise RuntimeError("FleetPeers.boxes: the fleet has no pre_plan yet: snapshot_commands() (or a TickState) makes it")
+        B, N = self.B, int(fleet.N)
+        if any(k >= N for k in self.stage_list):
+            raise ValueError(f"FleetPeers: a stage beyond the plan's {N} rows")
+        half = tuple(float(h) for h in (half if hasattr(half, "__len__") else (half,) * 3))
+        if len(half) != 3 or not all(math.isfinite(h) and h >= 0.0 for h in half):
+            raise ValueError("FleetPeers.boxes: half [3] finite and >= 0")
+        Q = PEERS_MAX_NEAR * (1 + len(self.stage_list)) if Q is None else int(Q)
+        if Q < 0:
+            raise ValueError("FleetPeers.boxes: Q >= 0")
+        if self.box_rows is not None and int(self.box_rows.shape[1]) != Q:
+            raise ValueError(f"FleetPeers.boxes: Q is fixed by the first call ({int(self.box_rows.shape[1])}), not {Q}")
+        if self.box_rows is None:
+            i32 = lambda *shape: t.zeros(shape, dtype=t.int32, device=self.device)
+            self.box_rows, self.box_count, self.box_overflow, self.dropped_own, self.path_hit, self._no_goal = i32(B, Q, 6), i32(B), i32(B), i32(B), i32(B) - 1, i32(B)
+        like = self.sep2_min
+        self._box_view = PeersBoxArgs(N, len(self.stage_list), Q, (ctypes.c_double * 3)(*half), (ctypes.c_double * 3)(*[float(o) for o in occmap.origin]),
+                                      float(occmap.resolution), (ctypes.c_int * 3)(*[int(g) for g in occmap.grid]),
+                                      checked_ptr(like, fleet.pre_plan, t.float64, (B, N, L.NZ)), checked_ptr(like, fleet.have_traj, t.int32, (B,)),
+                                      tensor_ptr(self.stages), self.box_rows.data_ptr() if Q else None, self.box_count.data_ptr(), self.box_overflow.data_ptr(),
+                                      self.dropped_own.data_ptr())
+        f = self.struct(1, self._grid1)
+        s = stream_ptr(stream, like)
+        _check(lib().frp_nmpc_peers_build(ctypes.byref(f), tensor_ptr(state), stride, None, s), "frp_nmpc_peers_build")
+        _check(lib().frp_nmpc_peers_boxes(ctypes.byref(f), ctypes.byref(self._box_view), tensor_ptr(state), stride, s), "frp_nmpc_peers_boxes")
+        return self.box_rows, self.box_count
+
+    def check_paths(self, planner, fsm=None, stride=5, stream=None):
+        """frp_nmpc_peers_check_paths: the safety timer's path walk of planner.kino_path / kino_size (every stride-th sample; fsm.have_traj
+        where fsm is given) against the boxes of the last boxes(); path_hit [B] int32 <- the first sample inside a box, or -1.  With fsm:
+        then fsm.safety_verdict(no goal verdict, path_hit) -- one more checkReplanCallback, which sends a planner whose path is hit to
+        REPLAN_TRAJ.  Returns path_hit."""
+        t = self.torch
+        if self._box_view is None:
+            raise RuntimeError("FleetPeers.check_paths: call boxes() first")
+        like = self.sep2_min
+        B, K = self.B, int(planner.kino_path.shape[1])
+        _check(lib().frp_nmpc_peers_check_paths(ctypes.byref(self._box_view), B, K, int(stride), checked_ptr(like, planner.kino_path, t.float64, (B, K, 3)),
+                                                checked_ptr(like, planner.kino_size, t.int32, (B,)),
+                                                None if fsm is None else checked_ptr(like, fsm.have_traj, t.int32, (B,)), self.path_hit.data_ptr(),
+                                                stream_ptr(stream, like)), "frp_nmpc_peers_check_paths")
+        if fsm is not None:
+            fsm.safety_verdict(self._no_goal, self.path_hit, stream)
+        return self.path_hit
 
     def summary(self, mask=None, stream=None):
         """frp_nmpc_peers_summary over the vehicles with mask [B] int32 != 0 (None: all): returns (out_i [5] int64: PEERS_I_*, out_f [1] f64:

@@ -130,7 +130,10 @@ class AstarPlanner:
     (frp_nmpc_astar_batch).  `world`: occupancy grid occ[x][y][z] (uint8) + the map / search constants of the reference's launch
     files (forces_resilient_planner_amd.workloads.astar_world), or an OccupancyMap: the planner then searches the map's own occ
     buffer (no copy: later inserts are seen) -- pass the local_box of the map's local view to plan().  Outputs stay in HBM: kino_path [B,K,3] / kino_size [B] are what
-    DeviceFleet.references() takes as a per-planner path."""
+    DeviceFleet.references() takes as a per-planner path.
+    overlay: None, or an object with box_rows [B,Q,6] int32 and box_count [B] int32 device tensors (a FleetPeers after boxes()): plan() then
+    searches, per planner, the map plus the first box_count[b] boxes (frp_nmpc_astar_batch_peers) -- a peer is an obstacle of the search.
+    Whoever calls plan() -- FleetFSM.exec_step inside a period, too -- gets that search; with None every call is what it was."""
 
     def __init__(self, world, B, K=1024, Ts=0.05, device="cuda:0", want_path_nodes=False, allocate_num=None):
         import torch
@@ -154,6 +157,7 @@ class AstarPlanner:
         self.allocate_num = int(allocate_num or world["allocate_num"])
         self._q = [torch.zeros((B, 3), **f64) for _ in range(6)]
         self._retry = None  # (retry_pt, retry_vel): the start of the repeated search, when it differs (upload(..., retry=...))
+        self.overlay = None
         a = self._args()
         self.ws_bytes = int(lib().frp_nmpc_astar_workspace_bytes(ctypes.byref(a)))
         self.ws = torch.empty((self.ws_bytes // 8 + 1,), **f64)
@@ -202,6 +206,15 @@ class AstarPlanner:
         end_pt / end_vel / external_acc: [B,3] f64 device tensors read in place of the uploaded ones (FleetFSM hands over its own
         end_pt and external_acc: no copy)."""
         a = self._args(init, local_box, active, end_pt, end_vel, external_acc)
+        if self.overlay is not None:
+            bx, cnt, t = self.overlay.box_rows, self.overlay.box_count, self.torch
+            if bx is None or cnt is None or bx.dtype != t.int32 or cnt.dtype != t.int32 or not bx.is_contiguous() or not cnt.is_contiguous() or \
+                    bx.device != self.device or cnt.device != self.device or bx.dim() != 3 or int(bx.shape[0]) != self.B or int(bx.shape[2]) != 6 or tuple(cnt.shape) != (self.B,):
+                raise ValueError("AstarPlanner.overlay: box_rows [B,Q,6] / box_count [B] int32 contiguous device tensors (FleetPeers.boxes() makes them)")
+            Q = int(bx.shape[1])
+            _check(lib().frp_nmpc_astar_batch_peers(ctypes.byref(a), tensor_ptr(bx) if Q else None, tensor_ptr(cnt) if Q else None, Q, tensor_ptr(self.ws),
+                                                    self.ws_bytes, stream_ptr(stream, self.device)), "frp_nmpc_astar_batch_peers")
+            return
         _check(lib().frp_nmpc_astar_batch(ctypes.byref(a), tensor_ptr(self.ws), self.ws_bytes, stream_ptr(stream, self.device)),
                "frp_nmpc_astar_batch")
 

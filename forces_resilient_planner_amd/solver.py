@@ -24,7 +24,7 @@ from .capi import (ABI_VERSION, ASTAR_MAX_PATH, ASTAR_NO_PATH, ASTAR_REACH_END, 
                    VEHICLE_SAT_THRUST_HI, VEHICLE_SAT_THRUST_LO, VEHICLE_SAT_YAW_WRAP, VEHICLE_SAT_ZERO_ACC, VEHICLE_STATE, VIEW_EXPORTS, Astar, Batch,
                    Command, Corridor, CorridorCut, CorridorLarge, DisturbanceArgs, EstimatorArgs, FlightRecordArgs, ForcesInfo, ForcesOutput, ForcesParams, Fsm,
                    FsmExecIn, MissionArgs, OccMap, OccMapBody, OccMapFuse, OccMapFuseBatch, OccMapFusePoints, OccMapRender, OccMapRenderScan, OccMapSharedView,
-                   OccMapView, Options, Pack, PeersArgs, PeersViewArgs, Reference, SensorNoiseArgs, Tick, TickIn, Tube, VehicleArgs, _PKG, _check, _lib, c_double_p, c_int_p, lib)
+                   OccMapView, Options, Pack, PeersArgs, PeersBoxArgs, PeersViewArgs, Reference, SensorNoiseArgs, Tick, TickIn, Tube, VehicleArgs, _PKG, _check, _lib, c_double_p, c_int_p, lib)
 from .batch import (DeviceSolver, _registered, default_options, host_register, host_unregister, host_unregister_all, kernel_timing_begin,
                     kernel_timing_end, solve_batch_host, solve_batch_host_begin, solve_batch_host_wait, solver_variant, stage_eval_host)
 from .occmap import (OCCMAP_BODY, OCCMAP_DEFAULTS, OCCMAP_DIST_DEFAULT_R, OCCMAP_FUSE_DEFAULTS, OCCMAP_FUSE_POINTS_PARAMS, SAFETY_INFLATE_CHECK,

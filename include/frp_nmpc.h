@@ -662,6 +662,71 @@ int FORCESNLPsolver_normal_solve(frp_forces_params *params, frp_forces_output *o
 int FORCESNLPsolver_final_solve(frp_forces_params *params, frp_forces_output *output, frp_forces_info *info,
                                 FILE *fs, frp_forces_extfunc evalextfunctions);
 
+/* ---- (19) peer avoidance: a planner's peers as boxes of map voxels, for the A* and for the safety timer's path walk ---- */
+/* (Declared here, ahead of section (15), for section (18)'s reasons: the exports of sections (15), (18), (16), (17) and (14) stay
+ * neighbours in that order and the flight record's stay the last.  frp_nmpc_peers is section (18)'s struct, named by its tag.)
+ * The peer cloud of section (18) reaches the corridor alone.  These three calls make a peer an obstacle of the SEARCH and of the PATH WALK: per
+ * planner, the voxels its neighbours occupy now and along their plans (boxes), the kinodynamic A* on the map plus those boxes, and
+ * checkReplanCallback's path loop against them.  Everything is opt-in: no existing call launches other code than it did, no existing
+ * struct changed, same ABI version.  NO REFERENCE COUNTERPART; tests/peers_avoid_oracle.py is the executable statement of the boxes and of
+ * the path walk (csrc/frp_peers_boxes.hip is built without contraction, no transcendental on the path), and the A* on a planner's boxes
+ * is oracle/astar_oracle.c on a copy of the world with the boxes written into occ.  CHOSEN, not derived: a peer's future stages are
+ * stamped as STANDING obstacles (no time axis in the search); boxes, not spheres (half[3] per axis); a box over the planner's own voxel
+ * is dropped (below); a goal blocked by a parked peer is not handled (the goal search reads the map alone); and the reference's
+ * "REPLAN from any state" applies to peers too: a hit on the held path sends the planner to REPLAN_TRAJ through frp_nmpc_fsm_safety.
+ *
+ * Boxes of planner b, on a grid built with S = 1 from pos (frp_nmpc_peers_cloud's preconditions, section 18):
+ *   peers and their order: the peer cloud's rule (ascending in (d2, q), the first FRP_PEERS_MAX_NEAR kept, overflow[b] as there)
+ *   centres of a kept peer, in this order: its current position; where have_traj[q] != 0, pre_plan[q][stages[k]][8..10], k = 0 ... K - 1
+ *          (a stage outside 0 ... N - 1 gives none)
+ *   box of a centre c, on every axis k, with inv = 1.0 / resolution formed once on the host:
+ *          lo = floor(((c[k] - half[k]) - origin[k]) * inv),  hi = floor(((c[k] + half[k]) - origin[k]) * inv)      (posToIndex's operations)
+ *   dropped, tested in this order on the doubles (nothing is converted to int before it was compared with 0 and grid[k]):
+ *          a bound that is not finite; a box wholly outside the map (hi < 0 or lo > grid[k] - 1 on some axis); a box that contains the
+ *          voxel of the planner's own position, own[k] = floor((pos[b][k] - origin[k]) * inv), lo <= own <= hi on every axis -- counted
+ *          in dropped_own[b]: a peer's later stage over the spot a planner is leaving must not wall that planner in
+ *   a kept box is clipped to [0, grid[k] - 1] and stored as min_id (3), max_id (3), inclusive, in boxes[b][j], peer rank first, then
+ *          centre; count[b] <- n -- or, where n > Q, nothing is stored and count[b] <- -n.  Rows past the count are not touched.
+ * Both consumers read a count below 1 as "no boxes" and never more than Q rows. */
+typedef struct frp_nmpc_peers_box_view {
+    int N, K, Q;                  /* rows of a plan (>= 1), stages taken (0 ... FRP_PEERS_MAX_STAGES), rows of boxes per planner (>= 0) */
+    double half[3];               /* metres, finite and >= 0: half the edge of a peer's box per axis                                   */
+    double origin[3], resolution; /* the MAP's origin (finite) and resolution (finite, > 0)                                            */
+    int grid[3];                  /* the MAP's voxels per axis (>= 1)                                                                  */
+    const double *pre_plan;       /* [B][N][17]                                                                                        */
+    const int *have_traj;         /* [B]                                                                                               */
+    const int *stages;            /* [K]; NULL iff K == 0                                                                              */
+    int *boxes;                   /* [B][Q][6] out; NULL iff Q == 0                                                                    */
+    int *count;                   /* [B] out                                                                                           */
+    int *overflow, *dropped_own;  /* [B] out                                                                                           */
+} frp_nmpc_peers_box_view;
+
+/* The boxes above.  One launch, one wavefront per planner.  The path walk reads pre_plan, have_traj and stages of v not at all.
+ * FRP_ERR_ARG: whatever frp_nmpc_peers_cloud refuses of p, pos and stride; v NULL; N < 1; K outside 0 ... FRP_PEERS_MAX_STAGES; Q < 0;
+ * B * Q * 6 or B * N * 17 beyond 2^31 - 1; a half not finite or negative; resolution not finite and positive; an origin not finite; a
+ * grid < 1; pre_plan, have_traj, count, overflow or dropped_own NULL; stages NULL with K > 0; boxes NULL with Q > 0. */
+struct frp_nmpc_peers;
+int frp_nmpc_peers_boxes(const struct frp_nmpc_peers *p, const frp_nmpc_peers_box_view *v, const double *pos, int stride, void *stream);
+
+/* frp_nmpc_astar_batch on the map in which, for planner b, a voxel is occupied where occ says so OR it lies in one of the first
+ * count[b] rows of boxes[b] (boxes [B][Q][6], count [B], as frp_nmpc_peers_boxes leaves them; a count below 1: none; a count above Q --
+ * the call cannot see it, the arrays are device memory -- reads Q rows).  getVoxelState's order is unchanged: outside the map -1, outside
+ * the local box 0, then the union.  Workspace: frp_nmpc_astar_workspace_bytes.  The kernel is csrc/frp_astar.hip's text compiled a second
+ * time with the overlay (csrc/frp_astar_peers.hip); frp_nmpc_astar_batch launches the code it launched before.  boxes and count both NULL
+ * with Q == 0 is the plain search (that kernel).  FRP_ERR_ARG: whatever frp_nmpc_astar_batch refuses; Q < 0; exactly one of boxes / count
+ * NULL; Q > 0 without them; Q == 0 with them; B * Q * 6 beyond 2^31 - 1. */
+int frp_nmpc_astar_batch_peers(const frp_nmpc_astar *p, const int *boxes, const int *count, int Q, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/* frp_nmpc_occmap_check_paths's loop against the boxes of v (origin, resolution, grid, Q, boxes and count are read): for planner b the
+ * samples 0, stride, ... < min(kino_size[b], path_K) of kino_path [B][path_K][3], none where have_traj (or NULL) [b] == 0.  A sample
+ * collides when its voxel floor((p[k] - origin[k]) * inv), inside the map on every axis, lies in one of b's boxes; first_hit[b] <- the
+ * smallest such sample index, or -1.  One launch, one thread per planner.
+ * FRP_ERR_ARG: v NULL or its map fields, Q, boxes or count against frp_nmpc_peers_boxes's rules; B < 0; path_K < 1; stride < 1; kino_path,
+ * kino_size or first_hit NULL with B > 0; B * path_K * 3 or B * Q * 6 beyond 2^31 - 1.  B == 0 is FRP_OK without a launch. */
+int frp_nmpc_peers_check_paths(const frp_nmpc_peers_box_view *v, int B, int path_K, int stride, const double *kino_path, const int *kino_size,
+                               const int *have_traj, int *first_hit, void *stream);
+
 /* ---- (15) the disturbance: the TRUE external force as a function of position, time and a seeded stream, on the device ---- */
 /* (Declared ahead of section (14): the flight record's five calls stay the last exports of this header.)
  * What acts on a vehicle of section (12), evaluated per command sample inside the step that flies the sample: wind zones fixed in the
@@ -1156,8 +1221,8 @@ int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min
                             const double *edges, long long *out_i, double *out_f, long long *hist, void *workspace, size_t workspace_bytes,
                             void *stream);
 
-/* (Sections (15), the disturbance, (18), the fleet peers, (16), the sensor noise, and (17), the mission, are declared ahead of section
- * (14), above.) */
+/* (Sections (19), peer avoidance, (15), the disturbance, (18), the fleet peers, (16), the sensor noise, and (17), the mission, are declared
+ * ahead of section (14), above.) */
 
 #ifdef __cplusplus
 }
