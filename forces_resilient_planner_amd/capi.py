@@ -237,6 +237,13 @@ class PeersBoxArgs(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ("pre_plan", "have_traj", "stages", "boxes", "count", "overflow", "dropped_own")]
 
 
+class YieldArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("n_clear", ctypes.c_int), ("hold_timeout", ctypes.c_int), ("r_release", ctypes.c_double), ("a_brake", ctypes.c_double)] + \
+               [(n, ctypes.c_void_p) for n in ("state", "astar_status", "outrank_boxes", "outrank_d2", "goal_in", "fresh_in", "fleet_have_traj", "cmd_end_pt",
+                                               "holding", "clear_count", "hold_age", "held_goal", "goal", "fresh", "holds", "releases", "timeouts", "hold_periods",
+                                               "longest_hold", "bad")]
+
+
 class OccMapBody(ctypes.Structure):
     _fields_ = [("ego_r", ctypes.c_double), ("ego_h", ctypes.c_double)]
 
@@ -264,7 +271,7 @@ EXTFUNC = ctypes.CFUNCTYPE(None, c_double_p, c_double_p, c_double_p, c_double_p,
 C_TYPES = {cls: (ctype, header) for header, group in {
     "frp_nmpc.h": {Options: "frp_nmpc_options", Batch: "frp_nmpc_batch", Pack: "frp_nmpc_pack", Tube: "frp_nmpc_tube", Corridor: "frp_nmpc_corridor",
                    CorridorCut: "frp_nmpc_corridor_cut", Reference: "frp_nmpc_reference", Astar: "frp_nmpc_astar", OccMap: "frp_nmpc_occmap",
-                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", SensorNoiseArgs: "frp_nmpc_sensor_noise", MissionArgs: "frp_nmpc_mission", PeersArgs: "frp_nmpc_peers", PeersViewArgs: "frp_nmpc_peers_view", PeersBoxArgs: "frp_nmpc_peers_box_view", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
+                   OccMapView: "frp_nmpc_occmap_view", DisturbanceArgs: "frp_nmpc_disturbance", SensorNoiseArgs: "frp_nmpc_sensor_noise", MissionArgs: "frp_nmpc_mission", PeersArgs: "frp_nmpc_peers", PeersViewArgs: "frp_nmpc_peers_view", PeersBoxArgs: "frp_nmpc_peers_box_view", YieldArgs: "frp_nmpc_yield", FlightRecordArgs: "frp_nmpc_flight_record", ForcesParams: "frp_forces_params", ForcesOutput: "frp_forces_output", ForcesInfo: "frp_forces_info"},
     "frp_nmpc_occmap_fuse.h": {OccMapFuse: "frp_nmpc_occmap_fuse"}, "frp_nmpc_occmap_fuse_batch.h": {OccMapFuseBatch: "frp_nmpc_occmap_fuse_batch"},
     "frp_nmpc_occmap_fuse_points.h": {OccMapFusePoints: "frp_nmpc_occmap_fuse_points"}, "frp_nmpc_occmap_check.h": {OccMapBody: "frp_nmpc_occmap_body"},
     "frp_nmpc_occmap_render.h": {OccMapRender: "frp_nmpc_occmap_render"}, "frp_nmpc_occmap_render_scan.h": {OccMapRenderScan: "frp_nmpc_occmap_render_scan"},
@@ -357,6 +364,9 @@ _BY_HEADER = {
         "frp_nmpc_device_count": (_i, []),
         "FORCESNLPsolver_normal_solve": _forces,
         "FORCESNLPsolver_final_solve": _forces,
+        "frp_nmpc_peers_boxes_ranked": (_i, [_peers, _P(PeersBoxArgs), _v, _i, _v, _v, _v, _v]),
+        "frp_nmpc_yield_step": (_i, [_P(YieldArgs), _fsm, _v]),
+        "frp_nmpc_yield_reset": (_i, [_P(YieldArgs), _v, _v]),
         "frp_nmpc_peers_boxes": (_i, [_peers, _P(PeersBoxArgs), _v, _i, _v]),
         "frp_nmpc_astar_batch_peers": (_i, [_P(Astar), _v, _v, _i, _v, _z, _v]),
         "frp_nmpc_peers_check_paths": (_i, [_P(PeersBoxArgs), _i, _i, _i, _v, _v, _v, _v, _v]),

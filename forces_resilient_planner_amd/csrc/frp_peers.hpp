@@ -2,7 +2,8 @@
 // frp_peers_boxes.hip: the peer boxes): the walk over the 27 cells around a planner and the selection of its FRP_PEERS_MAX_NEAR nearest
 // peers by one wavefront.  The helpers are frp_peers.hip's text as it was, moved; select_near is the candidate loop of its cloud kernel as
 // a function, which that kernel still states itself (called as a function it came out with other bytes; as it is, that unit's device code
-// did not change: profiles/peers_avoid_astar_identity.txt).  Both units are built with -ffp-contract=off.
+// did not change: profiles/peers_avoid_astar_identity.txt).  Both units are built with -ffp-contract=off.  frp_peers_yield.hip (section
+// 20, the ranked boxes) is the third: it shares the selection and, with frp_peers_boxes.hip, the box of a centre and the argument rules.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -129,7 +130,50 @@ __device__ __forceinline__ int select_near(const frp_nmpc_peers &p, const double
     return keep_smallest(cd, cp, kd, kp, n, lane);
 }
 
-// ---- host: the argument rules both units apply to a grid and to the positions it was built from ----
+// ---- the box of a centre: what frp_peers_boxes.hip and frp_peers_yield.hip (the ranked boxes) both state ----
+
+// floor((x - origin) * inv): posToIndex before its conversion
+__device__ inline double voxel_f(double x, double origin, double inv) { return floor((x - origin) * inv); }
+
+// Centre t of planner b's emission order (kept peer t / nc, centre t % nc) as the box it gives: 1 kept (lo / hi clipped, as ints), 0
+// dropped, -1 dropped because it holds the planner's own voxel.  own[k]: voxel_f of the planner's position.
+__device__ inline int peer_box(const frp_nmpc_peers &p, const frp_nmpc_peers_box_view &v, const double *pos, int stride, const int *kp, int nc, int t, double inv,
+                               const double own[3], int lo[3], int hi[3])
+{
+    const int peer = kp[t / nc], c = t % nc;
+    if (peer < 0 || peer >= p.B) return 0;
+    const double *src;
+    if (c == 0) {
+        src = pos + (size_t)peer * stride;
+    } else {
+        if (v.have_traj[peer] == 0) return 0;
+        const int st = v.stages[c - 1];
+        if (st < 0 || st >= v.N) return 0;
+        src = v.pre_plan + ((size_t)peer * v.N + st) * ROW + 8;
+    }
+    double fl[3], fh[3];
+    bool finite = true, outside = false, mine = true;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        fl[k] = voxel_f(src[k] - v.half[k], v.origin[k], inv);
+        fh[k] = voxel_f(src[k] + v.half[k], v.origin[k], inv);
+        const double top = (double)(v.grid[k] - 1);
+        finite = finite && finite_d(fl[k]) && finite_d(fh[k]);
+        outside = outside || fh[k] < 0.0 || fl[k] > top;
+        mine = mine && fl[k] <= own[k] && own[k] <= fh[k];
+    }
+    if (!finite || outside) return 0;
+    if (mine) return -1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { // (both bounds are finite, fh >= 0 and fl <= grid - 1: the clipped values are voxel indices)
+        const double top = (double)(v.grid[k] - 1);
+        lo[k] = fl[k] < 0.0 ? 0 : (int)fl[k];
+        hi[k] = fh[k] > top ? v.grid[k] - 1 : (int)fh[k];
+    }
+    return 1;
+}
+
+// ---- host: the argument rules the units apply to a grid and to the positions it was built from ----
 
 static bool grid_ok(const frp_nmpc_peers *p)
 {
@@ -147,6 +191,24 @@ static bool grid_ok(const frp_nmpc_peers *p)
 static bool pos_ok(const frp_nmpc_peers *p, const double *pos, int stride)
 {
     return pos && stride >= 3 && (long long)p->B * p->S * stride <= 0x7fffffffLL;
+}
+
+// the map fields, Q, boxes and count of a view: what the boxes and the path walk both need
+static bool map_ok(const frp_nmpc_peers_box_view *v, long long B)
+{
+    if (!v || v->Q < 0 || !positive(v->resolution) || !v->count || (v->Q > 0 && !v->boxes)) return false;
+    for (int k = 0; k < 3; k++)
+        if (!finite_d(v->origin[k]) || v->grid[k] < 1) return false;
+    return B * v->Q * 6 <= 0x7fffffffLL;
+}
+
+// what frp_nmpc_peers_boxes refuses of its arguments, for the entries that take the same ones
+static bool boxes_ok(const frp_nmpc_peers *p, const frp_nmpc_peers_box_view *v, const double *pos, int stride)
+{
+    if (!grid_ok(p) || p->S != 1 || !pos_ok(p, pos, stride) || !map_ok(v, p->B)) return false;
+    if (v->N < 1 || v->K < 0 || v->K > FRP_PEERS_MAX_STAGES || !non_negative(v->half[0]) || !non_negative(v->half[1]) || !non_negative(v->half[2])) return false;
+    if (!v->pre_plan || !v->have_traj || (v->K > 0 && !v->stages) || !v->overflow || !v->dropped_own) return false;
+    return (long long)p->B * v->N * ROW <= 0x7fffffffLL;
 }
 
 } // namespace peers

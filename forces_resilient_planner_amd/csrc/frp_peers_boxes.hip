@@ -18,47 +18,6 @@
 namespace frp {
 namespace peers {
 
-// floor((x - origin) * inv): posToIndex before its conversion
-__device__ inline double voxel_f(double x, double origin, double inv) { return floor((x - origin) * inv); }
-
-// Centre t of planner b's emission order (kept peer t / nc, centre t % nc) as the box it gives: 1 kept (lo / hi clipped, as ints), 0
-// dropped, -1 dropped because it holds the planner's own voxel.  own[k]: voxel_f of the planner's position.
-__device__ inline int peer_box(const frp_nmpc_peers &p, const frp_nmpc_peers_box_view &v, const double *pos, int stride, const int *kp, int nc, int t, double inv,
-                               const double own[3], int lo[3], int hi[3])
-{
-    const int peer = kp[t / nc], c = t % nc;
-    if (peer < 0 || peer >= p.B) return 0;
-    const double *src;
-    if (c == 0) {
-        src = pos + (size_t)peer * stride;
-    } else {
-        if (v.have_traj[peer] == 0) return 0;
-        const int st = v.stages[c - 1];
-        if (st < 0 || st >= v.N) return 0;
-        src = v.pre_plan + ((size_t)peer * v.N + st) * ROW + 8;
-    }
-    double fl[3], fh[3];
-    bool finite = true, outside = false, mine = true;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        fl[k] = voxel_f(src[k] - v.half[k], v.origin[k], inv);
-        fh[k] = voxel_f(src[k] + v.half[k], v.origin[k], inv);
-        const double top = (double)(v.grid[k] - 1);
-        finite = finite && finite_d(fl[k]) && finite_d(fh[k]);
-        outside = outside || fh[k] < 0.0 || fl[k] > top;
-        mine = mine && fl[k] <= own[k] && own[k] <= fh[k];
-    }
-    if (!finite || outside) return 0;
-    if (mine) return -1;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { // (both bounds are finite, fh >= 0 and fl <= grid - 1: the clipped values are voxel indices)
-        const double top = (double)(v.grid[k] - 1);
-        lo[k] = fl[k] < 0.0 ? 0 : (int)fl[k];
-        hi[k] = fh[k] > top ? v.grid[k] - 1 : (int)fh[k];
-    }
-    return 1;
-}
-
 __global__ __launch_bounds__(THREADS) void boxes_kernel(frp_nmpc_peers p, frp_nmpc_peers_box_view v, const double *pos, int stride, double R2, double inv)
 {
     __shared__ double cand_d[WAVES][CAND];
@@ -137,15 +96,6 @@ __global__ __launch_bounds__(THREADS) void check_paths_kernel(frp_nmpc_peers_box
     first_hit[b] = hit;
 }
 
-// the map fields, Q, boxes and count of a view: what the boxes and the path walk both need
-static bool map_ok(const frp_nmpc_peers_box_view *v, long long B)
-{
-    if (!v || v->Q < 0 || !positive(v->resolution) || !v->count || (v->Q > 0 && !v->boxes)) return false;
-    for (int k = 0; k < 3; k++)
-        if (!finite_d(v->origin[k]) || v->grid[k] < 1) return false;
-    return B * v->Q * 6 <= 0x7fffffffLL;
-}
-
 } // namespace peers
 } // namespace frp
 
@@ -154,10 +104,7 @@ extern "C" {
 int frp_nmpc_peers_boxes(const frp_nmpc_peers *p, const frp_nmpc_peers_box_view *v, const double *pos, int stride, void *stream)
 {
     using namespace frp::peers;
-    if (!grid_ok(p) || p->S != 1 || !pos_ok(p, pos, stride) || !map_ok(v, p->B)) return FRP_ERR_ARG;
-    if (v->N < 1 || v->K < 0 || v->K > FRP_PEERS_MAX_STAGES || !non_negative(v->half[0]) || !non_negative(v->half[1]) || !non_negative(v->half[2])) return FRP_ERR_ARG;
-    if (!v->pre_plan || !v->have_traj || (v->K > 0 && !v->stages) || !v->overflow || !v->dropped_own) return FRP_ERR_ARG;
-    if ((long long)p->B * v->N * ROW > 0x7fffffffLL) return FRP_ERR_ARG;
+    if (!boxes_ok(p, v, pos, stride)) return FRP_ERR_ARG;
     if (!device_ok()) return FRP_ERR_NO_DEVICE;
     if (p->B == 0) return FRP_OK;
     return launch(boxes_kernel, (unsigned)((p->B + WAVES - 1) / WAVES), stream, *p, *v, pos, stride, p->R * p->R, 1.0 / v->resolution);

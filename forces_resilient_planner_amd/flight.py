@@ -1,13 +1,13 @@
 """A fleet in flight, on the device: the state machine that drives the planners (FleetFSM), the vehicle that flies their commands
 (Vehicle), the force that acts on it (Disturbance), the errors of what it measures (SensorNoise), the estimator that tells them what it felt (ForceEstimator) and the record of what
-the fleet did (FlightRecord), and what it flies next and what time it is (Mission), and who flies next to whom (FleetPeers) (frp_nmpc_fsm_*, _vehicle_*,
-_disturbance_*, _estimator_*, _flight_*, _sensor_noise_*, _mission_*, _peers_*)."""
+the fleet did (FlightRecord), and what it flies next and what time it is (Mission), and who flies next to whom (FleetPeers) and who yields to whom (RightOfWay) (frp_nmpc_fsm_*, _vehicle_*,
+_disturbance_*, _estimator_*, _flight_*, _sensor_noise_*, _mission_*, _peers_*, _yield_*)."""
 import collections
 import ctypes
 
 from . import layout as L
 from .capi import (COMMAND_STRIDE, DISTURBANCE_EVENT_STRIDE, DISTURBANCE_MAX_EVENTS, DISTURBANCE_MAX_ZONES, DISTURBANCE_ZONE_STRIDE, DisturbanceArgs, FLIGHT_MAX_EDGES, FLIGHT_RESULT_BINS, FLIGHT_STATE_BINS, FLIGHT_SUM_F64, FLIGHT_SUM_INTS, FSM_INIT, MISSION_MAX_TRIES, MissionArgs, OccMapBody, ODOM_BODY, ODOM_WORLD, PEERS_MAX_CELLS, PEERS_MAX_NEAR, PEERS_MAX_STAGES, PEERS_SCAN_CHUNK, PEERS_SUM_INTS, PEERS_SUM_WORDS, PeersArgs, PeersBoxArgs, PeersViewArgs,
-                   SENSOR_NOISE_MAX_FRAMES, SensorNoiseArgs, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, _check,
+                   SENSOR_NOISE_MAX_FRAMES, SensorNoiseArgs, TICK_RUN, VEHICLE_HOLD_STRIDE, VEHICLE_MSG_STRIDE, VEHICLE_STATE, EstimatorArgs, FlightRecordArgs, Fsm, FsmExecIn, VehicleArgs, YieldArgs, _check,
                    checked_ptr, lib, optional_ptr, stream_ptr, tensor_ptr)
 from .fleet import TickState
 from .occmap import OCCMAP_BODY, OCCMAP_FUSE_DEFAULTS, SAFETY_INFLATE_CHECK, SafetyCheck
@@ -36,6 +36,11 @@ SENSOR_NOISE_DEFAULTS = dict(sigma_p=0.0, sigma_v=0.0, sigma_a=0.0, sigma_bias=0
 # times out, a drawn goal lies at goalCallback's z (NM:489) anywhere in the box, is tested as the safety timer tests a goal (ratio 1.2) and
 # gets four candidates per period; the clock's period is the tick's 50 ms
 MISSION_DEFAULTS = dict(arrive_radius=0.3, dwell=0.0, leg_timeout=0.0, z_goal=1.2, min_dist=0.0, max_dist=1.0e6, R=4, inflate_ratio=SAFETY_INFLATE_CHECK, period=0.05)
+
+# CHOSEN, not derived (the reference flies one vehicle): a held planner is released once its nearest outranking peer has been beyond 1 m,
+# or out of the peers' radius, for 4 periods in a row (0.2 s), brakes at 2 m/s^2 to its stop point, and is released whatever its peers do after 200 periods
+# (10 s) -- a hold must not outlive a peer that parked in the way
+RIGHT_OF_WAY_DEFAULTS = dict(r_release=1.0, n_clear=4, a_brake=2.0, hold_timeout=200)
 
 
 class Vehicle:
@@ -914,6 +919,7 @@ class FleetPeers:
         self.stages = t.tensor(self.stage_list, dtype=t.int32, device=dev) if self.stage_list else None
         self._built = None  # (pos, S, stride) of the last build(): what separation() reads
         self.box_rows = self.box_count = self.box_overflow = self.dropped_own = self.path_hit = self._no_goal = self._box_view = None  # boxes() makes them
+        self.outrank_boxes = self.outrank_d2 = None  # ranked_outputs() makes them
 
     def struct(self, S=None, grid=None):
         """The frp_nmpc_peers of a grid of S samples (None: the constructor's) on the buffers `grid` (None: update()'s own)."""
@@ -988,11 +994,14 @@ class FleetPeers:
         _check(lib().frp_nmpc_peers_cloud(ctypes.byref(f), ctypes.byref(v), tensor_ptr(state), stride, s), "frp_nmpc_peers_cloud")
         return view
 
-    def boxes(self, fleet, state, occmap, half, Q=None, stream=None):
+    def boxes(self, fleet, state, occmap, half, Q=None, stream=None, priority=None):
         """frp_nmpc_peers_boxes: a grid of its own (S = 1) of state [B,9] f64, then every planner's peers within R as boxes of occmap's voxels,
         centre -+ half [3] metres (a scalar: every axis), at their positions and at the constructor's stages of fleet.pre_plan.  Q rows per
         planner (None: FRP_PEERS_MAX_NEAR * (1 + stages), which cannot overflow).  Writes box_rows [B,Q,6] int32, box_count, box_overflow and
-        dropped_own [B] int32 -- allocated at the first call, the same tensors afterwards (a captured call replays into them)."""
+        dropped_own [B] int32 -- allocated at the first call, the same tensors afterwards (a captured call replays into them).
+        priority: None -- the call above -- or a [B] int32 device tensor: frp_nmpc_peers_boxes_ranked (section 20), which stamps the stages of
+        a peer's plan only for the planners that peer outranks (a higher priority, or the same and a lower id) and fills outrank_boxes [B]
+        int32 and outrank_d2 [B] f64 (allocated at the first such call)."""
         import math
         t = self.torch
         S, stride = self._samples(state)
@@ -1023,8 +1032,21 @@ class FleetPeers:
         f = self.struct(1, self._grid1)
         s = stream_ptr(stream, like)
         _check(lib().frp_nmpc_peers_build(ctypes.byref(f), tensor_ptr(state), stride, None, s), "frp_nmpc_peers_build")
-        _check(lib().frp_nmpc_peers_boxes(ctypes.byref(f), ctypes.byref(self._box_view), tensor_ptr(state), stride, s), "frp_nmpc_peers_boxes")
+        if priority is None:
+            _check(lib().frp_nmpc_peers_boxes(ctypes.byref(f), ctypes.byref(self._box_view), tensor_ptr(state), stride, s), "frp_nmpc_peers_boxes")
+            return self.box_rows, self.box_count
+        self.ranked_outputs()
+        _check(lib().frp_nmpc_peers_boxes_ranked(ctypes.byref(f), ctypes.byref(self._box_view), tensor_ptr(state), stride, checked_ptr(like, priority, t.int32, (B,)),
+                                                 self.outrank_boxes.data_ptr(), self.outrank_d2.data_ptr(), s), "frp_nmpc_peers_boxes_ranked")
         return self.box_rows, self.box_count
+
+    def ranked_outputs(self):
+        """Makes outrank_boxes (zeros) and outrank_d2 (R * R) exist: boxes(priority=...) and RightOfWay call it (an allocation, once)."""
+        t = self.torch
+        if self.outrank_boxes is None:
+            self.outrank_boxes = t.zeros((self.B,), dtype=t.int32, device=self.device)
+            self.outrank_d2 = t.full((self.B,), self.R * self.R, dtype=t.float64, device=self.device)
+        return self.outrank_boxes, self.outrank_d2
 
     def check_paths(self, planner, fsm=None, stride=5, stream=None):
         """frp_nmpc_peers_check_paths: the safety timer's path walk of planner.kino_path / kino_size (every stride-th sample; fsm.have_traj
@@ -1057,3 +1079,78 @@ class FleetPeers:
         t, f = self.torch, self.struct()
         _check(lib().frp_nmpc_peers_reset(ctypes.byref(f), optional_ptr(self.sep2_min, mask, t.int32, (self.B,)), stream_ptr(stream, self.sep2_min)),
                "frp_nmpc_peers_reset")
+
+
+class RightOfWay:
+    """Who yields to whom, on the device (include/frp_nmpc.h section 20): with FleetPeers.boxes(priority=...) a planner sees the plans of
+    the peers that outrank it alone, and this object makes a planner whose search fails behind such a peer's boxes stop, wait and take up
+    its goal again.  It has no reference counterpart; tests/right_of_way_oracle.py is the statement.  CHOSEN, not derived: the order
+    (priority [B] int32, None: all zero, ties to the lower id); hold means stop, not slow down; the stop point p + v * (|v| / (2 a_brake)) is
+    not checked against the map; release is by distance (r_release) and a count of periods (n_clear), or after hold_timeout periods; a
+    top-ranked planner whose search fails does what the reference does; goalCallback puts z at 1.2 again.
+    Nothing hooks into FleetFSM.period: the caller's period is, inside one graph if it wishes,
+        peers.boxes(fleet, veh.state, occmap, half, priority=row.priority); row.step(veh.state, goal, fresh)
+        peers.check_paths(planner, fsm); fsm.period(..., goal=row.goal, goal_fresh=row.fresh, vehicle=veh)
+    With a Mission a hold counts as a dropped leg: hand mission.goal / mission.fresh to step(), and the planner resumes with the mission's
+    next goal.
+    Owns, device tensors, [B] int32 unless noted: priority (zeros when None), holding, clear_count, hold_age, held_goal [B,3] f64, the outputs
+    goal [B,3] f64 and fresh, the counters holds, releases, timeouts, hold_periods, longest_hold, bad.  Nothing here synchronises; every buffer
+    is allocated in the constructor."""
+
+    INT_FIELDS = ("holding", "clear_count", "hold_age", "fresh", "holds", "releases", "timeouts", "hold_periods", "longest_hold", "bad")
+    F64_FIELDS = ("held_goal", "goal")
+
+    def __init__(self, peers, fsm, planner, priority=None, r_release=None, n_clear=None, a_brake=None, hold_timeout=None):
+        import math
+        t = fsm.torch
+        dev = fsm.state.device
+        self.torch, self.peers, self.fsm, self.planner, self.B = t, peers, fsm, planner, fsm.B
+        if peers.B != self.B or planner.B != self.B:
+            raise ValueError("RightOfWay: the peers, the state machine and the planner are one fleet's")
+        k = dict(RIGHT_OF_WAY_DEFAULTS)
+        k.update({n: v for n, v in (("r_release", r_release), ("n_clear", n_clear), ("a_brake", a_brake), ("hold_timeout", hold_timeout)) if v is not None})
+        self.r_release, self.a_brake, self.n_clear, self.hold_timeout = float(k["r_release"]), float(k["a_brake"]), int(k["n_clear"]), int(k["hold_timeout"])
+        if not (math.isfinite(self.r_release) and self.r_release >= 0.0 and self.a_brake > 0.0 and self.n_clear >= 1 and self.hold_timeout >= 1):
+            raise ValueError("RightOfWay: r_release finite and >= 0, a_brake > 0 (inf allowed), n_clear >= 1, hold_timeout >= 1")
+        if priority is None:
+            self.priority = t.zeros((self.B,), dtype=t.int32, device=dev)
+        else:
+            checked_ptr(fsm.state, priority, t.int32, (self.B,))
+            self.priority = priority
+        for n in self.INT_FIELDS:
+            setattr(self, n, t.zeros((self.B,), dtype=t.int32, device=dev))
+        for n in self.F64_FIELDS:
+            setattr(self, n, t.zeros((self.B, 3), dtype=t.float64, device=dev))
+        peers.ranked_outputs()
+
+    def struct(self, state=None, goal=None, goal_fresh=None):
+        """The frp_nmpc_yield of this object: its parameters, the planner's status, the peers' outrank arrays, the fleet's have_traj where
+        that is another tensor than the state machine's, the tick's cmd_end_pt and the arrays it owns (YieldArgs' field order).  state
+        [B,9] f64, goal [B,3] f64 and goal_fresh [B] int32 are step()'s; without them the struct is what reset() needs."""
+        t, f, like = self.torch, self.fsm, self.fsm.state
+        B = self.B
+        if (goal is None) != (goal_fresh is None):
+            raise ValueError("RightOfWay.step: goal and goal_fresh come together")
+        fleet_have = getattr(f.fleet, "have_traj", None)
+        return YieldArgs(B, self.n_clear, self.hold_timeout, self.r_release, self.a_brake, optional_ptr(like, state, t.float64, (B, 9)),
+                         checked_ptr(like, self.planner.status, t.int32, (B,)), self.peers.outrank_boxes.data_ptr(), self.peers.outrank_d2.data_ptr(),
+                         optional_ptr(like, goal, t.float64, (B, 3)), optional_ptr(like, goal_fresh, t.int32, (B,)),
+                         None if fleet_have is None or fleet_have is f.have_traj else checked_ptr(like, fleet_have, t.int32, (B,)),
+                         checked_ptr(like, f.tick.cmd_end_pt, t.float64, (B, 3)), *[getattr(self, n).data_ptr() for n, _ in YieldArgs._fields_[13:]])
+
+    def arrays(self):
+        """Every state array, output and counter on the host (a synchronising read-back: tests and logs)."""
+        return {n: getattr(self, n).cpu().numpy() for n in self.INT_FIELDS + self.F64_FIELDS}
+
+    def step(self, state, goal=None, goal_fresh=None, stream=None):
+        """frp_nmpc_yield_step on state [B,9] f64 (the odometry), the planner's status, the peers' outrank_boxes / outrank_d2 of the last
+        boxes(priority=...) and the caller's goal [B,3] f64 / goal_fresh [B] int32 (or None for both).  Writes goal and fresh; returns them."""
+        y, f = self.struct(state, goal, goal_fresh), self.fsm.struct()
+        _check(lib().frp_nmpc_yield_step(ctypes.byref(y), ctypes.byref(f), stream_ptr(stream, self.fsm.state)), "frp_nmpc_yield_step")
+        return self.goal, self.fresh
+
+    def reset(self, mask=None, stream=None):
+        """frp_nmpc_yield_reset: where mask [B] int32 != 0 (None: everywhere) nobody holds and every counter is zero."""
+        t, y = self.torch, self.struct()
+        _check(lib().frp_nmpc_yield_reset(ctypes.byref(y), optional_ptr(self.fsm.state, mask, t.int32, (self.B,)), stream_ptr(stream, self.fsm.state)),
+               "frp_nmpc_yield_reset")

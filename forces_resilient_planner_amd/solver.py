@@ -2,7 +2,7 @@
 
 Every function runs HIP kernels on the MI355X; there is no CPU fallback: a missing library or device raises.  The code lives by concern,
 each module importing only the ones before it: capi (structs, macros, signatures, loader), batch (the solve), occmap (the map), planning
-(tube, references, corridor, A*, commands), fleet (the tick), flight (state machine, vehicle, disturbance, sensor noise, estimator, flight record, mission, peers).
+(tube, references, corridor, A*, commands), fleet (the tick), flight (state machine, vehicle, disturbance, sensor noise, estimator, flight record, mission, peers, right of way).
 """
 from .capi import (ABI_VERSION, ASTAR_MAX_PATH, ASTAR_NO_PATH, ASTAR_REACH_END, ASTAR_REACH_END_BUT_SHOT_FAILS, ASTAR_REACH_HORIZON, CHECK_EXPORTS,
                    CMD_INIT_POSITION, CMD_PUB_END, CMD_PUB_TRAJ, CMD_ROTATE_YAW, CMD_WAIT, COMMAND_END, COMMAND_EXPORTS, COMMAND_NONE,
@@ -24,7 +24,7 @@ from .capi import (ABI_VERSION, ASTAR_MAX_PATH, ASTAR_NO_PATH, ASTAR_REACH_END, 
                    VEHICLE_SAT_THRUST_HI, VEHICLE_SAT_THRUST_LO, VEHICLE_SAT_YAW_WRAP, VEHICLE_SAT_ZERO_ACC, VEHICLE_STATE, VIEW_EXPORTS, Astar, Batch,
                    Command, Corridor, CorridorCut, CorridorLarge, DisturbanceArgs, EstimatorArgs, FlightRecordArgs, ForcesInfo, ForcesOutput, ForcesParams, Fsm,
                    FsmExecIn, MissionArgs, OccMap, OccMapBody, OccMapFuse, OccMapFuseBatch, OccMapFusePoints, OccMapRender, OccMapRenderScan, OccMapSharedView,
-                   OccMapView, Options, Pack, PeersArgs, PeersBoxArgs, PeersViewArgs, Reference, SensorNoiseArgs, Tick, TickIn, Tube, VehicleArgs, _PKG, _check, _lib, c_double_p, c_int_p, lib)
+                   OccMapView, Options, Pack, PeersArgs, PeersBoxArgs, PeersViewArgs, Reference, SensorNoiseArgs, Tick, TickIn, Tube, VehicleArgs, YieldArgs, _PKG, _check, _lib, c_double_p, c_int_p, lib)
 from .batch import (DeviceSolver, _registered, default_options, host_register, host_unregister, host_unregister_all, kernel_timing_begin,
                     kernel_timing_end, solve_batch_host, solve_batch_host_begin, solve_batch_host_wait, solver_variant, stage_eval_host)
 from .occmap import (OCCMAP_BODY, OCCMAP_DEFAULTS, OCCMAP_DIST_DEFAULT_R, OCCMAP_FUSE_DEFAULTS, OCCMAP_FUSE_POINTS_PARAMS, SAFETY_INFLATE_CHECK,
@@ -35,4 +35,4 @@ from .planning import (COMMAND_DEFAULTS, CORRIDOR_DEFAULTS, REFERENCE_PI, TUBE_D
                        tube_batch_device, tube_batch_host)
 from .fleet import DeviceFleet, TickState
 from .flight import (ESTIMATOR_DEFAULTS, FSM_EXEC_PERIOD, FSM_EXT_NOISE_BOUND, VEHICLE_DEFAULTS, Disturbance, FleetFSM, FleetPeers, FlightRecord, FlightSummary, ForceEstimator,
-                     MISSION_DEFAULTS, Mission, SENSOR_NOISE_DEFAULTS, SensorNoise, Vehicle)
+                     MISSION_DEFAULTS, Mission, RIGHT_OF_WAY_DEFAULTS, RightOfWay, SENSOR_NOISE_DEFAULTS, SensorNoise, Vehicle)

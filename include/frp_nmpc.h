@@ -662,6 +662,78 @@ int FORCESNLPsolver_normal_solve(frp_forces_params *params, frp_forces_output *o
 int FORCESNLPsolver_final_solve(frp_forces_params *params, frp_forces_output *output, frp_forces_info *info,
                                 FILE *fs, frp_forces_extfunc evalextfunctions);
 
+/* ---- (20) right of way: an order among vehicles, boxes that respect it, and the rule that makes the loser stop, wait and go on ---- */
+/* (Declared here, ahead of section (19), for that section's reasons: its exports stay in front of section (15)'s.  The two structs of
+ * sections (18) and (19) and the state machine's are named by their tags.)
+ * Section (19) is symmetric: two planners on crossing legs stamp each other's plan across their own, both searches fail, both fly on.
+ * This section breaks the symmetry.  Everything is opt-in: no existing call launches other code than it did, no existing struct changed,
+ * same ABI version.  NO REFERENCE COUNTERPART (the reference flies one vehicle); tests/right_of_way_oracle.py is the executable statement
+ * and csrc/frp_peers_yield.hip, built without contraction, agrees with it to the bit.
+ *
+ * THE ORDER.  q OUTRANKS b iff priority[q] > priority[b], or they are equal and q < b; priority NULL is all zero (the lower id wins).
+ * Strict and total, so "yields to" has no cycle.  CHOSEN, not derived.
+ *
+ * RANKED BOXES.  frp_nmpc_peers_boxes with one difference: of a kept peer q of planner b, the centre at q's CURRENT POSITION is always
+ * taken (a body is a fact), the centres at the stages of q's plan only where q outranks b (an intention binds only those who must
+ * yield to it).  Peers and their order, the bounds, the drop order, the clip, the storage order, count, overflow and dropped_own are
+ * section (19)'s, operation for operation.  Two more arrays:
+ *   outrank_boxes[b] <- the kept boxes (the n of section 19, whether or not n fits Q) that belong to peers outranking b
+ *   outrank_d2[b]    <- the smallest d2 (the selection's key) from b to a kept peer that outranks it, or R * R where there is none
+ * A planner every one of whose peers outranks it gets frp_nmpc_peers_boxes' rows; one that outranks all its peers gets that call's rows
+ * with K = 0.
+ * FRP_ERR_ARG: whatever frp_nmpc_peers_boxes refuses; outrank_boxes or outrank_d2 NULL. */
+struct frp_nmpc_peers;
+struct frp_nmpc_peers_box_view;
+int frp_nmpc_peers_boxes_ranked(const struct frp_nmpc_peers *p, const struct frp_nmpc_peers_box_view *v, const double *pos, int stride,
+                                const int *priority, int *outrank_boxes, double *outrank_d2, void *stream);
+
+/* HOLD AND RELEASE, one thread per planner, applied in this order (r2 = r_release * r_release, one product):
+ *   goals in   where fresh_in[b] != 0: a HOLDING planner latches goal_in into held_goal and fresh[b] <- 0; any other gets goal[b] <- goal_in[b],
+ *              fresh[b] <- 1.  Elsewhere (and with goal_in / fresh_in NULL) fresh[b] <- 0 and goal[b] stays.
+ *   enter      a planner that is not holding and got no fresh goal, with astar_status[b] == FRP_ASTAR_NO_PATH, outrank_boxes[b] > 0 and a
+ *              state other than EXEC_TRAJ.  Its odometry p = state[b][0..2], v = state[b][3..5] not finite: bad[b] += 1 and nothing else.
+ *              Otherwise  stop = p + v * (sqrt((vx vx + vy vy) + vz vz) / (2.0 * a_brake))  (a_brake = +inf: p itself), and
+ *                held_goal <- end_pt;  astar_status[b] <- 0 (the verdict is consumed: 0 is what a planner holds before its first search
+ *                and no code the search writes);  have_target <- 0, state <- WAIT_TARGET, exec_mpc <- 0, plan_fail_count <- 0, have_traj <- 0
+ *                (and fleet_have_traj where given) -- the reference's arrival stores --, cmd_status <- PUB_END, pub_end <- 1,
+ *                cmd_end_pt <- stop;  holding <- 1, holds += 1, hold_age <- clear_count <- 0.  The step ends here for this planner.
+ *   holding    (a planner that was holding when the step began)  hold_age += 1, hold_periods += 1, longest_hold <- max(longest_hold, hold_age);
+ *              clear iff outrank_d2[b] > r2 or outrank_boxes[b] == 0: clear_count += 1, else clear_count <- 0;
+ *              released when clear_count >= n_clear, or else when hold_age >= hold_timeout (timeouts += 1):
+ *                goal[b] <- held_goal, fresh[b] <- 1, holding <- 0, releases += 1 -- frp_nmpc_fsm_goal then does the rest as for any goal.
+ * CHOSEN, not derived: hold means stop, not slow down; the brake formula; release is by distance and a count of periods; a top-ranked
+ * planner whose search fails has nobody to yield to (outrank_boxes is 0) and does what the reference does; the stop point is not
+ * checked against the map; goalCallback puts z at 1.2 again. */
+typedef struct frp_nmpc_yield {
+    int B, n_clear, hold_timeout; /* planners (>= 1, the state machine's B); consecutive clear steps to a release (>= 1); steps to a timeout (>= 1) */
+    double r_release, a_brake;    /* metres, finite and >= 0; metres / s^2, > 0, +inf allowed                                                    */
+    const double *state;          /* [B][9] the odometry                                                                                       */
+    int *astar_status;            /* [B] in / out: frp_nmpc_astar.status                                                                       */
+    const int *outrank_boxes;     /* [B] of frp_nmpc_peers_boxes_ranked                                                                        */
+    const double *outrank_d2;     /* [B]                                                                                                       */
+    const double *goal_in;        /* [B][3] or NULL: the caller's goals ...                                                                    */
+    const int *fresh_in;          /* [B] or NULL: ... and which of them are messages; both or neither                                          */
+    int *fleet_have_traj;         /* [B] or NULL: have_mpc_traj_ (frp_nmpc_peers_box_view.have_traj), cleared with the state machine's         */
+    double *cmd_end_pt;           /* [B][3] frp_nmpc_tick.cmd_end_pt                                                                           */
+    int *holding, *clear_count, *hold_age;                                /* [B] state                                                         */
+    double *held_goal;                                                    /* [B][3]                                                            */
+    double *goal;                                                         /* [B][3] out: what frp_nmpc_fsm_goal takes                          */
+    int *fresh;                                                           /* [B] out                                                           */
+    int *holds, *releases, *timeouts, *hold_periods, *longest_hold, *bad; /* [B] counters                                                      */
+} frp_nmpc_yield;
+
+/* The rule above for every planner.  One launch, no LDS, no atomics.  Of f it reads and writes state, have_target, have_traj, exec_mpc,
+ * plan_fail_count, cmd_status, pub_end and reads end_pt.
+ * FRP_ERR_ARG: y or f NULL; B < 1 or other than f->B; one of those fields of f NULL; n_clear or hold_timeout < 1; r_release not finite or
+ * negative; a_brake not above 0 (a NaN); state, astar_status, outrank_boxes, outrank_d2, cmd_end_pt or one of y's own arrays NULL;
+ * exactly one of goal_in and fresh_in NULL. */
+struct frp_nmpc_fsm;
+int frp_nmpc_yield_step(const frp_nmpc_yield *y, const struct frp_nmpc_fsm *f, void *stream);
+
+/* Where mask (or NULL: everywhere) [b] != 0: holding, clear_count, hold_age, held_goal, goal, fresh and the six counters <- 0.
+ * FRP_ERR_ARG: y NULL, B < 1 or one of those arrays NULL. */
+int frp_nmpc_yield_reset(const frp_nmpc_yield *y, const int *mask, void *stream);
+
 /* ---- (19) peer avoidance: a planner's peers as boxes of map voxels, for the A* and for the safety timer's path walk ---- */
 /* (Declared here, ahead of section (15), for section (18)'s reasons: the exports of sections (15), (18), (16), (17) and (14) stay
  * neighbours in that order and the flight record's stay the last.  frp_nmpc_peers is section (18)'s struct, named by its tag.)
@@ -1221,7 +1293,7 @@ int frp_nmpc_flight_summary(const frp_nmpc_flight_record *rec, const double *min
                             const double *edges, long long *out_i, double *out_f, long long *hist, void *workspace, size_t workspace_bytes,
                             void *stream);
 
-/* (Sections (19), peer avoidance, (15), the disturbance, (18), the fleet peers, (16), the sensor noise, and (17), the mission, are declared
+/* (Sections (20), right of way, (19), peer avoidance, (15), the disturbance, (18), the fleet peers, (16), the sensor noise, and (17), the mission, are declared
  * ahead of section (14), above.) */
 
 #ifdef __cplusplus
